@@ -19,12 +19,24 @@ N GPUs run N independent env shards (weak scaling, no data-path collective).  ``
 without a launcher spawns the N ranks itself (torch.distributed.run, 127.0.0.1); under an
 external launcher WORLD_SIZE must equal N.  Rank 0 prints one JSON line.
 
-Extra keys: fp32 sim-only, the same window as one open-loop tape launch (hs_step_tape),
-full-episode legs on tapes T0/T1/T2, rollout (+ PPO.collect_rollouts fused vs
-per-step) / train / GAE, configs[3]/[4] (+ tape and fused-collect variants), the step-kernel
-roofline (HBM bytes vs 8 TB/s, live HIP events on the launch stream) and the CPU baseline (the
+A plain run (``--gpus 1 --steps N --warmup W``) does only what the headline needs: set up, stagger
+the episode phases, warm up, time the N steps, write the last timed step's outputs if
+``--dump-outputs DIR`` is given, and print the line (with the step-kernel roofline: HBM bytes vs
+8 TB/s from the HIP events recorded around the timed steps, no run of its own).
+
+``--dump-outputs DIR`` writes what the last timed ``step_tensors`` call returned on rank 0 -- obs,
+reward, terminated, truncated -- as ``DIR/<name>.npy`` (obs / reward in the run's precision, the
+flags as float32).  Seeds, reset noise and the action tape are fixed by the arguments, so two builds
+run with the same arguments can be compared array for array.  Above 64 MB in all (large ``--envs``)
+a fixed, seeded sample of env rows is written, with its indices as ``env_index.npy``.
+
+``--full`` adds the extra keys: the aux-row statistics of three further steps (sim_stats), fp32
+sim-only, the same window as one open-loop tape launch (hs_step_tape), full-episode legs on tapes
+T0/T1/T2, rollout (+ PPO.collect_rollouts fused vs per-step) / train / GAE, the drop-in
+numpy surfaces, configs[3]/[4] (+ tape and fused-collect variants) and the CPU baseline (the
 reference's n_envs=8 SubprocVecEnv path, on the oracle's fp64 C restatement of mj_step because
-MuJoCo is not installable: kind "port").
+MuJoCo is not installable: kind "port"); each has a ``--no-...`` switch.  Without ``--full`` those
+keys are null.
 """
 import argparse
 import json
@@ -188,6 +200,29 @@ def selftest_launch(args, world, rank):
         dist.destroy_process_group()
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays):
+    """Write per-env arrays (name -> [N, ...] tensor or ndarray) as ``out_dir/<name>.npy``: float64
+    stays float64, everything else becomes float32.  If they exceed DUMP_BUDGET_BYTES together, the
+    same fixed, seeded sample of env rows of each is written, plus its indices (env_index.npy)."""
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    n_rows = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, n_rows) for a in host.values()) + 4     # + env_index
+    if n_rows * row_bytes > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n_rows, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+        host = {name: a[keep] for name, a in host.items()}
+        host["env_index"] = keep.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- GPU
 def main():
     ap = argparse.ArgumentParser()
@@ -197,6 +232,12 @@ def main():
     ap.add_argument("--envs", type=int, default=N_ENVS_PER_GPU, help="envs per GPU")
     ap.add_argument("--precision", default="fp64", choices=["fp32", "fp64"],
                     help="headline arithmetic (fp64 = the reference's mjtNum; fp32 is an extra leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs (CPU baseline, sim_stats, fp32, tape, episodes, rollout, train, "
+                         "GAE, drop-in, configs[3]/[4]); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (obs, reward, terminated, truncated; rank 0) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--schedule", default="auto", help=argparse.SUPPRESS)   # A/B runs (HsBatch.configure)
     ap.add_argument("--no-rollout", action="store_true")
@@ -222,6 +263,8 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=60000, help="vec steps of the CPU baseline (~13 s)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -233,7 +276,7 @@ def main():
     if args.selftest_launch:
         return selftest_launch(args, world, rank)
     cpu_res = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(vec_steps=args.cpu_steps)   # before any GPU/torch init (fork-safe)
 
     import torch
@@ -305,7 +348,8 @@ def main():
 
     def timed(e, tape, steps, warmup, offset=0):
         """warm-up, then ``steps`` env steps bracketed by barrier + synchronize; returns
-        (wall seconds max over ranks, HIP-event ms per step on the launch stream)."""
+        (wall seconds max over ranks, HIP-event ms per step on the launch stream, the last step's
+        outputs: device views valid until the batch's next step)."""
         for k in range(warmup):
             e.step_tensors(tape[(offset + k) % tape.shape[0]])
         barrier()
@@ -313,10 +357,10 @@ def main():
         t0 = time.perf_counter()
         ev0.record(stream)
         for k in range(steps):
-            e.step_tensors(tape[(offset + warmup + k) % tape.shape[0]])
+            out = e.step_tensors(tape[(offset + warmup + k) % tape.shape[0]])
         ev1.record(stream)
         barrier()
-        return max_over_ranks(time.perf_counter() - t0), ev0.elapsed_time(ev1) / steps
+        return max_over_ranks(time.perf_counter() - t0), ev0.elapsed_time(ev1) / steps, out
 
     def timed_tape(e, tape, steps, warmup, offset=0, chunk=None):
         """The same window as ``timed`` as ONE tape launch (HsBatch.step_tape: K env steps, each env
@@ -338,7 +382,7 @@ def main():
             e.batch.step_tape(tp[c:c + chunk], outputs=True)
         ev1.record(stream)
         barrier()
-        return max_over_ranks(time.perf_counter() - t0), ev0.elapsed_time(ev1) / steps
+        return max_over_ranks(time.perf_counter() - t0), ev0.elapsed_time(ev1) / steps, None
 
     def ints_over_ranks(vals, op):
         """elementwise MAX / SUM of a list of per-rank integer counters over all ranks"""
@@ -376,19 +420,21 @@ def main():
     tape = make_tape("T1", 1024, n, 1 + rank)
     env = make_env(args.precision, 1000)
     precondition(env, tape)
-    elapsed, step_ms = timed(env, tape, args.steps, args.warmup, offset=EPISODE)
+    elapsed, step_ms, last_out = timed(env, tape, args.steps, args.warmup, offset=EPISODE)
     value = n * args.steps * ranks / elapsed
-    stats = stats_of(env, tape, EPISODE + args.warmup + args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("obs", "reward", "terminated", "truncated"), last_out)))
+    stats = stats_of(env, tape, EPISODE + args.warmup + args.steps) if args.full else None
     kernel_ms = step_ms
     queued = env.batch.queued()
     env.close()
 
     # ---- fp32 sim-only leg (the throughput engine; tolerance-based parity, not the headline)
     fp32_leg = None
-    if args.precision == "fp64" and not args.no_fp32:
+    if args.full and args.precision == "fp64" and not args.no_fp32:
         e = make_env("fp32", 5000)
         precondition(e, tape)
-        el, ms = timed(e, tape, args.steps, args.warmup, offset=EPISODE)
+        el, ms, _ = timed(e, tape, args.steps, args.warmup, offset=EPISODE)
         fp32_leg = dict(value=n * args.steps * ranks / el, unit="env_steps/s", dtype="f32", steps=args.steps,
                         kernel_ms_per_launch=ms, stats=stats_of(e, tape, EPISODE + args.warmup + args.steps),
                         note="same workload and staggered episode mix, fp32 engine (parity within fp32 tolerances, "
@@ -398,10 +444,10 @@ def main():
     # ---- open-loop tape leg: the same fp64 window as one tape launch (not the headline: a policy in
     # the loop steps one env step per launch)
     tape_leg = None
-    if not args.no_tape:
+    if args.full and not args.no_tape:
         e = make_env(args.precision, 1000)
         precondition(e, tape)
-        el, ms = timed_tape(e, tape, args.steps, args.warmup, offset=EPISODE)
+        el, ms, _ = timed_tape(e, tape, args.steps, args.warmup, offset=EPISODE)
         tape_leg = dict(value=n * args.steps * ranks / el, unit="env_steps/s", dtype="f64" if args.precision == "fp64"
                         else "f32", steps=args.steps, ms_per_env_step=ms, tape_aborts=e.batch.tape_aborts(),
                         note="same workload, window and action tape as the headline, all timed env steps in ONE "
@@ -412,7 +458,7 @@ def main():
 
     # ---- full episodes from a synchronized reset on tapes T0 / T1 / T2, per phase
     episodes = None
-    if not args.no_episodes:
+    if args.full and not args.no_episodes:
         episodes = {}
         phases = [(0, 50), (50, 100), (100, 200), (200, 300), (300, 400), (400, 500), (500, 600), (600, EPISODE)]
         for kind in ("T0", "T1", "T2"):
@@ -438,7 +484,7 @@ def main():
 
     # ---- rollout mode: policy MLP[256,256] forward + sampling + env step (on device)
     rollout = None
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         from mujocoposelearning_amd.ppo import ActorCritic, ppo_act
         e = make_env(args.precision, 7000)
         precondition(e, tape)
@@ -508,7 +554,7 @@ def main():
     # HumanoidVecEnv, numpy actions in, numpy obs / rewards / dones / infos out; custom_env.py:152-230
     # HumanoidEnv.step for one env), PCIe-inclusive
     dropin = None
-    if not args.no_dropin:
+    if args.full and not args.no_dropin:
         from mujocoposelearning_amd.env import HumanoidEnv
         dropin = {}
         rng_np = np.random.default_rng(3 + rank)
@@ -580,13 +626,13 @@ def main():
     # ---- BASELINE.json configs[3] (kneeling reward, 4096 envs) and configs[4] (full-state obs,
     # 8192 envs over 8 GPUs = 1024 per GPU): same staggered sim-only protocol
     config_legs = None
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         def leg(cfg_x, n_x, label):
             e = make_env(args.precision, 4000, cfg_x=cfg_x, n_x=n_x)
             tp = tape[:, :n_x] if n_x <= n else make_tape("T1", 1024, n_x, 5)
             precondition(e, tp)
             ks = min(args.steps, 50)
-            el, _ = timed(e, tp, ks, args.warmup, offset=EPISODE)
+            el, _, _ = timed(e, tp, ks, args.warmup, offset=EPISODE)
             r = dict(value=n_x * ks * ranks / el, unit="env_steps/s", n_envs_per_gpu=n_x, obs_dim=e.obs_dim,
                      workload=label)
             e.close()
@@ -614,7 +660,7 @@ def main():
             if not args.no_tape:   # the same window as one open-loop tape launch
                 e = make_env(args.precision, 4000, cfg_x=cfg_x, n_x=n_x)
                 precondition(e, tp)
-                elt, _ = timed_tape(e, tp, ks, args.warmup, offset=EPISODE)
+                elt, _, _ = timed_tape(e, tp, ks, args.warmup, offset=EPISODE)
                 r["tape"] = dict(value=n_x * ks * ranks / elt, unit="env_steps/s", tape_aborts=e.batch.tape_aborts())
                 e.close()
             return r
@@ -629,7 +675,7 @@ def main():
     # ---- train mode (SURVEY 8d iii): end-to-end on-device PPO iterations (rollout with the
     # MLP[256,256] policy + GAE + clipped-surrogate updates with the per-step gradient all-reduce)
     train_res = None
-    if args.train_iters > 0:
+    if args.full and args.train_iters > 0:
         from mujocoposelearning_amd.ppo import PPO
         e = make_env(args.precision, 8000)
         tk = dict(n_steps=32, batch_size=32768, n_epochs=4, learning_rate=3e-4, stagger_episodes=True,
@@ -685,7 +731,7 @@ def main():
 
     # ---- GAE leg: the rollout-end reverse scan (hs_gae) over an n_steps=2048 x n-env buffer
     gae_res = None
-    if not args.no_gae:
+    if args.full and not args.no_gae:
         from mujocoposelearning_amd.ppo import gae_device
         Tg = 2048
         gg = torch.Generator(device=dev).manual_seed(11)
@@ -802,7 +848,7 @@ def run_protocol(args, rank, world, ranks, make_env, make_tape, precondition, ti
         for seed in (0, 1, 2):
             tp = make_tape(kind, 1024, args.envs, 100 * seed + rank)
             e = make_env(args.precision, seed)
-            el, ms = timed(e, tp, 10000, 1000)
+            el, ms, _ = timed(e, tp, 10000, 1000)
             res[f"{kind}/seed{seed}"] = dict(value=args.envs * 10000 * ranks / el, kernel_ms_per_launch=ms,
                                              stats=stats_of(e, tp, 11000))
             e.close()

@@ -8,7 +8,7 @@ TAG=${1:-r6_rollout}
 OUT=gpurun_out/prof_${TAG}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-BENCH="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-rollout --no-gae --train-iters 2 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin --no-precondition"
+BENCH="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-rollout --no-gae --train-iters 2 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin --no-precondition"
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/bench_trace.log" 2>&1 || exit 21
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o fetch -- $BENCH > "$OUT/bench_fetch.log" 2>&1 || exit 22
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -o write -- $BENCH > "$OUT/bench_write.log" 2>&1 || exit 23

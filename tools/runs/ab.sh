@@ -14,7 +14,7 @@ L=$GRAFT_REPO_ROOT/mujocoposelearning_amd
 for v in "$@"; do
   case $v in env:*) ;; *) [ -f $L/libhsim_$v.so ] || { echo "missing libhsim_$v.so"; exit 2; } ;; esac
 done
-B="python bench.py ${BENCH_ARGS:---steps 50 --warmup 5 --no-cpu-baseline --no-rollout --no-gae --train-iters 0 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin}"
+B="python bench.py ${BENCH_ARGS:---full --steps 50 --warmup 5 --no-cpu-baseline --no-rollout --no-gae --train-iters 0 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin}"
 name() { case $1 in env:*) echo $1 | sed 's/^env://; s/[^A-Za-z0-9]/_/g' ;; *) echo $1 ;; esac; }
 for i in 1 2 3; do
   timeout -k 10 300 $B > $O/ab_def_$i.log 2>&1 || exit 3

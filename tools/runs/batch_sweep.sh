@@ -6,6 +6,6 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG
 mkdir -p $O
 for n in 4096 8192 16384 32768; do
-  timeout -k 10 400 python bench.py --envs $n --steps 20 --warmup 5 --no-cpu-baseline --no-rollout --no-gae --train-iters 0 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin > $O/envs_$n.log 2>&1 || exit 3
+  timeout -k 10 400 python bench.py --full --envs $n --steps 20 --warmup 5 --no-cpu-baseline --no-rollout --no-gae --train-iters 0 --no-configs --no-fp32 --no-episodes --no-tape --no-dropin > $O/envs_$n.log 2>&1 || exit 3
 done
 grep -o '"value": [0-9.]*' $O/envs_*.log

@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-me
 rc=$?
 echo "pytest rc $rc" >> $O/gputest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit 3; fi
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench.log 2>&1 || exit 4
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.log 2>&1 || exit 4
 bash profiles/collect.sh $TAG fp64 > $O/collect.log 2>&1 || exit 5
 bash profiles/collect_rollout.sh ${TAG}_rollout > $O/collect_rollout.log 2>&1 || exit 6
 bash profiles/census.sh $TAG > $O/census.log 2>&1 || exit 7

@@ -5,4 +5,4 @@ TAG=${1:?usage: rehearse_2rank.sh TAG}
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG
 mkdir -p $O
-HSIM_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-episodes --cpu-steps 100 > $O/bench_2rank_gloo.log 2>&1 || exit 4
+HSIM_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-episodes --cpu-steps 100 > $O/bench_2rank_gloo.log 2>&1 || exit 4
