@@ -218,7 +218,7 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
 
 // -- tape launches (hs_step_tape, hs_rollout) --------------------------------------------------
 // Each env finishes at most one episode per tape launch (its terminal obs / info rows are then written
-// once, see hs_kernels.hip step_pair): launches of at most the shortest episode's length.  An episode
+// once, see hs_env_step.h step_pair): launches of at most the shortest episode's length.  An episode
 // starts at time = one timestep (the reset's mj_step) and ends at time >= duration (custom_env.py:213)
 // or at max_steps.
 int min_episode_len(const hs_batch* b) {
@@ -328,7 +328,7 @@ bool init_state(hs_batch* b) {
          hip_ok(hipMemset(b->redo_total, 0, sizeof(unsigned long long)), "init") &&
          hip_ok(hipMemset(b->qsync, 0, hs::qsync_words(N) * sizeof(int)), "init") &&
          // a recycled UC block holds another batch's rows: a lost hand-off reads this row's warning
-         // counters and time (hs_kernels.hip step_pair), so they start at 0, not at stale bits
+         // counters and time (hs_env_step.h step_pair), so they start at 0, not at stale bits
          hip_ok(hipMemset(b->mid, 0, (size_t)N * hs::MIDDIM * es), "init");
 }
 
@@ -483,7 +483,7 @@ hs_batch* hs_batch_create(const hs_model* m, int n_envs, int device, uint64_t se
       !hip_ok(hipMalloc((void**)&b->redo_total, sizeof(unsigned long long)), "hipMalloc(redo_total)") ||
       // chunk-queue hand-off rows, claim counters and pair flags: UNCACHED device memory from the UC
       // pool above, so a hand-off between waves on different CUs / XCDs needs no L2 write-back or
-      // invalidate (hs_kernels.hip step_pair)
+      // invalidate (hs_env_step.h step_pair)
       !(uc_alloc(device, N * hs::MIDDIM * es, &b->mid) ? true
           : (g_err = "hipExtMallocWithFlags(mid, uncached) failed", false)) ||
       !(uc_alloc(device, hs::qsync_words((int)N) * sizeof(int), (void**)&b->qsync) ? true
@@ -627,7 +627,7 @@ int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_o
                                                : hs::resident_waves<float>(h.solver == 1);
   const bool tape_sched = b->cfg.schedule == HS_SCHED_AUTO || b->cfg.schedule == HS_SCHED_FIXED_ORDER;
   // without auto-reset a finished env keeps rewriting its terminal info every step (one launch
-  // must write each batch address once, see hs_kernels.hip step_pair): step by step
+  // must write each batch address once, see hs_env_step.h step_pair): step by step
   if (n_steps == 1 || !tape_sched || !b->cfg.autoreset || resident <= 0 || !b->mid || !b->qsync) return per_step();
   // one launch covers at most the shortest episode and at most QTAG_STEPS steps (its hand-off tags)
   const int min_len = std::min(min_episode_len(b), hs::QTAG_STEPS);

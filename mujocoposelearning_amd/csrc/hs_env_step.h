@@ -1,0 +1,761 @@
+// The env layer around mj_step: bad-state checks and reset (custom_env.py:97-150), the reward
+// plug-ins (reward_functions.py:66-261), the 352-dim obs (custom_env.py:232-261), the fused
+// rollout's policy forward, the per-env commit, and step_pair -- one env step (custom_env.py:152-230)
+// of a wave's env pair, which every step kernel inlines once.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "hs_philox.h"
+#include "hs_stepper.h"
+
+namespace hs {
+namespace {
+
+// ------------------------------------------------------------------ state helpers
+__device__ __forceinline__ uint64_t splitmix(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+template <typename T>
+__device__ __forceinline__ T uniform_pm(uint64_t seed, int env, uint32_t episode, int k, T scale) {
+  uint64_t h = splitmix(seed ^ splitmix(((uint64_t)env << 32) ^ ((uint64_t)episode << 8) ^ (uint64_t)k));
+  double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);   // [0, 1)
+  return (T)(-scale + 2.0 * scale * u);
+}
+
+template <typename T, typename C>
+__device__ __forceinline__ void reset_state(MPtr<T> m, Scratch<T, C>& s, int sl, T& time, T& xws) {
+  if (sl < m->nq) s.qpos[sl] = m->qpos0[sl];
+  if (sl + HL < m->nq) s.qpos[sl + HL] = m->qpos0[sl + HL];
+  if (sl < m->nv) s.qvel[sl] = 0;
+  if (sl < m->nu) s.ctrl[sl] = 0;
+  xws = 0;
+  time = 0;
+  WSYNC();
+}
+
+template <typename T, int NV, bool PGS, typename C>
+__device__ __forceinline__ void physics_step(Stepper<T, NV, C>& st, KPtr<T> k, T& time, T& xws, int* warn,
+                                             PgsCache<T, C>* pc) {
+  MPtr<T> m = st.m;
+  Scratch<T, C>& s = st.s;
+  const int sl = st.sl;
+  const bool up = st.up;
+  // mj_checkPos / mj_checkVel (auto-reset to qpos0, time 0)
+  bool bq = (sl < m->nq && isbad(s.qpos[sl])) || (sl + HL < m->nq && isbad(s.qpos[sl + HL]));
+  bool bv = sl < m->nv && isbad(s.qvel[sl]);
+  if (hballot(bq, up)) { warn[WARN_BADQPOS]++; reset_state(m, s, sl, time, xws); }
+  else if (hballot(bv, up)) { warn[WARN_BADQVEL]++; reset_state(m, s, sl, time, xws); }
+  T D[C::RPL], ar[C::RPL], rc[C::RPL];
+  int rd[C::RPL];
+  for (int attempt = 0; attempt < 2; attempt++) {
+    HS_STAMP(st.clk, 0);
+    st.kinematics();
+    HS_STAMP(st.clk, 1);
+    if (st.collision()) warn[WARN_OVERFLOW]++;
+    HS_STAMP(st.clk, 4);
+    st.mass_matrix();
+    HS_STAMP(st.clk, 2);
+    st.velocity_forces();
+    HS_STAMP(st.clk, 3);
+    if (st.rows(D, ar, rd, rc)) warn[WARN_OVERFLOW]++;
+    HS_STAMP(st.clk, 5);
+    if constexpr (PGS)
+      st.solve_pgs(xws, opaque(k)->p.max_newton, D, ar, rd, rc, *pc);
+    else
+      st.solve(xws, opaque(k)->p.max_newton, sizeof(T) == 8 ? T(1e-13) : T(1e-7), D, ar, rd, rc);
+    bool ba = sl < m->nv && isbad(st.qacc);
+    bool redo = hballot(ba, up) != 0 && attempt == 0;
+    if (__ballot(redo) == 0) break;          // wave-uniform loop control
+    if (redo) {                               // mj_checkAcc: reset and redo mj_forward
+      warn[WARN_BADQACC]++;
+      reset_state(m, s, sl, time, xws);
+    }
+  }
+  if (opaque(k)->p.full_state) st.post_constraint();   // pre-integration state, like cinert / cvel in the obs
+  st.euler(time);
+  HS_STAMP(st.clk, 13);
+  xws = st.qacc;
+}
+
+// sum |cfrc_ext| of the last two bodies ("feet", reward_functions.py:121-122,176-177)
+template <typename T, typename C>
+__device__ __forceinline__ void foot_forces(MPtr<T> m, const Scratch<T, C>& s, T& lf, T& rf) {
+  const int nb = m->nbody;
+  lf = 0;
+  rf = 0;
+  for (int k = 0; k < 6; k++) { lf += fabs(s.u.n.cfrc[nb - 2][k]); rf += fabs(s.u.n.cfrc[nb - 1][k]); }
+}
+
+// The reward plug-ins' inputs, gathered per env.  The step kernel fills them from its scratch
+// (compute_reward below); hs_reward_eval (reward_eval_kernel) from caller-supplied fields.  Both run
+// the same reward_formula, so the device formulas are pinned directly by the reference's golden vectors.
+template <typename T>
+struct RewardIn {
+  T h, qw, qx, qy, qz;   // qpos[2], qpos[3:7]
+  T vx;                  // qvel[0]
+  T time;
+  T com0, com1;          // subtree_com[0][0:2]
+  T comv;                // sum(subtree_linvel[0]^2), numpy order (sequential: 3 < 8 terms)
+  T lf, rf;              // sum |cfrc_ext[-2]|, sum |cfrc_ext[-1]| (numpy order: sequential over 6)
+  T energy;              // sum((qfrc_actuator[-nj:] * qvel[6:])^2), numpy's pairwise order (np_sum_half)
+  T ctrl_sq;             // sum(ctrl^2), numpy's pairwise order
+};
+
+// reward_functions.py:66-261 + utils.py:3-21, each expression in the reference's own association
+// and without FMA contraction, so the only difference to numpy is the device libm (exp / atan2 / asin).
+// The reference's Python min(a, b) is `b if b < a else a` (a NaN first operand is returned as is).
+template <typename T, typename KP>
+__device__ __forceinline__ T reward_formula(int reward_id, KP kn, const RewardIn<T>& in) {
+#pragma clang fp contract(off)
+  const T w = in.qw, x = in.qx, y = in.qy, z = in.qz;
+  const T roll = atan2(T(2) * (w * x + y * z), T(1) - T(2) * (x * x + y * y));
+  const T pitch = asin(T(2) * (w * y - z * x));   // not clamped: |sinp| > 1 -> NaN, as np.arcsin
+  const T h = in.h;
+  auto pymin = [](T a, T b) { return b < a ? b : a; };
+  if (reward_id == REWARD_STAND || reward_id == REWARD_WALK) {
+    const T hd = h - T(1.282);
+    const T height_reward = exp(T(-2.0) * (hd * hd));
+    const T orientation_reward = exp(T(-3.0) * (roll * roll + pitch * pitch));
+    const T posture = T(0.5) * height_reward + T(0.5) * orientation_reward;
+    const T torque = exp(T(-0.05) * in.ctrl_sq);
+    if (reward_id == REWARD_STAND) {                       // :156-211
+      if (h < T(0.8)) return T(0);
+      const T vd = in.vx - T(1.0);
+      const T vr = exp(T(-2.0) * (vd * vd));
+      const T total = in.lf + in.rf + T(1e-8);
+      const T foot = T(1.0) - pymin(in.lf, in.rf) / total;
+      return T(0.4) * vr + T(0.3) * posture + T(0.2) * foot + T(0.1) * torque;
+    }
+    if (h < T(0.8)) return T(0.1) * h / T(0.8);           // :213-261
+    const T vd = in.vx - T(10.0);
+    const T vr = exp(T(-0.5) * (vd * vd));
+    return vr + posture * torque;
+  }
+  if (reward_id == REWARD_KNEELING) {                      // :66-154
+    // kn: target_height, min_height, max_roll_pitch, com_radius, energy_w, posture_w, com_w, foot_w, alive_w
+    if (h < T(kn[1])) return h * h;
+    const T mrp = T(kn[2]);
+    const T orientation_error = (roll * roll + pitch * pitch) / (mrp * mrp);
+    const T posture_reward = exp(T(-5.0) * orientation_error);
+    const T hd = h - T(kn[0]);
+    const T height_reward = exp(T(-5.0) * (hd * hd));
+    const T posture = T(0.7) * posture_reward + T(0.3) * height_reward;
+    const T dist = sqrt(in.com0 * in.com0 + in.com1 * in.com1);
+    const T com = T(0.7) * exp(T(-10.0) * (dist / T(kn[3]))) + T(0.3) * exp(T(-0.1) * in.comv);
+    const T total = in.lf + in.rf + T(1e-8);
+    const T foot = pymin(in.lf, in.rf) / total;
+    const T energy = exp(T(-0.01) * in.energy);
+    const T alive = T(1.0) - exp(T(-0.5) * in.time);
+    return T(kn[5]) * posture + T(kn[6]) * com + T(kn[7]) * foot + T(kn[4]) * energy + T(kn[8]) * alive;
+  }
+  return T(0);
+}
+
+// the step kernel's reward: inputs from the env's scratch.  cfrc_ext and subtree_linvel are never
+// computed by mj_step without sensors (lazy), so the reference's reward reads zeros for them; with
+// full_state, the real wrenches / velocity of post_constraint.
+template <typename T, typename C>
+__device__ __forceinline__ T compute_reward(MPtr<T> m, const Scratch<T, C>& s, KPtr<T> k, T time,
+                                            T energy_sum, T ctrl_sq) {
+  RewardIn<T> in;
+  in.h = s.qpos[2];
+  in.qw = s.qpos[3];
+  in.qx = s.qpos[4];
+  in.qy = s.qpos[5];
+  in.qz = s.qpos[6];
+  in.vx = s.qvel[0];
+  in.time = time;
+  in.com0 = s.com[0];
+  in.com1 = s.com[1];
+  in.comv = T(0);
+  in.lf = T(0);
+  in.rf = T(0);
+  if (k->p.full_state) {
+#pragma clang fp contract(off)
+    for (int q = 0; q < 3; q++) in.comv += s.u.n.linv[0][q] * s.u.n.linv[0][q];
+    foot_forces(m, s, in.lf, in.rf);
+  }
+  in.energy = energy_sum;
+  in.ctrl_sq = ctrl_sq;
+  return reward_formula(k->p.reward_id, k->p.kneel, in);
+}
+
+// np.sum's order (numpy pairwise_sum, n <= 128) over the values x_i held by sub-lanes off + i,
+// i < n, of each 32-lane half: n < 8 -> ((0 + x0) + x1) + ...; else eight accumulators r_j = x_j +
+// x_{j+8} + ... over the whole blocks of 8, combined ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)),
+// then the rest added in order.  The block stage and the tree are DPP (row_ror:8, permlane16 swap,
+// the quad / half-mirror steps of hsum); the tail is a few lane reads.  off + n <= 32; the result is
+// in every lane of the half.  (hsum's butterfly order differs from numpy's by an ulp of the sum,
+// which the exp() of a reward term can amplify to several ulp of the reward.)
+template <typename T>
+__device__ __forceinline__ T np_sum_half(T v, int off, int n, int lane) {
+#pragma clang fp contract(off)
+  const int base = (lane & HL) + off;
+  auto at = [&](int i) { return __shfl(v, base + i, WAVE); };
+  T res;
+  int i;
+  if (n < 8) {
+    res = T(0);
+    i = 0;
+  } else {
+    T x = off == 0 ? v : __shfl(v, base + (lane & (HL - 1)), WAVE);   // x_j on sub-lane j
+    const int nb = n - n % 8;
+    T r = x;
+    const T x8 = dpp<0x128>(x);                           // row_ror:8 -> x_{j+8} on sub-lanes 0..7
+    if (nb >= 16) r += x8;
+    if (nb >= 24) { const T t = x; r += up_row(t); }       // x_{j+16}
+    if (nb >= 32) r += up_row(x8);                         // x_{j+24}
+    r += dpp<0xB1>(r);                                     // r0 + r1, r2 + r3, ...
+    r += dpp<0x4E>(r);                                     // (r0 + r1) + (r2 + r3), ...
+    r += dpp<0x141>(r);                                    // ... + ((r4 + r5) + (r6 + r7)) on sub-lane 0
+    res = bcast<0>(r);
+    i = nb;
+  }
+  for (; i < n; i++) res += at(i);
+  return res;
+}
+
+// custom_env.py:232-261 layout; qfrc_actuator comes from registers (sub-lane i holds dof i)
+template <typename T, typename C, typename O>
+__device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int sl, T qfa, O* out,
+                          int obs_dim) {
+  int nq = m->nq, nv = m->nv;
+  int o1 = nq - 2, o2 = o1 + nv, o3 = o2 + 10 * m->nbody, o4 = o3 + 6 * m->nbody;
+  for (int k = sl; k < o4; k += HL) {
+    T v;
+    if (k < o1) v = s.qpos[2 + k];
+    else if (k < o2) v = s.qvel[k - o1];
+    else if (k < o3) { int q = k - o2; v = s.cinert[q / 10][q % 10]; }
+    else { int q = k - o3; v = s.cvel[q / 6][q % 6]; }
+    out[k] = (O)v;
+  }
+  if (sl < nv && o4 + sl < obs_dim) out[o4 + sl] = (O)qfa;
+  const int o5 = o4 + nv, nf = 6 * (m->nbody - 1);
+  if (obs_dim >= o5 + nf)    // full_state: + cfrc_ext[1:] (custom_env.py:247,255, commented out there)
+    for (int k = sl; k < nf; k += HL) out[o5 + k] = (O)s.u.n.cfrc[1 + k / 6][k % 6];
+}
+
+// Fused rollout: the SB3 MlpPolicy's pi net (mlp_extractor.policy_net + action_net, fp32 as SB3's
+// policy) on the wave's two envs at once (the lower half-wave's env and the upper's; a ghost half
+// mirrors its partner).  Hidden layers of 256: lane L (of 64) owns outputs 4L .. 4L + 3 for BOTH envs,
+// so each input costs one 16-B weight load per lane (coalesced: the wave reads each weight row once)
+// and two LDS broadcasts (the two envs' inputs).  The head: sub-lane sl < A of each half owns action
+// sl of its half's env.  The obs rows and hidden activations are staged in each half's scratch union
+// (free after the env step).  Returns the action mean of (this half's env, sub-lane sl), 0 for sl >= A.
+// unroll of the hidden layers' loads (groups of 4 rows) and of the head's: measured 1 / 2 / 4 / 8 in
+// profiles/ab/ab_r4u_policy_unroll.log (4 and 8 tie), a rolling 16-row ring in ab_r4ae_policy_ring.log
+constexpr int kPolUnroll = 4, kPolHeadUnroll = 16;
+template <typename T, typename C>
+__device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
+  const bool up = lane >= HL;
+  const int sl = lane & (HL - 1);
+  float* xa = smem[0].u.pol.x;   // lower half's env
+  float* xb = smem[1].u.pol.x;   // upper half's env
+  float* ha = smem[0].u.pol.h;
+  float* hb = smem[1].u.pol.h;
+  const int D = k->ro.D, A = k->ro.A, ld1 = k->ro.ld1;
+  float* xo = up ? xb : xa;
+  for (int i = sl; i < D; i += HL) xo[i] = obs[i];
+  WSYNC();
+  auto layer = [&](const float* w, int ld, const float* b, const float* ina, const float* inb, int n, float* outa,
+                   float* outb) {
+    const float4 bb = reinterpret_cast<const float4*>(b + 4 * lane)[0];
+    float a[4] = {bb.x, bb.y, bb.z, bb.w}, c[4] = {bb.x, bb.y, bb.z, bb.w};
+    const float* wl = w + 4 * lane;
+#pragma unroll kPolUnroll
+    for (int i = 0; i < n; i += 4) {
+      const float4 va = *reinterpret_cast<const float4*>(ina + i);
+      const float4 vb = *reinterpret_cast<const float4*>(inb + i);
+      const float xs[4] = {va.x, va.y, va.z, va.w}, ys[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+      for (int ii = 0; ii < 4; ii++) {
+        const float4 u = *reinterpret_cast<const float4*>(wl + (size_t)(i + ii) * ld);
+        a[0] += xs[ii] * u.x; a[1] += xs[ii] * u.y; a[2] += xs[ii] * u.z; a[3] += xs[ii] * u.w;
+        c[0] += ys[ii] * u.x; c[1] += ys[ii] * u.y; c[2] += ys[ii] * u.z; c[3] += ys[ii] * u.w;
+      }
+    }
+    WSYNC();   // every lane has read the inputs (the outputs may alias them)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      outa[4 * lane + j] = fmaxf(a[j], 0.f);
+      outb[4 * lane + j] = fmaxf(c[j], 0.f);
+    }
+    WSYNC();
+  };
+  layer(k->ro.w1, ld1, k->ro.b1, xa, xb, D, ha, hb);        // obs -> h1
+  layer(k->ro.w2, 256, k->ro.b2, ha, hb, 256, xa, xb);      // h1 -> h2 (into the obs slots)
+  float mean = 0.f;
+  if (sl < A) {
+    mean = k->ro.b3[sl];
+    const float* w3 = k->ro.w3 + sl;
+#pragma unroll kPolHeadUnroll
+    for (int i = 0; i < 256; i++) mean += xo[i] * w3[(size_t)i * A];
+  }
+  return mean;
+}
+
+template <typename T, int NV, typename C>
+__device__ __forceinline__ void dump_debug(const Stepper<T, NV, C>& st, T* dbg) {
+  const Scratch<T, C>& s = st.s;
+  int sl = st.sl;
+  for (int k = sl; k < MAXBODY * 10; k += HL) dbg[200 + k] = s.cinert[k / 10][k % 10];
+  for (int k = sl; k < MAXDOF * 6; k += HL) dbg[500 + k] = s.cdof[k / 6][k % 6];
+  if (sl < NV)
+    for (int j = 0; j < NV; j++) dbg[700 + sl * MAXDOF + j] = st.Mr[j];
+  for (int k = sl; k < MAXBODY * 6; k += HL) dbg[1800 + k] = s.cvel[k / 6][k % 6];
+  if (sl < NV) {
+    dbg[2280 + sl] = st.qfa;
+    dbg[2320 + sl] = st.fsmooth;
+    dbg[2360 + sl] = st.fcon;
+    dbg[2400 + sl] = st.qacc;
+  }
+  if (sl == 0) {
+    dbg[2500] = s.com[0]; dbg[2501] = s.com[1]; dbg[2502] = s.com[2];
+    dbg[2503] = s.ncon; dbg[2504] = s.nefc; dbg[2505] = st.niter; dbg[2506] = s.nlim;
+  }
+  for (int c = sl; c < s.ncon; c += HL) {
+    T* o = dbg + 2600 + 11 * c;
+    for (int k = 0; k < 3; k++) { o[k] = s.con_pos[c][k]; o[3 + k] = s.con_n[c][k]; o[6 + k] = s.con_t1[c][k]; }
+    o[9] = s.con_dist[c];
+    o[10] = s.con_pair[c];
+  }
+  for (int r = sl; r < s.nefc; r += HL) {
+    T* o = dbg + 4000 + 6 * r;     // contacts above end at 2600 + 11 * 64
+    o[0] = rk_kind(s.row_kid[r]); o[1] = rk_id(s.row_kid[r]); o[2] = s.row_D[r]; o[4] = s.row_f[r];
+  }
+}
+
+// per-env commit of state (+ the optional aux row / ctrl copy) for one half-wave
+template <typename T, int NV, typename C>
+__device__ __forceinline__ void commit(MPtr<T> m, KPtr<T> k, const Stepper<T, NV, C>& st,
+                       int env, T time, T xws, int step_count, uint32_t episode, T total, const int* warn,
+                       bool full) {
+  const Scratch<T, C>& s = st.s;
+  const int sl = st.sl, nq = m->nq, nv = m->nv, nu = m->nu;
+  const int outputs = k->p.outputs;
+  if (sl < nq) k->b.qpos[(size_t)env * nq + sl] = s.qpos[sl];
+  if (sl + HL < nq) k->b.qpos[(size_t)env * nq + sl + HL] = s.qpos[sl + HL];
+  if (sl < nv) {
+    k->b.qvel[(size_t)env * nv + sl] = s.qvel[sl];
+    k->b.qacc_ws[(size_t)env * nv + sl] = xws;
+    if (outputs & OUT_AUX) k->b.aux[(size_t)env * AUXDIM + sl] = st.qacc;
+  }
+  // data.ctrl: always for resets and raw physics calls (rare); for env steps only with OUT_CTRL
+  // (the host marks the buffer stale otherwise, hs_api.cpp)
+  if (sl < nu && ((outputs & OUT_CTRL) || k->p.mode != MODE_ENV_STEP)) k->b.ctrl[(size_t)env * nu + sl] = s.ctrl[sl];
+  if (sl == 0) {
+    k->b.time[env] = time;
+    k->b.step_count[env] = step_count;
+    k->b.episode[env] = episode;
+    k->b.total_reward[env] = total;
+    if (outputs & OUT_AUX) {
+      T* a = k->b.aux + (size_t)env * AUXDIM;
+      a[MAXDOF + 0] = s.com[0]; a[MAXDOF + 1] = s.com[1]; a[MAXDOF + 2] = s.com[2];
+      a[MAXDOF + 3] = (T)s.ncon; a[MAXDOF + 4] = (T)s.nefc; a[MAXDOF + 5] = (T)st.niter;
+    }
+    for (int w = 0; w < NWARN; w++)   // read-modify-write only when set (a load here would wait for
+      if (warn[w]) k->b.warning[(size_t)env * NWARN + w] += warn[w];   // every store issued above)
+  }
+  if (full) {   // data.cfrc_ext / data.subtree_linvel of the last substep (pre-integration)
+    const int nb = m->nbody;
+    for (int q = sl; q < 6 * nb; q += HL) k->b.cfrc_ext[(size_t)env * 6 * nb + q] = s.u.n.cfrc[q / 6][q % 6];
+    for (int q = sl; q < 3 * nb; q += HL) k->b.subtree_linvel[(size_t)env * 3 * nb + q] = s.u.n.linv[q / 3][q % 3];
+  }
+}
+
+// ------------------------------------------------------------------ one env step of an env pair
+// One env step (or reset / raw physics call) of the env pair (index, index + 1) of one wave.
+// `list` (wide tier): indices map to env ids through it; resident tier: indices are env ids.
+// In the resident tier an env whose contacts / rows overflowed the resident capacity in any
+// substep is NOT committed: it is appended to the wide tier's work list instead, and the wide
+// launch that follows re-runs its whole step from the same (untouched) inputs.
+// Queued schedule (launch_step sets p.queue when the pairs outnumber the resident waves): the
+// pair's substeps [s0, s1) only.  A chunk that ends before the last substep hands the state over
+// through b.mid and sets the pair's flag := this launch's tag; the last-substep chunk waits for the
+// tag and starts from that row.  b.mid and the flags live in UNCACHED device memory (hs_api.cpp; its
+// blocks are recycled only as uncached memory), so the stores are in memory once `s_waitcnt
+// vmcnt(0)` returns and the consumer's loads cannot hit a stale L1 / L2 line: no cache invalidate or
+// write-back on either side.  Every chunk recomputes the whole mj_step pipeline from (qpos, qvel,
+// qacc_warmstart, time), so the hand-off is exact: results are bitwise those of one wave running all
+// substeps.
+// ghost: this half-wave mirrors env idx (the single-env schedule's upper half) and commits nothing.
+template <typename T, int NV, bool PGS, typename C, bool ROLL = false>
+__device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCache<T, C>* pcache, int idx,
+                                          int nidx, const int* list, int s0, int s1, int pair, bool ghost = false,
+                                          int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false) {
+  constexpr bool WIDE = C::WIDE;
+  const int lane = opaque_v(threadIdx.x);   // (no lane-derived value hoisted out of the chunk-queue loop)
+  const bool up = lane >= HL;
+  const int sl = lane & (HL - 1);
+  bool active = idx < nidx && !ghost;                 // ghost half: odd count, or the single-env schedule
+  const int ei = idx < nidx ? idx : nidx - 1;
+  const int env_id = list ? list[ei] : ei;
+  const int mode = ka->p.mode;
+  if (mode == MODE_RESET && ka->reset_mask && !ka->reset_mask[env_id]) active = false;
+  if (__ballot(active) == 0) return;                  // wave-uniform exit
+  const bool real = active;                           // this half steps (and commits) a real env
+  // fused rollout (fp64 engine): the episode return so far and the step's done flag, carried to the
+  // policy forward after the step; the action of steps after the launch's first comes in the row
+  const bool rollout = ROLL && ka->ro.obs != nullptr;
+  double epacc = 0.0;
+  bool rdone = false;
+  T act_row = T(0);
+  Scratch<T, C>& s = smem[up ? 1 : 0];
+  MPtr<T> m = ka->m;
+  const int nq = m->nq, nv = m->nv, nu = m->nu;
+  Stepper<T, NV, C> st(m, s, lane);
+  if (ka->b.dbg && env_id == 0 && active) st.dbg = ka->b.dbg;
+  int warn[NWARN] = {0, 0, 0, 0, 0};
+  T time, xws;
+  int step_count;
+  uint32_t episode;
+  T total, act;
+  {
+    if (wait_tag != 0) {   // queued: wait for the pair's previous chunk (or tape step) to hand the state over
+      int* flag = ka->b.qsync + QS_FLAG + pair;
+      int seen = 0, abort = 0;
+      if (lane == 0) {   // bounded (~0.5 s): a broken hand-off must not hang the GPU
+        int w = 0;
+        if (pair + 1 != ka->p.dbg_lose_pair1)   // test hook: treat this unit's hand-off as lost
+          while ((seen = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != wait_tag &&
+                 ++w < (1 << 22)) {
+            // a tape launch that aborted (overflow) never hands this pair over: leave at once
+            if (tstep > 0 && (abort = __hip_atomic_load(ka->b.qsync + QS_ABORT, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT)) != 0)
+              break;
+            __builtin_amdgcn_s_sleep(2);
+          }
+      }
+      if (__builtin_amdgcn_readfirstlane(abort) != 0) return;   // results discarded: the host replays
+      const bool lost = __builtin_amdgcn_readfirstlane(seen) != wait_tag;
+      WSYNC();   // (compiler order: the row loads stay behind the poll)
+      const T* r = ka->b.mid + (size_t)env_id * MIDDIM;
+      time = row_ld(r + MID_TIME);
+      xws = (sl < nv) ? row_ld(r + MID_WS + sl) : T(0);
+      if (sl < nq) s.qpos[sl] = row_ld(r + MID_Q + sl);
+      if (sl + HL < nq) s.qpos[sl + HL] = row_ld(r + MID_Q + sl + HL);
+      if (sl < nv) s.qvel[sl] = row_ld(r + MID_V + sl);
+#pragma unroll
+      for (int w = 0; w < NWARN; w++) warn[w] = (int)row_ld(r + MID_W + w);
+      step_count = (int)row_ld(r + MID_SC);
+      episode = (uint32_t)row_ld(r + MID_EP);
+      total = row_ld(r + MID_TOT);
+      if (rollout) {
+        if (sl < nu) act_row = row_ld(r + MID_ACT + sl);
+        epacc = (double)row_ld(r + MID_EPACC);
+      }
+      // never seen in practice; if it were, the state is poisoned so that the substep's mj_checkPos
+      // resets the env (mj_resetData, ctrl 0 for that substep) -- counted in its own slot,
+      // HS_WARN_HANDOFF, not as a bad state (the -1 cancels the HS_WARN_BADQPOS count the poisoned
+      // qpos draws); the trainer raises on it: loud, never silent
+      if (lost) {
+        warn[WARN_HANDOFF]++;
+        warn[WARN_BADQPOS]--;
+        if (sl == 2) s.qpos[2] = T(NAN);
+      }
+    } else {
+      time = ka->b.time[env_id];
+      xws = (sl < nv) ? ka->b.qacc_ws[(size_t)env_id * nv + sl] : T(0);
+      if (sl < nq) s.qpos[sl] = ka->b.qpos[(size_t)env_id * nq + sl];
+      if (sl + HL < nq) s.qpos[sl + HL] = ka->b.qpos[(size_t)env_id * nq + sl + HL];
+      if (sl < nv) s.qvel[sl] = ka->b.qvel[(size_t)env_id * nv + sl];
+      step_count = ka->b.step_count[env_id];
+      episode = ka->b.episode[env_id];
+      total = ka->b.total_reward[env_id];
+      if (rollout) epacc = ka->ro.ep_acc[env_id];
+    }
+    // data.ctrl is an input only to a raw physics call that keeps the current ctrl; env steps set
+    // it from the action, resets zero it
+    const float* actions = ka->actions;
+    if (sl < nu) s.ctrl[sl] = (mode == MODE_PHYSICS && !actions) ? ka->b.ctrl[(size_t)env_id * nu + sl] : T(0);
+    // the action is the same for all substeps: one load, issued with the state loads (a tape
+    // launch's step tstep reads its own [N][nu] slice)
+    // (a rollout's `actions` is its first step's, ro.act_clip; later steps' come in the row)
+    act = (rollout && tstep > 0) ? act_row
+        : (actions && sl < nu) ? (T)actions[((size_t)tstep * ka->nenv + env_id) * nu + sl] : T(0);
+  }
+  WSYNC();
+  st.clk.start();
+  st.qfa = 0;
+  st.qacc = 0;
+  st.niter = 0;
+  // resident tier: an overflowing env is deferred to the wide tier instead of committed
+  auto defer = [&](KPtr<T> k) -> bool {
+    if constexpr (WIDE) {
+      return false;
+    } else {
+      if (!k->b.redo || warn[WARN_OVERFLOW] == 0) return false;
+      if (sl == 0) {
+        const int slot = atomicAdd(&k->b.redo[0], 1);
+        k->b.redo[2 + slot] = env_id;
+        atomicAdd(k->b.redo_total, 1ull);
+      }
+      return true;
+    }
+  };
+  // Tape launch (set_tag on a whole-step item): the state goes on to the pair's next env step only
+  // through its hand-off row (uncached), together with the warning counters accumulated so far.
+  // Only the tape's LAST step commits to the batch buffers: consecutive steps of one env may run on
+  // different XCDs, whose L2s are not coherent with each other, so two steps writing the same
+  // batch address would leave whichever dirty line is written back last.  For the same reason the
+  // batch's obs / reward / done rows are written by the last step only when the tape has no
+  // per-step outputs, and the host keeps each env to at most one finished episode per tape launch
+  // (hs_step_tape), so its terminal obs / info rows are written once.
+  const bool tape_handoff = set_tag != 0 && s1 == ka->p.nsub;
+  const bool tape_final = !(ka->p.nsteps > 1 && tstep < ka->p.nsteps - 1);
+  bool deferred = false;
+  auto handoff = [&](KPtr<T> k, int env, T time_, T xws_, int sc, uint32_t ep, T tot) {
+    T* r = k->b.mid + (size_t)env * MIDDIM;
+    if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
+    if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
+    if (sl < nv) { row_st(r + MID_V + sl, s.qvel[sl]); row_st(r + MID_WS + sl, xws_); }
+    if (sl == 0) {
+      row_st(r + MID_TIME, time_);
+#pragma unroll
+      for (int w = 0; w < NWARN; w++) row_st(r + MID_W + w, (T)warn[w]);
+      row_st(r + MID_SC, (T)sc);
+      row_st(r + MID_EP, (T)ep);
+      row_st(r + MID_TOT, tot);
+    }
+  };
+  // this env step's output rows: the tape's slice tstep, or the batch's own buffers (null: an
+  // intermediate step of a tape launch without per-step outputs writes none)
+  auto obs_row = [&](KPtr<T> k, int env, int obs_dim) -> T* {
+    if (k->tape.obs) return k->tape.obs + ((size_t)tstep * k->nenv + env) * obs_dim;
+    return tape_final ? k->b.obs + (size_t)env * obs_dim : nullptr;
+  };
+  // fused rollout: the rollout buffer's obs row of step g + 1 (the obs this step returns)
+  auto ro_next_obs = [&](KPtr<T> k, int env) -> float* {
+    const int g = k->ro.t_begin + tstep;
+    return g + 1 < k->ro.t_total ? k->ro.obs + ((size_t)(g + 1) * k->nenv + env) * k->ro.D
+                                 : k->ro.obs_last + (size_t)env * k->ro.D;
+  };
+
+  // Both halves always run the same instruction stream; a half that is inactive (ghost env,
+  // masked reset) or not resetting while its partner resets computes on scratch but commits
+  // nothing (its real state was committed before the shared reset pass).
+  bool do_reset = mode == MODE_RESET && active;
+  const int nsub = (mode == MODE_RESET) ? 0 : ka->p.nsub;
+  bool in_reset = false;
+#ifdef HS_TIMING
+  int tot_iter = 0;
+  const int titem = (ka->p.queue ? (s0 > 0 ? (nidx + 1) / 2 : 0) + pair : -1);
+#endif
+  // One loop, ONE inlined physics_step call site: substeps 0..nsub-1 apply the action; after the
+  // last one the env bookkeeping runs; if any half of the wave must reset, one more substep
+  // runs with the reset state (a half that is not resetting has already committed and computes
+  // on scratch only).  Launch arguments are re-read through k = opaque(ka) at each use.
+  for (int sub = s0;; sub++) {
+    st.m = opaque(st.m);
+    st.sl = opaque_v(st.sl);
+    const int env = opaque_v(env_id);   // per-env addresses recomputed at each use, not kept live
+    if (sub == s1 && s1 < nsub) {         // queued chunk ends before the last substep: hand over
+      KPtr<T> k = opaque(ka);
+      if (active) {
+        T* r = k->b.mid + (size_t)env * MIDDIM;
+        if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
+        if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
+        if (sl < nv) { row_st(r + MID_V + sl, s.qvel[sl]); row_st(r + MID_WS + sl, xws); }
+        if (sl == 0) {
+          row_st(r + MID_TIME, time);
+#pragma unroll
+          for (int w = 0; w < NWARN; w++) row_st(r + MID_W + w, (T)warn[w]);
+          row_st(r + MID_SC, (T)step_count);
+          row_st(r + MID_EP, (T)episode);
+          row_st(r + MID_TOT, total);
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the row is in memory before the flag is
+      if (lane == 0) __hip_atomic_store(k->b.qsync + QS_FLAG + pair, set_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      HS_FLUSH();
+      break;
+    }
+    if (sub == nsub && !in_reset) {
+      if (nsub > 0) {
+        KPtr<T> k = opaque(ka);
+        const int obs_dim = k->p.obs_dim;
+        HS_STAMP(st.clk, 22);
+        T* orow = obs_row(k, env, obs_dim);
+        if (active && orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
+        HS_STAMP(st.clk, 23);
+        if (k->p.mode == MODE_ENV_STEP) {
+          step_count += 1;
+          bool trunc = step_count >= k->p.max_steps;
+          // np.sum(np.square(qfrc_actuator[-nj:] * qvel[6:])) and np.sum(np.square(ctrl)) in numpy's order
+          // (each sum only for the reward that reads it: kneeling the energy, stand / walk the torque;
+          // the launch's reward id is wave-uniform)
+          const int rid = opaque(k)->p.reward_id;
+          const T e = sl < nv ? st.qfa * s.qvel[sl] : T(0);
+          const T esum = rid == REWARD_KNEELING ? np_sum_half(e * e, 6, nv - 6, lane) : T(0);
+          const T cu = sl < st.m->nu ? s.ctrl[sl] : T(0);
+          const T csum = (rid == REWARD_STAND || rid == REWARD_WALK) ? np_sum_half(cu * cu, 0, st.m->nu, lane) : T(0);
+          HS_STAMP(st.clk, 24);
+          T r = trunc ? T(0) : compute_reward(st.m, s, k, time, esum, csum);
+          HS_STAMP(st.clk, 25);
+          total += r;
+          bool term = (double)time >= k->p.duration;
+          if (sl == 0 && active && (k->tape.reward || tape_final)) {
+            const size_t o = k->tape.reward ? (size_t)tstep * k->nenv : 0;
+            (k->tape.reward ? k->tape.reward : k->b.reward)[o + env] = r;
+            (k->tape.terminated ? k->tape.terminated : k->b.terminated)[o + env] = term;
+            (k->tape.truncated ? k->tape.truncated : k->b.truncated)[o + env] = trunc;
+          }
+          // the final step's info of a finished episode (SubprocVecEnv returns its step_count /
+          // total_reward before resetting, custom_env.py:216-224), with or without auto-reset
+          if ((term || trunc) && active && sl == 0) {
+            if (k->b.term_step_count) k->b.term_step_count[env] = step_count;
+            if (k->b.term_total_reward) k->b.term_total_reward[env] = total;
+          }
+          // fused rollout: SB3 collect_rollouts' bookkeeping of this step (ppo_post_kernel): reward and
+          // done rows, the episode return, TimeLimit.truncated envs' terminal obs for the bootstrap,
+          // and the returned obs (an env that auto-resets returns its reset obs, written below)
+          if (rollout && active) {
+            const float rf = (float)r;
+            const double acc = epacc + (double)rf;
+            rdone = term || trunc;
+            const size_t gi = (size_t)(k->ro.t_begin + tstep) * k->nenv + env;
+            if (sl == 0) {
+              k->ro.rew[gi] = rf;
+              k->ro.done[gi] = rdone;
+              k->ro.epret[gi] = acc;
+              k->ro.boot[gi] = trunc && !term;
+            }
+            epacc = rdone ? 0.0 : acc;
+            if (trunc && !term) write_obs(st.m, s, sl, st.qfa, k->ro.tobs + gi * obs_dim, obs_dim);
+            if (!rdone) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);
+          }
+          if ((term || trunc) && k->p.autoreset && active) {
+            write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
+            do_reset = true;
+          }
+        }
+        if (active && !do_reset) {
+          if (!defer(k)) {
+            if (tape_final) commit(st.m, k, st, env, time, xws, step_count, episode, total, warn, k->p.full_state != 0);
+            if (tape_handoff) handoff(k, env, time, xws, step_count, episode, total);
+          } else {
+            deferred = true;
+          }
+          active = false;   // committed (or deferred); a reset pass below is scratch work for this half
+        }
+      }
+      if (__ballot(do_reset) == 0) { HS_FLUSH(); break; }
+      // custom_env.py:97-130: mj_resetData; qpos = init (z=1.282, upright); += U(+-0.01) noise
+      // with z noise x0.1 and no quaternion noise; qvel = U(+-0.01); one mj_step with ctrl = 0.
+      KPtr<T> k = opaque(ka);
+      in_reset = true;
+      st.dbg = nullptr;
+      T sc = (T)k->p.noise_scale;
+      const uint64_t seed = k->p.seed;
+      const T* nz_q = k->nz_q;
+      const T* nz_v = k->nz_v;
+      uint32_t ep = episode + 1;
+      for (int q = sl; q < nq; q += HL) {
+        T v = m->qpos0[q];
+        T nzq = nz_q ? nz_q[(size_t)env * nq + q] : uniform_pm<T>(seed, env, ep, q, sc);
+        if (m->jnt_type[0] == JNT_FREE) {
+          if (q == 2) { v = (T)k->p.init_height; nzq *= T(0.1); }
+          if (q >= 3 && q < 7) { v = q == 3 ? T(1) : T(0); nzq = 0; }
+        }
+        s.qpos[q] = v + nzq;
+      }
+      if (sl < nv) s.qvel[sl] = nz_v ? nz_v[(size_t)env * nv + sl] : uniform_pm<T>(seed, env, ep, 64 + sl, sc);
+      if (sl < nu) s.ctrl[sl] = 0;
+      xws = 0;
+      time = 0;
+      episode = ep;
+      WSYNC();
+    } else if (sub > nsub) {
+      if (do_reset && active) {
+        KPtr<T> k = opaque(ka);
+        if (k->b.dbg && env == 0) dump_debug(st, k->b.dbg);
+        const int obs_dim = k->p.obs_dim;
+        T* orow = obs_row(k, env, obs_dim);
+        if (orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
+        if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);   // the reset obs
+        if (!defer(k)) {
+          if (tape_final) commit(st.m, k, st, env, time, xws, 0, episode, T(0), warn, k->p.full_state != 0);
+          if (tape_handoff) handoff(k, env, time, xws, 0, episode, T(0));
+        } else {
+          deferred = true;
+        }
+      }
+      HS_FLUSH();
+      break;
+    } else {
+      // data.ctrl[:] = action each substep (custom_env.py:159); mj_resetData may have zeroed it
+      if (sl < nu && opaque(ka)->actions) s.ctrl[sl] = act;
+      WSYNC();
+    }
+    physics_step<T, NV, PGS>(st, ka, time, xws, warn, pcache);
+#ifdef HS_TIMING
+    tot_iter += st.niter;
+#endif
+    if (st.dbg && active && !in_reset) dump_debug(st, st.dbg);
+  }
+  if constexpr (ROLL) {
+    if (rollout) {   // the policy acts on the step's obs: step g + 1's action, drawn as ppo_act_kernel does
+      KPtr<T> k = opaque(ka);
+      const int g = k->ro.t_begin + tstep, N = k->nenv, A = k->ro.A;
+      const bool last_of_launch = tstep == k->p.nsteps - 1;
+      T* r = k->b.mid + (size_t)env_id * MIDDIM;
+      if (g + 1 < k->ro.t_total) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
+        const float mean = policy_mean(k, k->ro.obs + ((size_t)(g + 1) * N + env_id) * k->ro.D, smem, lane);
+        const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
+        float z = 0.f;
+        if (!k->ro.deterministic && sl < A)
+          z = policy_noise((uint32_t)env_id, (uint32_t)sl, (uint64_t)(g + 1) + *k->ro.ctr_base, k->ro.k0, k->ro.k1);
+        const float a = mean + __expf(ls) * z;
+        const float lp = half_sum(sl < A ? -0.5f * z * z - ls - 0.91893853320467274f : 0.f);
+        if (real) {
+          const size_t gi = (size_t)(g + 1) * N + env_id;
+          if (sl < A) {
+            const float ac = fminf(fmaxf(a, -1.f), 1.f);
+            k->ro.act[gi * A + sl] = a;
+            if (last_of_launch) k->ro.act_clip[(size_t)env_id * A + sl] = ac;
+            else row_st(r + MID_ACT + sl, (T)ac);
+          }
+          if (sl == 0) {
+            k->ro.logp[gi] = lp;
+            k->ro.start[gi] = rdone ? 1.f : 0.f;
+          }
+        }
+      }
+      // the rollout's last step: act_clip ends as the action that step ran with (as the per-step path)
+      if (real && last_of_launch && g + 1 >= k->ro.t_total && sl < A) k->ro.act_clip[(size_t)env_id * A + sl] = (float)act;
+      if (real && sl == 0) {
+        if (last_of_launch) {
+          k->ro.ep_acc[env_id] = epacc;
+          k->ro.episode_start[env_id] = rdone ? 1.f : 0.f;
+        } else {
+          row_st(r + MID_EPACC, (T)epacc);
+        }
+      }
+    }
+  }
+  // A tape launch never runs the wide tier, so an env deferred on ANY of its steps -- the last one
+  // included, which hands nothing over -- stops the launch: the host restores the saved state and
+  // replays the tape step by step (hs_api.cpp guarded_tape).  Otherwise the pair's next env step may
+  // start: rows in memory, then the flag.
+  if (tape_handoff || tape_launch) {
+    KPtr<T> k = opaque(ka);
+    const bool any_deferred = __ballot(deferred) != 0;
+    if (tape_handoff || any_deferred) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) {
+        if (any_deferred)
+          __hip_atomic_store(k->b.qsync + QS_ABORT, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+          __hip_atomic_store(k->b.qsync + QS_FLAG + pair, set_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
+}  // namespace
+}  // namespace hs

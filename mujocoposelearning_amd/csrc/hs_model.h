@@ -21,7 +21,7 @@ constexpr int MAXTEN = 4;
 constexpr int MAXWRAP = 4;    // joints per fixed tendon
 constexpr int MAXU = 24;
 constexpr int MAXPAIR = 192;  // static candidate geom pairs
-// Contact / constraint-row capacity per env comes in two tiers (hs_kernels.hip):
+// Contact / constraint-row capacity per env comes in two tiers (hs_lanes.h Cap):
 //  * resident tier: what every launch runs with, sized so all 4096 envs of configs[1] stay
 //    resident (LDS) -- 2.3x / 2.5x the worst full-episode counts measured on the oracle
 //    (14 contacts, 52 rows over 48 episodes x tapes T0/T1/T2);

@@ -1,0 +1,88 @@
+// Per-env LDS layouts: Scratch (the mjData fields one mj_step needs, phase-local arrays aliased in a
+// union so a wave's two envs fit 20 KB) and the PGS instance's row cache.
+#pragma once
+#include <cstdint>
+
+#include "hs_lanes.h"
+#include "hs_model.h"
+
+namespace hs {
+namespace {
+
+enum RowKind { RK_JLO = 0, RK_JHI = 1, RK_TLO = 2, RK_THI = 3, RK_CN = 4, RK_P0 = 5 };   // P0..P0+3: pyramid
+__device__ __forceinline__ int rk_kind(int kid) { return kid >> 16; }
+__device__ __forceinline__ int rk_id(int kid) { return kid & 0xffff; }
+
+template <typename T, typename C>
+struct Scratch {
+  T qpos[MAXQ];
+  T qvel[MAXDOF];
+  T ctrl[MAXU];
+  alignas(16) T vx[MAXDOF];   // generalized vector for J x; Cholesky column buffer
+  T com[4];
+  T cinert[MAXBODY][10];
+  T cdof[MAXDOF][6];
+  T cvel[MAXBODY][6];
+  T con_pos[C::CON][3];
+  T con_n[C::CON][3];
+  T con_t1[C::CON][3];
+  T con_dist[C::CON];
+  T con_v[C::CON][3];
+  T con_U[C::CON][6];
+  T con_F[C::CON][3];
+  int con_pair[C::CON];
+  int con_adr[C::CON];
+  uint32_t con_bb[C::CON];    // b1 | b2 << 8 | condim << 16 of the contact's pair (no model lookups per use)
+  uint32_t con_m1[C::CON];    // dof chain masks of the contact's bodies (m1 = 0: world)
+  uint32_t con_m2[C::CON];
+  T con_mu[C::CON];
+  uint32_t con_act[(C::CON + HL - 1) / HL];   // contacts with a nonzero force (contact_aggregates)
+  uint16_t lim_row[MAXDOF];   // joint-limit rows of a dof: (lo row + 1) | (hi row + 1) << 8
+  uint32_t dense_mask[C::RPL];   // rows added as dense rank-1 Hessian terms (tendons, body-body)
+  int row_kid[C::EFC];
+  T row_D[C::EFC];
+  T row_f[C::EFC];
+  int ncon, nefc, nlim, njl;   // njl: joint-limit rows (tendon rows are [njl, nlim))
+  int niter;                   // this env's Newton iterations (the wave's loop runs for the slower env)
+  struct Kin { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; T xanchor[MAXJNT][3];
+               T xaxis[MAXJNT][3]; T gpos[MAXGEOM][3]; T gax[MAXGEOM][3]; };
+  union {   // phase-local arrays (aliased)
+    Kin k;                                                        // kinematics + collision
+    struct { T crb[MAXBODY][10]; T buf[MAXDOF][6]; } c;          // composite rigid body
+    struct { T cdofdot[MAXDOF][6]; T cfrc[MAXBODY][6]; T csub[MAXBODY][6]; } r;   // RNE
+    struct { T bvel[MAXBODY][6];                                  // J x mapping (rows, Newton)
+             alignas(16) T cb[MAXDOF][2];                         // Cholesky column pairs
+             T cfrc[MAXBODY][6], linv[MAXBODY][3], mv[MAXBODY][3]; } n;   // full_state (after solve)
+    // fused rollout's policy forward (fp64 engine only: inside the union's 4 KB there; the fp32
+    // engine's union is smaller and must not grow, so its member is a stub)
+    struct { alignas(16) float x[sizeof(T) == 8 ? 512 : 4]; alignas(16) float h[sizeof(T) == 8 ? 256 : 4]; } pol;
+  } u;
+};
+
+// PGS solver scratch (the <option solver="PGS"> kernel instance only; the Newton instance never
+// allocates it).  With M = L L', row r's u_r = L^-1 J_r' (one nv-vector per row) gives the whole dual:
+// AR = J M^-1 J' + R has AR_ik = u_i . u_k + R_i [i == k], and J_r qacc = u_r . (L' qacc).  Rows
+// [0, NC) keep u_r in LDS (later rows rebuild it per use); every row keeps b_r = -aref_r, R_r, AR_rr,
+// 1 / AR_rr and its lookahead Gram terms.
+// Row sweep lookahead: row r's residual u_r . z is started PGS_LA rows early, on a z that still lacks the
+// updates of rows r-PGS_LA .. r-1, and corrected with delta_{r-j} (u_r . u_{r-j}) when row r's turn
+// comes (the Gram terms G_rj are computed once per substep).  The half-wave sum thus leaves the
+// serial chain, which shrinks to a few scalar FMAs per row.
+constexpr int PGS_LA = 3;
+// cached rows: 40 in fp32 keep the resident PGS instance at 4 workgroups per CU; fp64 (48) runs at 2
+template <typename T>
+constexpr int pgs_cache_rows() { return sizeof(T) == 4 ? 40 : 48; }
+template <typename T>
+struct alignas(4 * sizeof(T)) PgsRow {
+  T b, R, ar, ai;                 // -aref_r, R_r, AR_rr, 1 / max(AR_rr, MINVAL)
+  T g[4];                         // G_rj = u_r . u_{r-j}, j = 1..PGS_LA (0 past the first row)
+};
+template <typename T, typename C>
+struct PgsCache {
+  static constexpr int NC = pgs_cache_rows<T>();
+  T u[NC][MAXDOF];
+  PgsRow<T> row[C::EFC];
+};
+
+}  // namespace
+}  // namespace hs
