@@ -24,6 +24,7 @@
  *                           formulas of hs_step on supplied fields)
  *   hs_reward            <- the same on the batch's current states (custom_env.py:263-271 _compute_reward)
  *   hs_debug_lose_handoff   (test hook: mj_step's warning + mj_resetData path, custom_env.py:160)
+ *   hs_debug_queue_order    (test view of the chunk queue's next claim order; no counterpart)
  *   hs_last_tape_ms, hs_tape_aborts, hs_stream_orders, hs_batch_counters   (diagnostics)
  *   hs_state_io          <- reads/writes of data.qpos/qvel/qacc_warmstart/time/ctrl (custom_env.py:105-117)
  *   hs_get_buffers       <- data.* arrays as device buffers (obs, reward, terminated, ...)
@@ -288,6 +289,13 @@ int hs_physics_step(hs_batch* b, const float* ctrl, int nsub, void* stream);
  * state (qpos0, qvel 0, time 0), HS_WARN_HANDOFF += 1, and the step continues from there.
  * env = -1 turns it off.  Only launches on the queued schedule consult it. */
 int hs_debug_lose_handoff(hs_batch* b, int env);
+/* Debug view of the chunk queue (tests only): the order in which the batch's next queued launch
+ * will claim its units (env pairs; single envs for a batch small enough that every env has a
+ * resident wave of its own) -- the bucket lists the previous queued launch filed, concatenated,
+ * bucket 0 (the pairs with an env about to auto-reset) first.  Writes min(count, n) unit indices
+ * to `out` and returns the count; 0 when that launch would claim in the fixed permutation (no
+ * queued launch yet, or a schedule other than HS_SCHED_AUTO); -1 on error.  Synchronous. */
+int hs_debug_queue_order(hs_batch* b, int* out, int n);
 
 /* Synchronous host<->device state copy in fp64.  dir 0: device -> host, 1: host -> device.
  * Any pointer may be NULL.  Arrays are [N][nq], [N][nv], [N][nv], [N], [N][nu]. */

@@ -490,6 +490,17 @@ class HsBatch:
             inside = env is not None and lo <= int(env) < hi
             check(lib().hs_debug_lose_handoff(h, int(env) - lo if inside else -1))
 
+    def queue_order(self):
+        """Tests only (hs_debug_queue_order): the env pairs in the order the next chunk-queue launch
+        of the first group will claim them -- pairs with an env about to auto-reset first, then by
+        the last launch's measured cost; empty while that launch would use the fixed permutation.
+        Synchronous."""
+        out = np.zeros(self._groups[0][2] - self._groups[0][1], dtype=np.int32)
+        cnt = lib().hs_debug_queue_order(self._h, out.ctypes.data, len(out))
+        if cnt < 0:
+            raise _lib.HsimError(lib().hs_last_error().decode())
+        return out[:cnt].copy()
+
     def get_debug(self):
         out = np.zeros(_lib.DBGDIM)
         check(lib().hs_get_debug(self._h, out.ctypes.data, _lib.DBGDIM))

@@ -739,6 +739,30 @@ int hs_debug_lose_handoff(hs_batch* b, int env) {
   return 0;
 }
 
+int hs_debug_queue_order(hs_batch* b, int* out, int n) {
+  if (!b || (!out && n > 0) || n < 0) return fail("hs_debug_queue_order: bad argument");
+  if (!b->qsync || b->cfg.schedule != HS_SCHED_AUTO) return 0;
+  DeviceGuard g(b->device);
+  if (!hip_ok(hipDeviceSynchronize(), "sync")) return -1;
+  // the queue's unit, as launch_step picks it (a small batch only ever queues tape launches, by env)
+  const bool pgs = b->model->host.solver == 1;
+  const int resident = b->precision == HS_FP64 ? hs::resident_waves<double>(pgs) : hs::resident_waves<float>(pgs);
+  const int nunits = b->n <= resident ? b->n : (b->n + 1) / 2;
+  std::vector<int> q(hs::qsync_words(b->n));
+  if (!hip_ok(hipMemcpy(q.data(), b->qsync, q.size() * sizeof(int), hipMemcpyDeviceToHost), "qsync")) return -1;
+  const int par = q[hs::QS_EPOCH] & 1;   // the parity the next launch reads
+  const int* cnt = q.data() + hs::qs_cnt(nunits, par);
+  const int* ord = q.data() + hs::qs_ord(nunits, par);
+  long long total = 0;
+  for (int k = 0; k < hs::QNB; k++) total += cnt[k] < 0 ? (long long)nunits + 1 : cnt[k];
+  if (total != nunits) return 0;
+  int w = 0;
+  for (int k = 0; k < hs::QNB; k++)
+    for (int s = 0; s < cnt[k]; s++, w++)
+      if (w < n) out[w] = ord[(size_t)k * nunits + s];
+  return nunits;
+}
+
 int hs_set_autoreset_noise(hs_batch* b, const void* qpos_noise, const void* qvel_noise) {
   if (!b) return fail("null batch");
   if ((qpos_noise == nullptr) != (qvel_noise == nullptr)) return fail("bind both noise arrays or neither");

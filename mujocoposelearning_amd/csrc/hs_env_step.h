@@ -368,6 +368,19 @@ __device__ __forceinline__ void commit(MPtr<T> m, KPtr<T> k, const Stepper<T, NV
 }
 
 // ------------------------------------------------------------------ one env step of an env pair
+// step_pair's hint bits (wave-uniform): an env of the pair will auto-reset in its next env step / the
+// wave ran the reset pass in this one.  Scheduling hints for the chunk queue, never results.
+constexpr int STEP_WILL_RESET = 1, STEP_DID_RESET = 2;
+
+// Will an env that commits (time, step_count) end its episode in the next env step and auto-reset?
+// The next step's own tests (below) on the values it will see: its clock after nsub more substeps
+// and its step count + 1.  A prediction only: set_state / reset / configure between the launches,
+// a bad-state reset, or the rounding of time + nsub * dt against nsub additions can make it wrong.
+template <typename T>
+__device__ __forceinline__ bool resets_next(KPtr<T> k, MPtr<T> m, T time, int step_count) {
+  return k->p.autoreset && ((double)(time + (T)k->p.nsub * m->timestep) >= k->p.duration ||
+                            step_count + 1 >= k->p.max_steps);
+}
 // One env step (or reset / raw physics call) of the env pair (index, index + 1) of one wave.
 // `list` (wide tier): indices map to env ids through it; resident tier: indices are env ids.
 // In the resident tier an env whose contacts / rows overflowed the resident capacity in any
@@ -383,10 +396,13 @@ __device__ __forceinline__ void commit(MPtr<T> m, KPtr<T> k, const Stepper<T, NV
 // qacc_warmstart, time), so the hand-off is exact: results are bitwise those of one wave running all
 // substeps.
 // ghost: this half-wave mirrors env idx (the single-env schedule's upper half) and commits nothing.
-template <typename T, int NV, bool PGS, typename C, bool ROLL = false>
+// HINTS (the chunk queue): *hint = STEP_* bits of this call.
+template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false>
 __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCache<T, C>* pcache, int idx,
                                           int nidx, const int* list, int s0, int s1, int pair, bool ghost = false,
-                                          int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false) {
+                                          int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false,
+                                          int* hint = nullptr) {
+  if constexpr (HINTS) *hint = 0;
   constexpr bool WIDE = C::WIDE;
   const int lane = opaque_v(threadIdx.x);   // (no lane-derived value hoisted out of the chunk-queue loop)
   const bool up = lane >= HL;
@@ -541,6 +557,9 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
   bool do_reset = mode == MODE_RESET && active;
   const int nsub = (mode == MODE_RESET) ? 0 : ka->p.nsub;
   bool in_reset = false;
+  // wave-uniform: some env of the pair will auto-reset in its NEXT env step (the clock or the step
+  // count it commits here already says so); the chunk queue claims such pairs first (step_kernel_queue)
+  bool will_reset_next = false;
 #ifdef HS_TIMING
   int tot_iter = 0;
   const int titem = (ka->p.queue ? (s0 > 0 ? (nidx + 1) / 2 : 0) + pair : -1);
@@ -632,6 +651,9 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
             write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
             do_reset = true;
           }
+          // (an env that resets below restarts at time = dt, step 0: not flagged)
+          if constexpr (HINTS)
+            will_reset_next = __ballot(active && !do_reset && resets_next(k, st.m, time, step_count)) != 0;
         }
         if (active && !do_reset) {
           if (!defer(k)) {
@@ -755,6 +777,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
       }
     }
   }
+  if constexpr (HINTS) *hint = (will_reset_next ? STEP_WILL_RESET : 0) | (in_reset ? STEP_DID_RESET : 0);
 }
 
 }  // namespace

@@ -35,7 +35,10 @@ __host__ __device__ constexpr int qtag(uint32_t epoch, int t, int stage) {
 // Cost-ordered claims: every queued launch measures each pair's duration (first chunk + last
 // substep, 100 MHz realtime clock) and counts the pair into one of QNB buckets of QBIN ticks,
 // heaviest first; the next queued launch claims the pairs bucket by bucket (a counting sort done
-// by the previous launch), so the launch ends on the cheapest last substeps.  After the flags:
+// by the previous launch), so the launch ends on the cheapest last substeps.  Bucket 0 is not a
+// duration bucket: it takes the pairs with an env that will auto-reset in the next env step (its
+// clock or step count already says so, hs_env_step.h resets_next), whose last item then runs the
+// reset's mj_step as well -- about two substeps that no measured duration foretells.  After the flags:
 // qcost[npairs] (first-chunk durations), cnt[2][QNB] (bucket counts, by epoch parity: the launch
 // reads cnt[e & 1], counts into cnt[(e + 1) & 1], and its last wave out zeroes cnt[e & 1]),
 // ord[2][QNB][npairs] (the pairs of each bucket).  A launch whose read counts do not sum to npairs

@@ -69,11 +69,12 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
 // every pair's last substep (+ obs / reward / auto-reset), so the launch ends on short items
 // instead of a second generation of whole env steps.  Pairs are taken heaviest
 // first by the durations the previous queued launch measured (QNB cost buckets, hs_kernels.h), so
-// the launch ends on the cheapest last substeps; the batch's first queued launch uses a fixed
-// multiplicative permutation (p.qmul).  The order only decides which wave runs which pair when:
-// results are bitwise the same in any order.  Items are claimed only by running waves and a
-// last-substep item waits only on its own pair's first chunk, claimed npairs items earlier by a
-// running wave: no residency can deadlock it.
+// the launch ends on the cheapest last substeps, and ahead of them all the pairs with an env that
+// auto-resets in this step (known since the previous step's commit; their last item runs the reset's
+// mj_step too); the batch's first queued launch uses a fixed multiplicative permutation (p.qmul).
+// The order only decides which wave runs which pair when: results are bitwise the same in any
+// order.  Items are claimed only by running waves and a last-substep item waits only on its own
+// pair's first chunk, claimed npairs items earlier by a running wave: no residency can deadlock it.
 // ROLL: the fused-rollout instance (fp64 Newton engine; launch_step picks it for hs_rollout), so the
 // policy forward's code and registers stay out of the per-step kernel
 template <typename T, int NV, bool PGS, bool ROLL = false>
@@ -145,8 +146,15 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
     const int s0 = last ? nsub - 1 : 0, s1 = (tape || last) ? nsub : nsub - 1;
     const int wait_tag = tape ? (t > 0 ? qtag(epoch, t - 1, 1) : 0) : (last ? qtag(epoch, 0, 0) : 0);
     const int set_tag = tape ? (t < K - 1 ? qtag(epoch, t, 1) : 0) : (last ? 0 : qtag(epoch, 0, 0));
-    step_pair<T, NV, PGS, Resident<T>, ROLL>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair, single && upper,
-                                             wait_tag, set_tag, t, tape);
+    int hint;   // (STEP_* bits, wave-uniform)
+    step_pair<T, NV, PGS, Resident<T>, ROLL, true>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair, single && upper,
+                                                   wait_tag, set_tag, t, tape, &hint);
+#ifdef HS_TIMING
+    // per item (indexed as step_pair's q0 stamps): its claim index within its chunk kind, and whether
+    // it ran the reset pass
+    if (T* dbg = opaque(ka)->b.dbg; dbg && threadIdx.x == 0 && (last ? npairs : 0) + pair < 4096)
+      dbg[28672 + (last ? npairs : 0) + pair] = (T)(2 * ii + ((hint & STEP_DID_RESET) ? 1 : 0));
+#endif
     // the pair's duration for the next launch's order: the first chunk's is kept in qcost (its
     // store trails the hand-off, but the last substep reads it ~100 us later; a stale value only
     // makes the order less exact, never the results different); a tape launch times the pair's
@@ -158,7 +166,12 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
         qs[qs_cost(npairs) + pair] = (int)d;
       } else if (!tape || t == K - 1) {
         const uint32_t tot = tape ? d : d + (uint32_t)qs[qs_cost(npairs) + pair];
-        const int b = QNB - 1 - (int)min(tot / (uint32_t)QBIN, (uint32_t)(QNB - 1));
+        // bucket 0 (claimed first) is kept for the pairs step_pair flags: an env of theirs will
+        // auto-reset in the next env step, so that step's last item also runs the reset's mj_step,
+        // about two substeps, which no measured duration foretells; claimed late, it would end the
+        // launch alone.  The rest go by duration into buckets 1 .. QNB - 1
+        int b = QNB - 1 - (int)min(tot / (uint32_t)QBIN, (uint32_t)(QNB - 2));
+        if (hint & STEP_WILL_RESET) b = 0;
         const int slot = atomicAdd(&qs[qs_cnt(npairs, (epoch + 1) & 1) + b], 1);
         qs[qs_ord(npairs, (epoch + 1) & 1) + (size_t)b * npairs + slot] = pair;
       }

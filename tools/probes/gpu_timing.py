@@ -75,8 +75,8 @@ def main(n=4096, steps=20, prec="fp32", staggered=False):
         busy[int(a_ / span * 199):int(e_ / span * 199) + 1] += 1
     print("  resident waves over the launch (20 bins): " + " ".join(f"{v:.0f}" for v in busy.reshape(20, 10).mean(1)))
     q0 = dbg[20480:20480 + 8192].reshape(-1, 2).astype(np.int64)
-    qw = dbg[28672:28672 + 4096]
-    if q0.any():    # chunk-queue schedule: per item realtime start / end and flag-wait cycles
+    qw = dbg[28672:28672 + 4096]   # per item: 2 * claim index within its chunk kind + (ran the reset pass)
+    if q0.any():    # chunk-queue schedule: per item realtime start / end
         qs, qe = (q0[:, 0] - q0[:, 0].min()) % (1 << 24), (q0[:, 1] - q0[:, 0].min()) % (1 << 24)
         span = qe.max()
         npair = len(life)
@@ -158,7 +158,54 @@ def predict_queue(n=4096, prec="fp64", steps=6):
              d1=np.array([h[1] for h in hist]))
 
 
+def tail(n=4096, prec="fp64", launches=24, out=None):
+    """Chunk-queue schedule, staggered mix: the per-item records of `launches` consecutive per-step
+    launches (pair, chunk kind, claim index, realtime start / end, reset bit), saved as
+    <out>/queue_tail_<prec>_<n>.npz (out: default bench_out_probes/ in the repository), then who
+    is busy at the launch's end and the claim loop replayed under other orders
+    (tools/probes/queue_replay.py)."""
+    import queue_replay
+    model = HsModel(os.path.join(ROOT, "mujocoposelearning_amd", "assets", "humanoid.xml"))
+    b = HsBatch(model, n, precision=prec, seed=1)
+    b.configure(frame_skip=3, duration=10.0, reward_id=0)
+    b.reset()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    b.set_state(time=np.floor(np.arange(n) * 667 / n) * 0.015 + 0.005)
+    for k in range(667 + 5):
+        b.step(torch.rand(n, 21, device="cuda", generator=g) * 2 - 1)
+    b.set_debug(True)
+    np_ = (n + 1) // 2
+    assert 2 * np_ <= 4096, "the timing build records 4096 items"
+    rec = {k: [] for k in ("pair", "kind", "claim", "start", "end", "reset")}
+    for k in range(launches):
+        b.step(torch.rand(n, 21, device="cuda", generator=g) * 2 - 1)
+        dbg = b.get_debug()
+        q0 = dbg[20480:20480 + 4 * np_].reshape(-1, 2).astype(np.int64)
+        fl = dbg[28672:28672 + 2 * np_].astype(np.int64)
+        # 24-bit stamps: relative to the first item's start, then to the launch's first start
+        rel = lambda x: (x - q0[0, 0] + (1 << 23)) % (1 << 24) - (1 << 23)   # noqa: E731
+        st, en = rel(q0[:, 0]), rel(q0[:, 1])
+        en, st = en - st.min(), st - st.min()
+        rec["pair"].append(np.tile(np.arange(np_), 2))
+        rec["kind"].append(np.repeat([0, 1], np_))
+        rec["claim"].append(fl >> 1)
+        rec["reset"].append(fl & 1)
+        rec["start"].append(st)
+        rec["end"].append(en)
+    path = os.path.join(out or os.path.join(ROOT, "bench_out_probes"), f"queue_tail_{prec}_{n}.npz")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez_compressed(path, **{k: np.array(v, dtype=np.int32) for k, v in rec.items()})
+    z = np.load(path)
+    print(f"[{prec} staggered] N={n}: {path}")
+    print(queue_replay.tail_report(z))
+    print(queue_replay.replay_report(z, b.resident_waves)[0])
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[2] == "tail":
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        tail(prec=sys.argv[1], out=sys.argv[3] if len(sys.argv) > 3 else None)
+        sys.exit(0)
     if len(sys.argv) > 2 and sys.argv[2] == "predict_queue":
         predict_queue(prec=sys.argv[1])
         sys.exit(0)
