@@ -16,7 +16,10 @@
  *   hs_step              <- HumanoidEnv.step: frame_skip x mj_step, _get_state, reward, done
  *                           custom_env.py:152-230 (+ SB3 auto-reset on done)
  *   hs_step_tape         <- K x HumanoidEnv.step over a given action tape (open loop), one launch
- *   hs_rollout           <- SB3 PPO.collect_rollouts' per-step loop (policy + env step + buffers), one launch
+ *   hs_rollout           <- SB3 PPO.collect_rollouts' per-step loop (policy + env step + buffers), one launch;
+ *                           pi nets of two ReLU layers of 64 (config.py's net_arch), 128 or 256
+ *   hs_mlp2_forward(_h)  <- ActorCriticPolicy.forward's mlp_extractor + action_net / value_net GEMMs of
+ *                           the same nets (policies.py, SB3 2.3.2), one launch per net
  *   hs_physics_step      <- raw `data.ctrl[:] = a; mujoco.mj_step(model, data)` custom_env.py:159-160
  *   hs_pack_outputs      <- the worker -> main-process pipe transfer of SubprocVecEnv.step_wait (obs,
  *                           rewards, dones, info values; train_sb3.py:203): one packed device buffer
@@ -219,11 +222,19 @@ int hs_last_tape_ms(const hs_batch* b, double* ms);
 int hs_stream_orders(const hs_batch* b, uint64_t* n);
 
 /* Fused PPO rollout (the fp64 Newton engine).  The SB3 MlpPolicy's pi net -- two hidden layers of
- * 256, ReLU, then the action head, fp32 -- with [in][out] row-major weights (w1 [obs_dim][ld1],
- * columns 0..255 the pi net's, w2 [256][256], w3 [256][act_dim]) and the DiagGaussian log_std. */
+ * the same width `hidden` (64, 128 or 256), ReLU, then the action head, fp32 -- with [in][out]
+ * row-major weights and the DiagGaussian log_std:
+ *   w1 [obs_dim][ld1], columns 0..hidden-1 the pi net's (b1 [hidden]);
+ *   w2 [hidden][hidden] (b2 [hidden]);
+ *   w3 [hidden][act_dim] (b3 [act_dim]);
+ *   ld1 >= hidden, ld1 % 4 == 0.
+ * hidden = 0 means 256 (callers from before the field).  The struct must be zero-initialised
+ * (hs_policy p = {0};) before its fields are filled in, so that a caller that does not know `hidden`
+ * passes 0 and not an indeterminate value.  `hidden` sits in what was tail padding: the size stays 72. */
 typedef struct hs_policy {
   const float *w1, *b1, *w2, *b2, *w3, *b3, *log_std;
   int ld1, obs_dim, act_dim;
+  int hidden;
 } hs_policy;
 /* The RolloutBuffer of SB3 PPO.collect_rollouts (on_policy_algorithm.py, 2.3.2) for t_total steps of
  * N envs, device arrays: obs [t_total][N][obs_dim] (row 0 = the rollout's first obs), obs_last
@@ -367,6 +378,11 @@ int hs_gae(const float* rewards, const float* values, const float* episode_start
 int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1, const float* W2,
                     int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A, float* out, int ldo,
                     void* stream);
+/* The same forward for hidden layers of H = 64, 128 or 256 (W1 [H][ld1 >= D], W2 [H][ld2], W3 [A][ld3],
+ * ld2 / ld3 >= H): H / 32 waves per workgroup.  hs_mlp2_forward is this with H = 256. */
+int hs_mlp2_forward_h(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
+                      const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
+                      float* out, int ldo, void* stream);
 int hs_ppo_act(const float* mean, int mean_ld, const float* value, int value_ld, const float* log_std,
                const float* episode_start, uint64_t seed, uint64_t counter, const uint64_t* counter_base,
                int deterministic, float* actions,

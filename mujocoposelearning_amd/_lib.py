@@ -42,7 +42,7 @@ class hs_tape_out(C.Structure):
 
 class hs_policy(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "log_std")] + \
-               [("ld1", C.c_int), ("obs_dim", C.c_int), ("act_dim", C.c_int)]
+               [("ld1", C.c_int), ("obs_dim", C.c_int), ("act_dim", C.c_int), ("hidden", C.c_int)]   # hidden 0: 256
 
 
 class hs_rollout_bufs(C.Structure):
@@ -121,6 +121,7 @@ def lib():
         "hs_adam_clip": (i, [i, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double,
                              vp]),
         "hs_mlp2_forward": (i, [vp, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
+        "hs_mlp2_forward_h": (i, [vp, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
         "hs_colsum_partial_rows": (u64, [u64, u64]),
         "hs_relu_grad_colsum": (i, [vp, vp, u64, u64, vp, vp, vp]),
         "hs_dgrad_mask_partial_rows": (u64, [i, i]),
@@ -146,7 +147,7 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",
             "hs_ppo_act", "hs_ppo_post", "hs_gauss_logp", "hs_gauss_logp_grad",
             "hs_ppo_loss_workspace", "hs_ppo_loss", "hs_ppo_loss_grad", "hs_adam_workspace", "hs_adam_clip",
-            "hs_mlp2_forward", "hs_colsum_partial_rows", "hs_relu_grad_colsum", "hs_dgrad_mask_partial_rows",
+            "hs_mlp2_forward", "hs_mlp2_forward_h", "hs_colsum_partial_rows", "hs_relu_grad_colsum", "hs_dgrad_mask_partial_rows",
             "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_colsum_pair",
             "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version")
 

@@ -686,12 +686,14 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
     return fail("hs_rollout: needs auto-reset with the on-device reset noise and a device reward");
   if (b->cfg.schedule != HS_SCHED_AUTO && b->cfg.schedule != HS_SCHED_FIXED_ORDER)
     return fail("hs_rollout: needs the chunk-queue schedule (HS_SCHED_AUTO or HS_SCHED_FIXED_ORDER)");
+  const int hidden = pol->hidden ? pol->hidden : 256;   // 0: a caller from before the field
   if (pol->obs_dim != b->obs_dim || pol->act_dim != h.nu || pol->act_dim > 32 || pol->obs_dim % 4 ||
-      pol->obs_dim > 512 || pol->ld1 < 256 || pol->ld1 % 4)
+      pol->obs_dim > 512 || (hidden != 64 && hidden != 128 && hidden != 256) || pol->ld1 < hidden || pol->ld1 % 4)
     return fail("hs_rollout: policy shape (obs_dim " + std::to_string(pol->obs_dim) + ", act_dim " +
-                std::to_string(pol->act_dim) + ", ld1 " + std::to_string(pol->ld1) +
+                std::to_string(pol->act_dim) + ", ld1 " + std::to_string(pol->ld1) + ", hidden " +
+                std::to_string(pol->hidden) +
                 ") does not fit the fused forward (obs_dim = the batch's, a multiple of 4 and <= 512; act_dim = nu "
-                "<= 32; hidden layers of 256)");
+                "<= 32; two hidden layers of 64, 128 or 256 (hidden = 0: 256); ld1 >= hidden, a multiple of 4)");
   if (n_steps < 1 || t_begin < 0 || t_begin + n_steps > t_total || n_steps > min_episode_len(b) ||
       n_steps > hs::QTAG_STEPS)
     return fail("hs_rollout: steps [t_begin, t_begin + n_steps) must lie in [0, t_total) and n_steps in [1, " +
@@ -711,7 +713,7 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
   hs::RolloutArgs ro{};
   ro.w1 = pol->w1; ro.b1 = pol->b1; ro.w2 = pol->w2; ro.b2 = pol->b2; ro.w3 = pol->w3; ro.b3 = pol->b3;
   ro.log_std = pol->log_std;
-  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim;
+  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden;
   ro.t_begin = t_begin; ro.t_total = t_total;
   ro.obs = rb->obs; ro.obs_last = rb->obs_last; ro.act = rb->actions; ro.logp = rb->log_probs;
   ro.start = rb->episode_starts; ro.rew = rb->rewards; ro.done = rb->dones; ro.epret = rb->episode_returns;
@@ -937,19 +939,26 @@ int hs_adam_clip(int nt, float* const* params, const float* const* grads, float*
              : -1;
 }
 
-int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1, const float* W2,
-                    int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A, float* out, int ldo,
-                    void* stream) {
-  if (N < 0 || D < 1 || D > 512 || A < 1 || A > 32 || ld1 < D || ld2 < 256 || ld3 < 256 || ldx < D || ldo < A)
-    return fail("hs_mlp2_forward: need N >= 0, 1 <= D <= 512, 1 <= A <= 32, ld1 >= D, ld2 >= 256, ld3 >= 256, "
-                "ldx >= D, ldo >= A");
+int hs_mlp2_forward_h(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
+                      const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
+                      float* out, int ldo, void* stream) {
+  if (H != 64 && H != 128 && H != 256) return fail("hs_mlp2_forward: need H = 64, 128 or 256");
+  if (N < 0 || D < 1 || D > 512 || A < 1 || A > 32 || ld1 < D || ld2 < H || ld3 < H || ldx < D || ldo < A)
+    return fail("hs_mlp2_forward: need N >= 0, 1 <= D <= 512, 1 <= A <= 32, ld1 >= D, ld2 >= " + std::to_string(H) +
+                ", ld3 >= " + std::to_string(H) + ", ldx >= D, ldo >= A");
   if (N == 0) return 0;
   if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out) return fail("hs_mlp2_forward: null buffer");
-  return hip_ok(hs::launch_mlp2_fwd(X, ldx, D, N, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo,
+  return hip_ok(hs::launch_mlp2_fwd(X, ldx, D, N, H, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo,
                                     (hipStream_t)stream),
                 "mlp2_fwd_kernel")
              ? 0
              : -1;
+}
+
+int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1, const float* W2,
+                    int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A, float* out, int ldo,
+                    void* stream) {
+  return hs_mlp2_forward_h(X, ldx, D, N, 256, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo, stream);
 }
 
 uint64_t hs_colsum_partial_rows(uint64_t rows, uint64_t cols) { return hs::colsum_partial_rows(rows, cols); }

@@ -241,16 +241,34 @@ __device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int
 
 // Fused rollout: the SB3 MlpPolicy's pi net (mlp_extractor.policy_net + action_net, fp32 as SB3's
 // policy) on the wave's two envs at once (the lower half-wave's env and the upper's; a ghost half
-// mirrors its partner).  Hidden layers of 256: lane L (of 64) owns outputs 4L .. 4L + 3 for BOTH envs,
-// so each input costs one 16-B weight load per lane (coalesced: the wave reads each weight row once)
-// and two LDS broadcasts (the two envs' inputs).  The head: sub-lane sl < A of each half owns action
-// sl of its half's env.  The obs rows and hidden activations are staged in each half's scratch union
-// (free after the env step).  Returns the action mean of (this half's env, sub-lane sl), 0 for sl >= A.
+// mirrors its partner).  Two hidden layers of H = 64 R (R = 1, 2, 4: RolloutArgs::H = 64, 128, 256):
+// lane L (of 64) owns outputs R L .. R L + R - 1 for BOTH envs, so each input costs one 4 R-byte weight
+// load per lane (coalesced: the wave reads each weight row once) and two LDS broadcasts (the two envs'
+// inputs).  Every output sums its inputs in ascending index, whatever R.  The head: sub-lane sl < A of
+// each half owns action sl of its half's env.  The obs rows and hidden activations are staged in each
+// half's scratch union (free after the env step; x[512] / h[256] hold every width).  Returns the action
+// mean of (this half's env, sub-lane sl), 0 for sl >= A.
 // unroll of the hidden layers' loads (groups of 4 rows) and of the head's: measured 1 / 2 / 4 / 8 in
 // profiles/ab/ab_r4u_policy_unroll.log (4 and 8 tie), a rolling 16-row ring in ab_r4ae_policy_ring.log
+// -- at H = 256 only; the narrower nets (latency-bound: a 256- or 512-byte row per wave) keep them
 constexpr int kPolUnroll = 4, kPolHeadUnroll = 16;
-template <typename T, typename C>
-__device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
+// R consecutive floats as one load of 4 R bytes (p is 4 R-byte aligned)
+template <int R>
+__device__ __forceinline__ void pol_load(const float* p, float (&u)[R]) {
+  static_assert(R == 1 || R == 2 || R == 4, "hidden width 64, 128 or 256");
+  if constexpr (R == 4) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
+  } else if constexpr (R == 2) {
+    const float2 v = *reinterpret_cast<const float2*>(p);
+    u[0] = v.x; u[1] = v.y;
+  } else {
+    u[0] = p[0];
+  }
+}
+template <int R, typename T, typename C>
+__device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
+  constexpr int H = 64 * R;
   const bool up = lane >= HL;
   const int sl = lane & (HL - 1);
   float* xa = smem[0].u.pol.x;   // lower half's env
@@ -263,9 +281,11 @@ __device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratc
   WSYNC();
   auto layer = [&](const float* w, int ld, const float* b, const float* ina, const float* inb, int n, float* outa,
                    float* outb) {
-    const float4 bb = reinterpret_cast<const float4*>(b + 4 * lane)[0];
-    float a[4] = {bb.x, bb.y, bb.z, bb.w}, c[4] = {bb.x, bb.y, bb.z, bb.w};
-    const float* wl = w + 4 * lane;
+    float a[R], c[R];
+    pol_load<R>(b + R * lane, a);
+#pragma unroll
+    for (int j = 0; j < R; j++) c[j] = a[j];
+    const float* wl = w + R * lane;
 #pragma unroll kPolUnroll
     for (int i = 0; i < n; i += 4) {
       const float4 va = *reinterpret_cast<const float4*>(ina + i);
@@ -273,29 +293,46 @@ __device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratc
       const float xs[4] = {va.x, va.y, va.z, va.w}, ys[4] = {vb.x, vb.y, vb.z, vb.w};
 #pragma unroll
       for (int ii = 0; ii < 4; ii++) {
-        const float4 u = *reinterpret_cast<const float4*>(wl + (size_t)(i + ii) * ld);
-        a[0] += xs[ii] * u.x; a[1] += xs[ii] * u.y; a[2] += xs[ii] * u.z; a[3] += xs[ii] * u.w;
-        c[0] += ys[ii] * u.x; c[1] += ys[ii] * u.y; c[2] += ys[ii] * u.z; c[3] += ys[ii] * u.w;
+        float u[R];
+        pol_load<R>(wl + (size_t)(i + ii) * ld, u);
+#pragma unroll
+        for (int j = 0; j < R; j++) a[j] += xs[ii] * u[j];
+#pragma unroll
+        for (int j = 0; j < R; j++) c[j] += ys[ii] * u[j];
       }
     }
     WSYNC();   // every lane has read the inputs (the outputs may alias them)
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      outa[4 * lane + j] = fmaxf(a[j], 0.f);
-      outb[4 * lane + j] = fmaxf(c[j], 0.f);
+    for (int j = 0; j < R; j++) {
+      outa[R * lane + j] = fmaxf(a[j], 0.f);
+      outb[R * lane + j] = fmaxf(c[j], 0.f);
     }
     WSYNC();
   };
   layer(k->ro.w1, ld1, k->ro.b1, xa, xb, D, ha, hb);        // obs -> h1
-  layer(k->ro.w2, 256, k->ro.b2, ha, hb, 256, xa, xb);      // h1 -> h2 (into the obs slots)
+  layer(k->ro.w2, H, k->ro.b2, ha, hb, H, xa, xb);          // h1 -> h2 (into the obs slots)
   float mean = 0.f;
   if (sl < A) {
     mean = k->ro.b3[sl];
     const float* w3 = k->ro.w3 + sl;
 #pragma unroll kPolHeadUnroll
-    for (int i = 0; i < 256; i++) mean += xo[i] * w3[(size_t)i * A];
+    for (int i = 0; i < H; i++) mean += xo[i] * w3[(size_t)i * A];
   }
   return mean;
+}
+// The narrow instances are calls, not inlined: inlined beside the 256 one they cost the rollout kernel
+// registers (4 AGPRs more, profiles/rollout_widths.md), and a call per env step is noise next to the step.
+template <int R, typename T, typename C>
+__device__ __noinline__ float policy_mean_call(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
+  return policy_mean_body<R>(k, obs, smem, lane);
+}
+// one wave-uniform dispatch on the hidden width (hs_rollout admits 64, 128 and 256 only)
+template <typename T, typename C>
+__device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
+  const int H = k->ro.H;
+  if (H == 256) return policy_mean_body<4>(k, obs, smem, lane);
+  if (H == 128) return policy_mean_call<2>(k, obs, smem, lane);
+  return policy_mean_call<1>(k, obs, smem, lane);
 }
 
 template <typename T, int NV, typename C>

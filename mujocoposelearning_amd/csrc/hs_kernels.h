@@ -135,19 +135,20 @@ enum Solver { SOLVER_NEWTON = 0, SOLVER_PGS = 1 };
 // actions: [N][nu] float32 (may be null in MODE_RESET); reset_mask: [N] (null = all);
 // noise_qpos/noise_qvel: [N][nq]/[N][nv] host-supplied reset noise (null = device RNG).
 // Fused PPO rollout (hs_rollout, fp64 engine): a tape launch whose actions come from the policy.
-// After each env step the env's wave runs the SB3 MlpPolicy's pi net (2 hidden layers of 256, ReLU)
-// on the new obs, draws the action (the Philox stream of ppo_act_kernel) and does the rollout
-// buffer bookkeeping of ppo_post_kernel, so a K-step rollout is one launch.  Rollout buffers are
-// indexed by the global step g = t_begin + t.
+// After each env step the env's wave runs the SB3 MlpPolicy's pi net (2 hidden layers of H = 64, 128
+// or 256, ReLU) on the new obs, draws the action (the Philox stream of ppo_act_kernel) and does the
+// rollout buffer bookkeeping of ppo_post_kernel, so a K-step rollout is one launch.  Rollout buffers
+// are indexed by the global step g = t_begin + t.
 struct RolloutArgs {
-  const float* w1;      // [D][ld1] pi layer 1 ([in][out], columns 0..255), ld1 >= 256
-  const float* b1;      // [256]
-  const float* w2;      // [256][256]
-  const float* b2;      // [256]
-  const float* w3;      // [256][A]
+  const float* w1;      // [D][ld1] pi layer 1 ([in][out], columns 0..H-1), ld1 >= H
+  const float* b1;      // [H]
+  const float* w2;      // [H][H]
+  const float* b2;      // [H]
+  const float* w3;      // [H][A]
   const float* b3;      // [A]
   const float* log_std; // [A]
   int ld1, D, A;
+  int H;                // hidden width: 64, 128 or 256 (policy_mean dispatches on it)
   int t_begin, t_total; // global step of this launch's first step; rollout length (n_steps)
   float* obs;           // [t_total][N][D]: rows g + 1 written (row 0 is the caller's)
   float* obs_last;      // [N][D]: the obs after step t_total - 1 (the next rollout's first obs)
@@ -235,8 +236,8 @@ hipError_t launch_ppo_post(const float* reward, const uint8_t* terminated, const
                            uint8_t* boot_out, int obs_dim, float gamma, const float* obs, float* obs_out,
                            size_t obs_floats, float* reward_out, uint8_t* done_out, double* ep_acc,
                            double* ep_return_out, float* episode_start, int N, hipStream_t stream);
-// fused 2-hidden-layer (H = 256) ReLU MLP forward of one packed policy net (ppo.hip mlp2_fwd_kernel)
-hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1,
+// fused 2-hidden-layer (H = 64, 128 or 256) ReLU MLP forward of one packed policy net (ppo.hip mlp2_fwd_kernel)
+hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
                            const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
                            float* out, int ldo, hipStream_t stream);
 // column sums of a row-major [rows][cols] float32 matrix (ppo.hip); workspace of

@@ -536,24 +536,28 @@ __global__ __launch_bounds__(CS_COLS* CS_PHASES) void colsum_pair_kernel(const f
 // ------------------------------------------------------------------ fused 2-hidden-layer MLP forward
 // out = relu(relu(X W1' + b1) W2' + b2) W3' + b3 for one policy net (PPO rollout: the pi net's mean per
 // env step, the vf net's values once per rollout).  The weights come as nn.Linear stores them,
-// [out][in] row-major (W1 [256][ld1], W2 [256][ld2], W3 [A][ld3]): the reduction index k is
+// [out][in] row-major (W1 [H][ld1], W2 [H][ld2], W3 [A][ld3]): the reduction index k is
 // contiguous, so one 16-byte load fetches a lane's B operand for four v_mfma_f32_16x16x4_f32 steps.
 // Within each group of 16 k the MFMA steps run over a permuted k (step j of lane group ak takes
 // k = 16 q + 4 ak + j) so that A (from LDS) and B (from global) are both one b128 per lane per
 // group -- the sum over k is the same, only its order differs from the GEMM's.
-// One workgroup per 16 RB rows, 8 waves: wave w owns output columns [32 w, 32 w + 32) of a hidden
-// layer for all the rows (RB row blocks x 2 column tiles of accumulators).  Its weight rows are read
-// by no other wave, so they stream straight into VGPRs (the MI355X guide's GEMV rule: no LDS round
+// The hidden width H is a template parameter (64, 128 or 256).
+// One workgroup per 16 RB rows, H / 32 waves (8 at H = 256): wave w owns output columns
+// [32 w, 32 w + 32) of a hidden layer for all the rows (RB row blocks x 2 column tiles of
+// accumulators).  Its weight rows are read by no other wave, so they stream straight into VGPRs (the MI355X guide's GEMV rule: no LDS round
 // trip), MLP_PF groups ahead of the MFMAs in a register ring, and each 16-byte weight load feeds RB
 // row blocks; the input tile and the hidden activations live in LDS (dynamic: sized to D).
 // RB = 1 for the per-step pi forward (4096 rows: 256 workgroups, every CU busy), RB = 2 for the
 // rollout-buffer vf pass (half the weight traffic per row).
-// Replaces three library GEMM launches and their two [N][256] HBM round trips.
-constexpr int MLP_H = 256, MLP_WAVES = 8, MLP_TPB = 64 * MLP_WAVES, MLP_MAXD = 512, MLP_PF = 4;
+// Replaces three library GEMM launches and their two [N][H] HBM round trips.
+// MLP_TPB: the threads of the H = 256 instance (and of dgrad_mask_mfma_kernel, which shares the tiles)
+constexpr int MLP_WAVES = 8, MLP_TPB = 64 * MLP_WAVES, MLP_MAXD = 512, MLP_PF = 4;
 // above this many rows two row blocks per wave (A/B with each forced, tools/probes/gpu_mlp2_fwd.py,
-// profiles/r5i: 4096 rows 23.5 vs 26.6 us, 8192 rows 40.2 vs 26.4 us)
+// profiles/r5i: 4096 rows 23.5 vs 26.6 us, 8192 rows 40.2 vs 26.4 us).  Measured at H = 256 only;
+// the H = 64 and 128 instances keep the rule, not re-measured.
 constexpr int MLP_RB2_ROWS = 6144;
-constexpr int MLP_SH = MLP_H + 4;   // LDS row stride (floats) of the hidden tiles: 16-byte aligned rows
+// LDS row stride (floats) of the hidden tiles: 16-byte aligned rows
+__host__ __device__ constexpr int mlp_sh(int H) { return H + 4; }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <bool VEC>
@@ -611,12 +615,16 @@ __device__ __forceinline__ void mlp_groups(const float* a, int sa, const float* 
 }
 
 // dynamic LDS of one workgroup: the input tile (row stride roundup16(D) + 4), later layer 2's output
-// (stride MLP_SH), then layer 1's output
-__host__ __device__ constexpr int mlp_xs_stride(int D) { return ((D + 15) & ~15) + 4 > MLP_SH ? ((D + 15) & ~15) + 4 : MLP_SH; }
-__host__ __device__ constexpr size_t mlp_lds_bytes(int RB, int D) { return (size_t)16 * RB * (mlp_xs_stride(D) + MLP_SH) * 4; }
+// (stride mlp_sh(H)), then layer 1's output
+__host__ __device__ constexpr int mlp_xs_stride(int D, int H) {
+  return ((D + 15) & ~15) + 4 > mlp_sh(H) ? ((D + 15) & ~15) + 4 : mlp_sh(H);
+}
+__host__ __device__ constexpr size_t mlp_lds_bytes(int RB, int D, int H) {
+  return (size_t)16 * RB * (mlp_xs_stride(D, H) + mlp_sh(H)) * 4;
+}
 
-template <bool VEC, int RB>
-__global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restrict__ X, int ldx, int D, int N,
+template <bool VEC, int RB, int H>
+__global__ __launch_bounds__(2 * H) void mlp2_fwd_kernel(const float* __restrict__ X, int ldx, int D, int N,
                                                            const float* __restrict__ W1, int ld1,
                                                            const float* __restrict__ b1,
                                                            const float* __restrict__ W2, int ld2,
@@ -624,9 +632,10 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
                                                            const float* __restrict__ W3, int ld3,
                                                            const float* __restrict__ b3, int A,
                                                            float* __restrict__ out, int ldo) {
-  constexpr int R = 16 * RB;
+  static_assert(H == 64 || H == 128 || H == 256, "hidden width");
+  constexpr int R = 16 * RB, TPB = 2 * H, SH = mlp_sh(H), KQ = H / 64;   // H / 32 waves; KQ head k-slices of 64
   extern __shared__ __attribute__((aligned(16))) float mlp_lds[];
-  const int sx = mlp_xs_stride(D);
+  const int sx = mlp_xs_stride(D, H);
   float* xs = mlp_lds;                 // X tile, then layer 2's output
   float* hs = mlp_lds + R * sx;        // layer 1's output, then the head's partial sums
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -634,7 +643,7 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
   const int row0 = blockIdx.x * R;
   const int Gf = D >> 4, Dp = (D + 15) & ~15;
   if ((D & 3) == 0 && (ldx & 3) == 0 && ((uintptr_t)X & 15) == 0) {   // 16-byte staging: 32 threads per row
-    for (int r = threadIdx.x >> 5; r < R; r += MLP_TPB / 32) {
+    for (int r = threadIdx.x >> 5; r < R; r += TPB / 32) {
       const bool live = row0 + r < N;
       const float* xr = X + (size_t)(live ? row0 + r : 0) * ldx;
       for (int c = 4 * (threadIdx.x & 31); c < Dp; c += 128) {
@@ -643,7 +652,7 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
       }
     }
   } else {
-    for (int e = threadIdx.x; e < R * Dp; e += MLP_TPB) {
+    for (int e = threadIdx.x; e < R * Dp; e += TPB) {
       const int r = e / Dp, c = e - r * Dp;
       xs[r * sx + c] = (row0 + r < N && c < D) ? X[(size_t)(row0 + r) * ldx + c] : 0.f;
     }
@@ -658,7 +667,7 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
       for (int rb = 0; rb < RB; rb++)
 #pragma unroll
         for (int r = 0; r < 4; r++)
-          dst[(16 * rb + 4 * ak + r) * MLP_SH + c0 + 16 * t] = fmaxf(acc[rb][t][r] + bb, 0.f);
+          dst[(16 * rb + 4 * ak + r) * SH + c0 + 16 * t] = fmaxf(acc[rb][t][r] + bb, 0.f);
     }
   };
   {   // layer 1: K = D (full groups pipelined, a partial last group with masked loads)
@@ -680,22 +689,22 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
     epilogue(acc, b1, hs);
   }
   __syncthreads();
-  {   // layer 2: K = 256, into xs (the X tile is dead)
+  {   // layer 2: K = H, into xs (the X tile is dead)
     f32x4 acc[RB][2] = {};
     const float* w0 = W2 + (size_t)c0 * ld2 + 4 * ak;
-    mlp_groups<VEC, RB>(hs + ar * MLP_SH + 4 * ak, 16 * MLP_SH, w0, w0 + (size_t)16 * ld2, MLP_H / 16, acc);
+    mlp_groups<VEC, RB>(hs + ar * SH + 4 * ak, 16 * SH, w0, w0 + (size_t)16 * ld2, H / 16, acc);
     epilogue(acc, b2, xs);
   }
   __syncthreads();
-  // head: A <= 32 columns = 2 tiles x 4 quarters of k over the 8 waves (every wave's 4 weight loads in
-  // flight at once), the quarters' partial sums added through LDS (hs is free after layer 2); a lane
-  // whose column is >= A reads row A - 1 and multiplies zeros
+  // head: A <= 32 columns = 2 tiles x KQ = H / 64 slices of 64 k over the H / 32 waves (every wave's 4
+  // weight loads in flight at once), the slices' partial sums added through LDS (hs is free after
+  // layer 2); a lane whose column is >= A reads row A - 1 and multiplies zeros
   {
     const int t = wave & 1, kq = wave >> 1, col = 16 * t + ar;
     if (16 * t < A) {
       const float* w = W3 + (size_t)(col < A ? col : A - 1) * ld3 + 4 * ak + 64 * kq;
       const float keep = col < A ? 1.f : 0.f;
-      const float* a = xs + ar * MLP_SH + 4 * ak + 64 * kq;
+      const float* a = xs + ar * SH + 4 * ak + 64 * kq;
       f32x4 bw[4];
 #pragma unroll
       for (int g = 0; g < 4; g++) bw[g] = mlp_ld4<VEC>(w + 16 * g) * keep;
@@ -704,7 +713,7 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
       for (int g = 0; g < 4; g++)
 #pragma unroll
         for (int rb = 0; rb < RB; rb++) {
-          const f32x4 x = *reinterpret_cast<const f32x4*>(a + 16 * rb * MLP_SH + 16 * g);
+          const f32x4 x = *reinterpret_cast<const f32x4*>(a + 16 * rb * SH + 16 * g);
 #pragma unroll
           for (int s = 0; s < 4; s++) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[s], bw[g][s], acc[rb], 0, 0, 0);
         }
@@ -715,11 +724,13 @@ __global__ __launch_bounds__(MLP_TPB) void mlp2_fwd_kernel(const float* __restri
     }
   }
   __syncthreads();
-  for (int e = threadIdx.x; e < R * A; e += MLP_TPB) {
+  for (int e = threadIdx.x; e < R * A; e += TPB) {
     const int r = e / A, c = e - r * A;
-    if (row0 + r < N)
-      out[(size_t)(row0 + r) * ldo + c] = b3[c] + ((hs[r * 32 + c] + hs[(R + r) * 32 + c]) +
-                                                   (hs[(2 * R + r) * 32 + c] + hs[(3 * R + r) * 32 + c]));
+    if (row0 + r >= N) continue;
+    float s = hs[r * 32 + c];
+    if constexpr (KQ == 2) s += hs[(R + r) * 32 + c];
+    if constexpr (KQ == 4) s = (s + hs[(R + r) * 32 + c]) + (hs[(2 * R + r) * 32 + c] + hs[(3 * R + r) * 32 + c]);
+    out[(size_t)(row0 + r) * ldo + c] = b3[c] + s;
   }
 }
 
@@ -1043,10 +1054,11 @@ hipError_t launch_colsum_pair(const float* x0, size_t rows0, size_t cols0, float
 }
 
 
-hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1,
+hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
                            const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
                            float* out, int ldo, hipStream_t stream) {
-  if (D < 1 || D > MLP_MAXD || A < 1 || A > 32 || N < 0 || ld1 < D || ld2 < MLP_H || ld3 < MLP_H || ldx < D || ldo < A)
+  if ((H != 64 && H != 128 && H != 256) || D < 1 || D > MLP_MAXD || A < 1 || A > 32 || N < 0 || ld1 < D || ld2 < H ||
+      ld3 < H || ldx < D || ldo < A)
     return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
   // 16-byte weight loads when every weight row starts 16-byte aligned; two row blocks per wave for
@@ -1055,19 +1067,26 @@ hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, const float* W
   const bool vec = al(W1, ld1) && al(W2, ld2) && al(W3, ld3);
   const int RB = N > MLP_RB2_ROWS ? 2 : 1;
   const dim3 grid((N + 16 * RB - 1) / (16 * RB));
-  const size_t lds = mlp_lds_bytes(RB, D);
+  const size_t lds = mlp_lds_bytes(RB, D, H);
   // dynamic LDS above 64 KiB needs the per-kernel opt-in (once per instance)
-#define MLP_LAUNCH(V, B)                                                                                     \
-  do {                                                                                                      \
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp2_fwd_kernel<V, B>), \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                                                       (int)mlp_lds_bytes(B, MLP_MAXD));                    \
-    if (attr != hipSuccess) return attr;                                                                    \
-    mlp2_fwd_kernel<V, B><<<grid, MLP_TPB, lds, stream>>>(X, ldx, D, N, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, \
-                                                          A, out, ldo);                                     \
+#define MLP_LAUNCH(V, B, HH)                                                                                      \
+  do {                                                                                                           \
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp2_fwd_kernel<V, B, HH>), \
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize,               \
+                                                       (int)mlp_lds_bytes(B, MLP_MAXD, HH));                     \
+    if (attr != hipSuccess) return attr;                                                                         \
+    mlp2_fwd_kernel<V, B, HH><<<grid, 2 * HH, lds, stream>>>(X, ldx, D, N, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, \
+                                                             A, out, ldo);                                       \
   } while (0)
-  if (vec) { if (RB == 2) MLP_LAUNCH(true, 2); else MLP_LAUNCH(true, 1); }
-  else { if (RB == 2) MLP_LAUNCH(false, 2); else MLP_LAUNCH(false, 1); }
+#define MLP_LAUNCH_H(HH)                                                      \
+  do {                                                                       \
+    if (vec) { if (RB == 2) MLP_LAUNCH(true, 2, HH); else MLP_LAUNCH(true, 1, HH); }   \
+    else { if (RB == 2) MLP_LAUNCH(false, 2, HH); else MLP_LAUNCH(false, 1, HH); }     \
+  } while (0)
+  if (H == 256) MLP_LAUNCH_H(256);
+  else if (H == 128) MLP_LAUNCH_H(128);
+  else MLP_LAUNCH_H(64);
+#undef MLP_LAUNCH_H
 #undef MLP_LAUNCH
   return hipGetLastError();
 }

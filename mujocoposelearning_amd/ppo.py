@@ -26,13 +26,22 @@ import torch.nn as nn
 
 
 from . import batch as _batch_mod
-from .ppo_ops import (Linear, _GaussLogpFn, _PPOLossFn, _SplitKLinearFn, _SplitKLinearReLUFn,  # noqa: F401
+from .ppo_ops import (FUSED_WIDTHS, Linear, _GaussLogpFn, _PPOLossFn, _SplitKLinearFn, _SplitKLinearReLUFn,  # noqa: F401
                       _SPLITK_ROWS, adam_clip_step, colsum, gae_device, mlp2_forward, mlp_forward,
                       mlp_head_forward, ppo_act, ppo_loss, ppo_post)
 
 FUSED_MLP = True      # rollout forward through the fused hs_mlp2_forward kernel where it applies
 FUSED_MLP_MAX_ROWS = None   # ... up to this many rows (None: any)
 FUSED_ROLLOUT = True  # whole rollouts as hs_rollout launches (policy inside the env kernel) where they apply
+
+
+def _fused_width(w1, mid):
+    """The hidden width H of a packed pi / vf pair (pack_heads: w1 [D, 2H], mid) that the fused kernels
+    run -- two hidden layers of the same width, 64, 128 or 256 -- else None."""
+    H = w1.shape[1] // 2
+    if len(mid) != 1 or w1.shape[1] != 2 * H or H not in FUSED_WIDTHS or tuple(mid[0][0].shape) != (2, H, H):
+        return None
+    return H
 
 
 def _flat_packed(pk):
@@ -158,14 +167,14 @@ class ActorCritic(nn.Module):
         return out[0], out[1, :, 0]
 
     def _fused_mlp_ok(self, obs):
-        """The fused hs_mlp2_forward kernel applies: packed equal pi / vf nets of two hidden layers of
-        256 (ReLU), <= 512 inputs and <= 32 actions, fp32 rows with unit stride on a device, and at
+        """The fused hs_mlp2_forward_h kernel applies: packed equal pi / vf nets of two hidden layers of
+        the same width, 64, 128 or 256 (ReLU), <= 512 inputs and <= 32 actions, fp32 rows with unit stride on a device, and at
         most FUSED_MLP_MAX_ROWS rows (above, the library GEMM chain is faster)."""
         pk = getattr(self, "_packed", None)
         if pk is None or not FUSED_MLP or not obs.is_cuda:
             return False
         w1, _, mid, w3, _ = pk
-        return (len(mid) == 1 and w1.shape[1] == 512 and obs.shape[1] <= 512 and w3.shape[2] <= 32
+        return (_fused_width(w1, mid) is not None and obs.shape[1] <= 512 and w3.shape[2] <= 32
                 and obs.dtype == torch.float32 and obs.stride(1) == 1
                 and (FUSED_MLP_MAX_ROWS is None or obs.shape[0] <= FUSED_MLP_MAX_ROWS))
 
@@ -359,7 +368,8 @@ class PPO:
     def _fused_rollout_args(self):
         """(batch handle, hs_policy) when the whole rollout can run as hs_rollout launches -- the env's
         fp64 engine with the device reward (HumanoidVecEnv.rollout_handle) and a pi net of two ReLU
-        layers of 256 (the reference's net_arch, README.md:44-50) -- else None."""
+        layers of the same width, 64, 128 or 256 (the reference's config.py net_arch is [64, 64], its
+        README.md:44-50 results' [256, 256]) -- else None."""
         if not FUSED_ROLLOUT or self.device.type != "cuda":
             return None
         handle = self.env.rollout_handle() if hasattr(self.env, "rollout_handle") else None
@@ -368,7 +378,8 @@ class PPO:
             return None
         w1, b1, mid, w3, b3 = pk
         D, A = w1.shape[0], w3.shape[2]
-        if (len(mid) != 1 or w1.shape[1] != 512 or D != self.env.obs_dim or D % 4 or D > 512 or A > 32
+        H = _fused_width(w1, mid)
+        if (H is None or D != self.env.obs_dim or D % 4 or D > 512 or A > 32
                 or A != self.env.act_dim):
             return None
         from . import _lib
@@ -376,7 +387,7 @@ class PPO:
         keep = (w1, b1, mid[0][0][0], mid[0][1][0, 0], w3[0], b3[0, 0], ls)
         if not all(t.is_contiguous() for t in keep):
             return None
-        pol = _lib.hs_policy(*[t.data_ptr() for t in keep], w1.shape[1], D, A)
+        pol = _lib.hs_policy(*[t.data_ptr() for t in keep], w1.shape[1], D, A, H)
         return handle, pol, keep
 
     def _rollout_fused(self):
