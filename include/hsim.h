@@ -28,6 +28,7 @@
  *   hs_reward            <- the same on the batch's current states (custom_env.py:263-271 _compute_reward)
  *   hs_debug_lose_handoff   (test hook: mj_step's warning + mj_resetData path, custom_env.py:160)
  *   hs_debug_queue_order    (test view of the chunk queue's next claim order; no counterpart)
+ *   hs_debug_queue_counters (test view of the chunk queue's claim / exit counters; no counterpart)
  *   hs_last_tape_ms, hs_tape_aborts, hs_stream_orders, hs_batch_counters   (diagnostics)
  *   hs_state_io          <- reads/writes of data.qpos/qvel/qacc_warmstart/time/ctrl (custom_env.py:105-117)
  *   hs_get_buffers       <- data.* arrays as device buffers (obs, reward, terminated, ...)
@@ -307,6 +308,11 @@ int hs_debug_lose_handoff(hs_batch* b, int env);
  * to `out` and returns the count; 0 when that launch would claim in the fixed permutation (no
  * queued launch yet, or a schedule other than HS_SCHED_AUTO); -1 on error.  Synchronous. */
 int hs_debug_queue_order(hs_batch* b, int* out, int n);
+/* Debug view of the chunk queue's sync words (tests only): out[0..3] = claim counter, exit counter,
+ * launch epoch, tape-abort word.  Between launches both counters are 0 (the last wave out of every
+ * queued launch resets them) and the epoch counts the queued launches so far.  Returns 0, or -1 on
+ * error (a batch without queue buffers included).  Synchronous. */
+int hs_debug_queue_counters(hs_batch* b, int* out);
 
 /* Synchronous host<->device state copy in fp64.  dir 0: device -> host, 1: host -> device.
  * Any pointer may be NULL.  Arrays are [N][nq], [N][nv], [N][nv], [N], [N][nu]. */

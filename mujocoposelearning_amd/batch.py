@@ -501,6 +501,13 @@ class HsBatch:
             raise _lib.HsimError(lib().hs_last_error().decode())
         return out[:cnt].copy()
 
+    def queue_counters(self):
+        """Tests only (hs_debug_queue_counters): the first group's chunk-queue sync words as
+        {"head", "exit", "epoch", "abort"}; head and exit are 0 between launches.  Synchronous."""
+        out = np.zeros(4, dtype=np.int32)
+        check(lib().hs_debug_queue_counters(self._h, out.ctypes.data))
+        return dict(zip(("head", "exit", "epoch", "abort"), out.tolist()))
+
     def get_debug(self):
         out = np.zeros(_lib.DBGDIM)
         check(lib().hs_get_debug(self._h, out.ctypes.data, _lib.DBGDIM))

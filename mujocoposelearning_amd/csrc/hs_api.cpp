@@ -765,6 +765,16 @@ int hs_debug_queue_order(hs_batch* b, int* out, int n) {
   return nunits;
 }
 
+int hs_debug_queue_counters(hs_batch* b, int* out) {
+  if (!b || !out) return fail("hs_debug_queue_counters: null argument");
+  if (!b->qsync) return fail("hs_debug_queue_counters: the batch has no queue buffers");
+  DeviceGuard g(b->device);
+  if (!hip_ok(hipDeviceSynchronize(), "sync")) return -1;
+  static_assert(hs::QS_HEAD == 0 && hs::QS_EXIT == 1 && hs::QS_EPOCH == 2 && hs::QS_ABORT == 3, "sync word order");
+  if (!hip_ok(hipMemcpy(out, b->qsync, 4 * sizeof(int), hipMemcpyDeviceToHost), "qsync")) return -1;
+  return 0;
+}
+
 int hs_set_autoreset_noise(hs_batch* b, const void* qpos_noise, const void* qvel_noise) {
   if (!b) return fail("null batch");
   if ((qpos_noise == nullptr) != (qvel_noise == nullptr)) return fail("bind both noise arrays or neither");

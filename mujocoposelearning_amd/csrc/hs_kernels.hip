@@ -73,8 +73,11 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
 // auto-resets in this step (known since the previous step's commit; their last item runs the reset's
 // mj_step too); the batch's first queued launch uses a fixed multiplicative permutation (p.qmul).
 // The order only decides which wave runs which pair when: results are bitwise the same in any
-// order.  Items are claimed only by running waves and a last-substep item waits only on its own
-// pair's first chunk, claimed npairs items earlier by a running wave: no residency can deadlock it.
+// order.  Items are claimed only by running waves -- a wave's first item, item blockIdx.x, is its
+// own from the start, and the grid is no larger than the waves the GPU holds at once -- and a
+// last-substep item waits only on its own pair's first chunk, claimed npairs items earlier by a
+// running wave: the launch cannot deadlock.  (Should other work keep part of the grid from starting,
+// a wave may wait for the first chunk of a wave that has not started; the wait is bounded as ever.)
 // ROLL: the fused-rollout instance (fp64 Newton engine; launch_step picks it for hs_rollout), so the
 // policy forward's code and registers stay out of the per-step kernel
 template <typename T, int NV, bool PGS, bool ROLL = false>
@@ -106,14 +109,31 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
     if (lane == 0) qpre[0] = 0;
     WSYNC();
   }
+  // The wave's held claim: the index of the item it runs next, or -1 (one LDS word, so nothing is
+  // kept in registers across an item).  Items [0, gridDim.x) are never claimed from the counter:
+  // item blockIdx.x is this wave's first, held from the start, so a launch does not open with one
+  // returning atomic per wave on the same word (1024 of them: the last is served ~11 us in).  Later
+  // claims are gridDim.x + the counter's value.  A held first item counts as claimed by a running
+  // wave only if its wave runs: launch_step never makes the grid larger than the waves this
+  // instance holds at once (queue_waves).  A wave whose first item lies past the end (a launch with
+  // fewer items than waves) leaves like one whose claim does.
+  __shared__ int qheld;
+  if (threadIdx.x == 0) qheld = (int)blockIdx.x;
+  WSYNC();
   for (;;) {
     const KPtr<T> k = opaque(ka);       // nothing uniform kept live across items
     const bool single = k->p.single != 0;
     const int nsub = k->p.nsub, npairs = single ? k->nenv : (k->nenv + 1) / 2, K = k->p.nsteps;   // (units)
     int* qs = k->b.qsync;
-    int i = 0;
-    if (threadIdx.x == 0) i = atomicAdd(&qs[QS_HEAD], 1);
-    i = __builtin_amdgcn_readfirstlane(i);
+    int i = __builtin_amdgcn_readfirstlane(qheld);
+    WSYNC();
+    if (i < 0) {
+      if (threadIdx.x == 0) i = (int)gridDim.x + atomicAdd(&qs[QS_HEAD], 1);
+      i = __builtin_amdgcn_readfirstlane(i);
+    } else if (threadIdx.x == 0) {
+      qheld = -1;   // consumed: a wave holds at most one claim
+    }
+    WSYNC();
     // tape launch: K whole env steps per pair, step-major (step t of every pair, then step t + 1);
     // one env step: every pair's first chunk, then every pair's last substep
     const bool tape = K > 1 || k->ro.obs != nullptr;   // (a fused rollout is a tape launch even for K = 1)
@@ -365,6 +385,28 @@ int resident_waves(bool pgs) {
   return v > 0 ? v : 0;
 }
 
+// waves of a chunk-queue instance the current device holds at once (0 if unknown), cached per
+// device.  The queue's grid must not exceed it: a wave's first item is item blockIdx.x, taken without
+// a claim (step_kernel_queue), so every wave of the grid has to be running from the start.  It is
+// below resident_waves() where the queue instance's occupancy is below the direct kernel's (the fp32
+// Newton engine: 1 wave per SIMD against 2).
+template <typename T, bool PGS, bool ROLL>
+int queue_waves() {
+  constexpr int MAXDEV = 64;
+  static int cache[MAXDEV] = {};   // 0: not yet computed
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return 0;
+  if (cache[dev] != 0) return cache[dev] > 0 ? cache[dev] : 0;
+  int per_cu = 0, v = -1;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL>, WAVE, 0) == hipSuccess &&
+      per_cu > 0)
+    v = per_cu * prop.multiProcessorCount;
+  cache[dev] = v;
+  return v > 0 ? v : 0;
+}
+
 template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
@@ -427,20 +469,33 @@ hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b
   // one solver's launches: the resident tier (chunk-queue or direct schedule), then the wide tier's
   // re-run of the envs it deferred (a generic lambda, not a function template: the kernel instances
   // then keep their order in the code object)
-  auto launch_tiers = [&](auto pgs) {
+  // (the queue's grid: no more waves than its instance holds at once, queue_waves)
+  auto queue_grid = [&](int held) { return dim3(std::min((int)grid.x, held)); };
+  auto launch_tiers = [&](auto pgs) -> hipError_t {
     constexpr bool PGS = decltype(pgs)::value;
-    if (args.p.queue) hipLaunchKernelGGL((step_kernel_queue<T, 27, PGS>), grid, block, 0, stream, args);
-    else hipLaunchKernelGGL((step_kernel<T, 27, PGS>), grid, block, 0, stream, args);
+    if (args.p.queue) {
+      const int held = queue_waves<T, PGS, false>();
+      if (held <= 0) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((step_kernel_queue<T, 27, PGS>), queue_grid(held), block, 0, stream, args);
+    } else {
+      hipLaunchKernelGGL((step_kernel<T, 27, PGS>), grid, block, 0, stream, args);
+    }
     if (b.redo && !tape_launch) hipLaunchKernelGGL((step_kernel_wide<T, 27, PGS>), wgrid, block, 0, stream, args);
+    return hipSuccess;
   };
+  hipError_t rc = hipSuccess;
   if (p.solver == SOLVER_PGS) {
-    launch_tiers(std::true_type{});
+    rc = launch_tiers(std::true_type{});
   } else if (ro) {
-    if constexpr (sizeof(T) == 8) hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true>), grid, block, 0, stream, args);
+    if constexpr (sizeof(T) == 8) {
+      const int held = queue_waves<T, false, true>();
+      if (held <= 0) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true>), queue_grid(held), block, 0, stream, args);
+    }
   } else {
-    launch_tiers(std::false_type{});
+    rc = launch_tiers(std::false_type{});
   }
-  return hipGetLastError();
+  return rc != hipSuccess ? rc : hipGetLastError();
 }
 
 template <typename T>

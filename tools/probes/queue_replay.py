@@ -17,7 +17,10 @@ Orders:
   d  pairs ordered by the true duration of their last item, longest first (the ceiling of any
      rule that orders the launch's end)
 
-    python tools/probes/queue_replay.py bench_out_probes/queue_tail_fp64_4096.npz [waves]
+Claim point (lead_report): the used order with the next claim issued 0 ticks, `tail` ticks (the
+Euler + obs remainder after an item's last solve) and a whole item before the current item ends.
+
+    python tools/probes/queue_replay.py bench_out_probes/queue_tail_fp64_4096.npz [waves [tail ticks]]
 """
 import heapq
 import sys
@@ -25,22 +28,39 @@ import sys
 import numpy as np
 
 
-def replay(d0, d1, order, waves):
+def _leads(lead, d0, d1):
+    """`lead` as two per-pair arrays (first chunks, last items): a constant, or an array [2][npairs]
+    (kind, pair).  np.inf: the claim is issued when the item starts (a whole-item lead)."""
+    lead = np.asarray(lead, dtype=float)
+    if lead.ndim == 0:
+        return np.full(len(d0), float(lead)), np.full(len(d1), float(lead))
+    assert lead.shape == (2, len(d0)), lead.shape
+    return lead[0], lead[1]
+
+
+def replay(d0, d1, order, waves, lead=0.0):
     """Makespan of one launch: first-chunk durations d0[pair], last-item durations d1[pair], the
-    pairs claimed in `order` for both chunk kinds, on `waves` waves."""
-    free = [0.0] * min(waves, 2 * len(order))
-    heapq.heapify(free)
+    pairs claimed in `order` for both chunk kinds, on `waves` waves.  A wave issues its next claim
+    `lead` ticks before its current item ends (never before the item starts); the claims are served
+    in the order they are issued and the claimed item starts when the wave's current one has ended.
+    lead = 0 is the claim loop without claim-ahead."""
+    l0, l1 = _leads(lead, d0, d1)
+    nw = min(waves, 2 * len(order))
+    claims = [(0.0, w) for w in range(nw)]      # (time the wave's pending claim was issued, wave)
+    heapq.heapify(claims)
+    free = [0.0] * nw                           # when the wave's current item ends
     done0 = {}
     end = 0.0
-    for p in order:
-        t = heapq.heappop(free) + d0[p]
-        done0[p] = t
-        end = max(end, t)
-        heapq.heappush(free, t)
-    for p in order:
-        t = max(heapq.heappop(free), done0[p]) + d1[p]
-        end = max(end, t)
-        heapq.heappush(free, t)
+    for kind, d, l in ((0, d0, l0), (1, d1, l1)):
+        for p in order:
+            _, w = heapq.heappop(claims)
+            start = free[w] if kind == 0 else max(free[w], done0[p])
+            t = start + d[p]
+            if kind == 0:
+                done0[p] = t
+            end = max(end, t)
+            free[w] = t
+            heapq.heappush(claims, (max(start, t - l[p]), w))
     return end
 
 
@@ -140,7 +160,30 @@ def replay_report(z, waves=1024):
     return "\n".join(lines), {k: float(np.mean(v)) for k, v in res.items()}
 
 
+def lead_report(z, waves=1024, tail=1000.0):
+    """The claim point of a claim-ahead: the used order replayed with the claim issued at the end of
+    the item (no lead), `tail` ticks before it (the nearly constant Euler + obs / commit remainder
+    after the item's last solve), and at its start (a whole item early)."""
+    L = z["pair"].shape[0]
+    res = {"none": [], "tail": [], "item": []}
+    for launch in range(L):
+        used, d0, d1, _, _ = per_pair(z, launch)
+        for k, lead in (("none", 0.0), ("tail", tail), ("item", np.inf)):
+            res[k].append(replay(d0, d1, used, waves, lead))
+    us = 10 / 1e3
+    a = np.mean(res["none"])
+    lines = [f"claim point on {waves} waves, {L} launches, the order used"]
+    for k, name in (("none", "claim when the item ends (lead 0)"),
+                    ("tail", f"claim {tail * us:.1f} us before the item ends"),
+                    ("item", "claim when the item starts (whole item)")):
+        m = np.mean(res[k])
+        lines.append(f"  {name:42s} makespan {m * us:7.1f} us  {100 * (a - m) / a:+5.2f} % vs lead 0")
+    return "\n".join(lines), {k: float(np.mean(v)) for k, v in res.items()}
+
+
 if __name__ == "__main__":
     z = np.load(sys.argv[1])
+    waves = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
     print(tail_report(z))
-    print(replay_report(z, int(sys.argv[2]) if len(sys.argv) > 2 else 1024)[0])
+    print(replay_report(z, waves)[0])
+    print(lead_report(z, waves, float(sys.argv[3]) if len(sys.argv) > 3 else 1000.0)[0])
