@@ -16,10 +16,11 @@
  *   hs_step              <- HumanoidEnv.step: frame_skip x mj_step, _get_state, reward, done
  *                           custom_env.py:152-230 (+ SB3 auto-reset on done)
  *   hs_step_tape         <- K x HumanoidEnv.step over a given action tape (open loop), one launch
- *   hs_rollout           <- SB3 PPO.collect_rollouts' per-step loop (policy + env step + buffers), one launch;
- *                           pi nets of two ReLU layers of 64 (config.py's net_arch), 128 or 256
- *   hs_mlp2_forward(_h)  <- ActorCriticPolicy.forward's mlp_extractor + action_net / value_net GEMMs of
- *                           the same nets (policies.py, SB3 2.3.2), one launch per net
+ *   hs_rollout(_act)     <- SB3 PPO.collect_rollouts' per-step loop (policy + env step + buffers), one launch;
+ *                           pi nets of two layers of 64 (config.py's net_arch), 128 or 256, ReLU (config.py's
+ *                           activation_fn) or Tanh (SB3's MlpPolicy default, policies.py)
+ *   hs_mlp2_forward(_h, _act) <- ActorCriticPolicy.forward's mlp_extractor + action_net / value_net GEMMs
+ *                           of the same nets (policies.py, SB3 2.3.2), one launch per net
  *   hs_physics_step      <- raw `data.ctrl[:] = a; mujoco.mj_step(model, data)` custom_env.py:159-160
  *   hs_pack_outputs      <- the worker -> main-process pipe transfer of SubprocVecEnv.step_wait (obs,
  *                           rewards, dones, info values; train_sb3.py:203): one packed device buffer
@@ -46,10 +47,11 @@
  *                           surrogate, value MSE (stable_baselines3 2.3.2 ppo/ppo.py) and its backward
  *   hs_adam_clip         <- torch.nn.utils.clip_grad_norm_(max_grad_norm) + torch.optim.Adam.step of
  *                           SB3 PPO.train (ppo.py: max_grad_norm 0.5, Adam eps 1e-5)
- *   hs_dgrad_mask        <- the input gradient of each layer fed by a ReLU, fused with that ReLU's
- *                           backward (same loss.backward())
- *   hs_relu_grad_colsum, hs_colsum_pair <- the ReLU backward + bias / weight-gradient sums of the
- *                           same loss.backward() (fewer passes and launches)
+ *   hs_dgrad_mask, hs_dgrad_act <- the input gradient of each layer fed by an activation (ReLU; ReLU or
+ *                           Tanh), fused with that activation's backward (same loss.backward())
+ *   hs_relu_grad_colsum, hs_act_grad_colsum, hs_colsum_pair <- the activation backward (threshold_backward /
+ *                           tanh_backward) + bias / weight-gradient sums of the same loss.backward()
+ *                           (fewer passes and launches)
  *   hs_colsum            <- the bias-gradient and split-K weight-gradient reductions of the PPO
  *                           update's loss.backward() (SB3 PPO.train, ppo.py; train_sb3.py:229)
  *
@@ -222,8 +224,16 @@ int hs_last_tape_ms(const hs_batch* b, double* ms);
 /* cross-stream waits the library inserted to keep this batch's launches ordered (diagnostics) */
 int hs_stream_orders(const hs_batch* b, uint64_t* n);
 
+/* Hidden-layer activation of a policy net: SB3's policy_kwargs["activation_fn"] -- nn.ReLU (the reference's
+ * config.py) or nn.Tanh (the default of ActorCriticPolicy, policies.py, SB3 2.3.2).  The Tanh is one
+ * function in every kernel: sign(x) (1 - 2 / (exp(2 |x|) + 1)), odd, exact at 0, +-1 beyond |x| = 16,
+ * within ~2^-23 of the exact tanh. */
+#define HS_ACT_RELU 0
+#define HS_ACT_TANH 1
+
 /* Fused PPO rollout (the fp64 Newton engine).  The SB3 MlpPolicy's pi net -- two hidden layers of
- * the same width `hidden` (64, 128 or 256), ReLU, then the action head, fp32 -- with [in][out]
+ * the same width `hidden` (64, 128 or 256), ReLU or Tanh (the `act` of hs_rollout_act; the struct does
+ * not carry it), then the action head, fp32 -- with [in][out]
  * row-major weights and the DiagGaussian log_std:
  *   w1 [obs_dim][ld1], columns 0..hidden-1 the pi net's (b1 [hidden]);
  *   w2 [hidden][hidden] (b2 [hidden]);
@@ -275,6 +285,12 @@ typedef struct hs_rollout_bufs {
  * to the call's start, and the caller collects these steps step by step (hs_step).  Synchronizes. */
 int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int t_begin, int n_steps, int t_total,
                void* stream);
+/* hs_rollout for a pi net whose hidden activation is `act` (HS_ACT_RELU or HS_ACT_TANH; anything else is an
+ * error): the same per-step loop of SB3 collect_rollouts (on_policy_algorithm.py) for an MlpPolicy built with
+ * activation_fn = nn.ReLU or nn.Tanh (policies.py).  hs_rollout is this with HS_ACT_RELU; hs_policy and
+ * hs_rollout_bufs are the same structs. */
+int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
+                   int t_total, void* stream);
 int hs_rollout_max_steps(const hs_batch* b);
 /* Auto-reset noise source of hs_step: [N][nq] / [N][nv] device arrays of the batch precision with
  * the raw U(-noise_scale, noise_scale) draws of the NEXT reset of each env (the kernel applies the
@@ -374,7 +390,7 @@ int hs_gae(const float* rewards, const float* values, const float* episode_start
  * uint64) is not NULL -- graph replays then draw fresh noise; z = 0 when deterministic != 0); writes
  * actions [N][A] (unclipped, the buffer copy), actions_clipped [N][A] (clip to [-1, 1], what the
  * env steps with), log_prob [N], values [N] and episode_starts_out [N].  Asynchronous on `stream`. */
-/* Fused forward of one 2-hidden-layer ReLU MLP (H = 256): out[N][A] = relu(relu(X W1' + b1) W2' + b2)
+/* Fused forward of one 2-hidden-layer MLP (H = 256, ReLU; hs_mlp2_forward_act: ReLU or Tanh): out[N][A] = relu(relu(X W1' + b1) W2' + b2)
  * W3' + b3, weights as nn.Linear stores them, [out][in] row-major (W1 [256][ld1 >= D], W2 [256][ld2],
  * W3 [A][ld3], ld2 / ld3 >= 256); D <= 512, A <= 32.  16-byte weight loads when every weight row
  * is 16-byte aligned, element loads otherwise.  Replaces the three GEMMs of SB3's MlpPolicy forward (ActorCriticPolicy.forward ->
@@ -389,6 +405,12 @@ int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int 
 int hs_mlp2_forward_h(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
                       const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
                       float* out, int ldo, void* stream);
+/* The same forward with the hidden activation `act` (HS_ACT_RELU or HS_ACT_TANH): out = act(act(X W1' + b1)
+ * W2' + b2) W3' + b3, the mlp_extractor + head of an MlpPolicy built with activation_fn = nn.ReLU or nn.Tanh
+ * (ActorCriticPolicy.forward, policies.py, SB3 2.3.2).  hs_mlp2_forward_h is this with HS_ACT_RELU. */
+int hs_mlp2_forward_act(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
+                        const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
+                        const float* b3, int A, float* out, int ldo, void* stream);
 int hs_ppo_act(const float* mean, int mean_ld, const float* value, int value_ld, const float* log_std,
                const float* episode_start, uint64_t seed, uint64_t counter, const uint64_t* counter_base,
                int deterministic, float* actions,
@@ -455,8 +477,13 @@ int hs_adam_clip(int nt, float* const* params, const float* const* grads, float*
 uint64_t hs_colsum_partial_rows(uint64_t rows, uint64_t cols);
 int hs_relu_grad_colsum(const float* g, const float* y, uint64_t rows, uint64_t cols, float* gm, float* partial,
                         void* stream);
-/* Input gradient of a Linear layer fed by a ReLU, fused with that ReLU's backward and the first
- * pass of its bias gradient: GX[B][N] = (G W) masked by X > 0, partial[p][N] = column sums of GX
+/* The same pass for the activation `act` of the layer whose output is y: HS_ACT_RELU as above, HS_ACT_TANH
+ * gm = g (1 - y^2) -- threshold_backward / tanh_backward of SB3's loss.backward() through mlp_extractor
+ * (policies.py, SB3 2.3.2) with the bias sum's first read.  hs_relu_grad_colsum is this with HS_ACT_RELU. */
+int hs_act_grad_colsum(const float* g, const float* y, uint64_t rows, uint64_t cols, int act, float* gm,
+                       float* partial, void* stream);
+/* Input gradient of a Linear layer fed by an activation, fused with that activation's backward and the
+ * first pass of its bias gradient (hs_dgrad_mask: ReLU): GX[B][N] = (G W) masked by X > 0, partial[p][N] = column sums of GX
  * over row block p, p < hs_dgrad_mask_partial_rows(B, K).  G [B][K] (row stride ldg) is the layer's
  * output gradient, W [K][N] its weight as nn.Linear stores it ([out][in], row stride ldw), X [B][N]
  * (ldx) its input = the previous layer's ReLU output; GX is contiguous.  N = 256; K <= 32 (a policy
@@ -468,6 +495,12 @@ uint64_t hs_dgrad_mask_partial_rows(int B, int K);
 uint64_t hs_dgrad_mask_workspace(int K);
 int hs_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B, int N,
                   float* GX, float* partial, float* workspace, void* stream);
+/* The same for a layer fed by the activation `act`: HS_ACT_RELU as above, HS_ACT_TANH GX = (G W) (1 - X^2), X
+ * the previous layer's tanh output (nothing else needs to be kept for the backward).  Replaces `g @ w` +
+ * tanh_backward + the bias sum's first read of SB3's loss.backward() through a Tanh mlp_extractor
+ * (policies.py, SB3 2.3.2).  Same shapes, workspace and partial rows; hs_dgrad_mask is this with HS_ACT_RELU. */
+int hs_dgrad_act(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B, int N,
+                 int act, float* GX, float* partial, float* workspace, void* stream);
 /* Two single-pass column sums in one launch: out0[c] = sum_r x0[r][c] ([rows0][cols0]) and
  * out1[c] = sum_r x1[r][c] ([rows1][cols1]) -- for short matrices (split-K slices, partials). */
 int hs_colsum_pair(const float* x0, uint64_t rows0, uint64_t cols0, float* out0, const float* x1, uint64_t rows1,

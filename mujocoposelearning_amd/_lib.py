@@ -19,6 +19,7 @@ HS_NWARN = 5
 HS_AUXDIM = 40
 HS_OUT_AUX, HS_OUT_CTRL = 1, 2   # hs_env_config.outputs bits
 HS_SCHED_AUTO, HS_SCHED_DIRECT, HS_SCHED_SINGLE, HS_SCHED_FIXED_ORDER = 0, 1, 2, 3   # hs_env_config.schedule
+HS_ACT_RELU, HS_ACT_TANH = 0, 1   # hidden activation of hs_rollout_act / hs_mlp2_forward_act / hs_dgrad_act
 DBGDIM = 32768
 
 
@@ -95,6 +96,7 @@ def lib():
         "hs_last_tape_ms": (i, [vp, vp]),
         "hs_stream_orders": (i, [vp, vp]),
         "hs_rollout": (i, [vp, vp, vp, i, i, i, vp]),
+        "hs_rollout_act": (i, [vp, vp, i, vp, i, i, i, vp]),
         "hs_rollout_max_steps": (i, [vp]),
         "hs_set_autoreset_noise": (i, [vp, vp, vp]),
         "hs_physics_step": (i, [vp, vp, i, vp]),
@@ -123,11 +125,14 @@ def lib():
                              vp]),
         "hs_mlp2_forward": (i, [vp, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
         "hs_mlp2_forward_h": (i, [vp, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
+        "hs_mlp2_forward_act": (i, [vp, i, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
         "hs_colsum_partial_rows": (u64, [u64, u64]),
         "hs_relu_grad_colsum": (i, [vp, vp, u64, u64, vp, vp, vp]),
+        "hs_act_grad_colsum": (i, [vp, vp, u64, u64, i, vp, vp, vp]),
         "hs_dgrad_mask_partial_rows": (u64, [i, i]),
         "hs_dgrad_mask_workspace": (u64, [i]),
         "hs_dgrad_mask": (i, [vp, i, i, vp, i, vp, i, i, i, vp, vp, vp, vp]),
+        "hs_dgrad_act": (i, [vp, i, i, vp, i, vp, i, i, i, i, vp, vp, vp, vp]),
         "hs_colsum_pair": (i, [vp, u64, u64, vp, vp, u64, u64, vp, vp]),
         "hs_colsum_workspace": (u64, [u64, u64]),
         "hs_colsum": (i, [vp, u64, u64, vp, vp, vp, vp]),
@@ -143,13 +148,14 @@ def lib():
 
 
 EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create", "hs_batch_destroy",
-            "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_max_steps", "hs_set_autoreset_noise",
+            "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_set_autoreset_noise",
             "hs_physics_step", "hs_state_io", "hs_kinematics", "hs_set_debug", "hs_debug_lose_handoff", "hs_debug_queue_order", "hs_debug_queue_counters", "hs_get_debug", "hs_synchronize", "hs_batch_counters", "hs_gae",
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",
             "hs_ppo_act", "hs_ppo_post", "hs_gauss_logp", "hs_gauss_logp_grad",
             "hs_ppo_loss_workspace", "hs_ppo_loss", "hs_ppo_loss_grad", "hs_adam_workspace", "hs_adam_clip",
-            "hs_mlp2_forward", "hs_mlp2_forward_h", "hs_colsum_partial_rows", "hs_relu_grad_colsum", "hs_dgrad_mask_partial_rows",
-            "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_colsum_pair",
+            "hs_mlp2_forward", "hs_mlp2_forward_h", "hs_mlp2_forward_act", "hs_colsum_partial_rows", "hs_relu_grad_colsum",
+            "hs_act_grad_colsum", "hs_dgrad_mask_partial_rows",
+            "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_dgrad_act", "hs_colsum_pair",
             "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version")
 
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/hsim.h"
+#include "hs_act.h"
 #include "hs_kernels.h"
 #include "mjcf.h"
 
@@ -671,6 +672,8 @@ int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_o
   return 0;
 }
 
+static_assert(HS_ACT_RELU == hs::ACT_RELU && HS_ACT_TANH == hs::ACT_TANH, "activation ids");
+
 int hs_rollout_max_steps(const hs_batch* b) {
   if (!b) return fail("null batch");
   return std::min(min_episode_len(b), hs::QTAG_STEPS);
@@ -678,6 +681,11 @@ int hs_rollout_max_steps(const hs_batch* b) {
 
 int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int t_begin, int n_steps, int t_total,
                void* stream) {
+  return hs_rollout_act(b, pol, HS_ACT_RELU, rb, t_begin, n_steps, t_total, stream);
+}
+
+int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
+                   int t_total, void* stream) {
   if (!b || !pol || !rb) return fail("null argument");
   const auto& h = b->model->host;
   if (b->precision != HS_FP64 || h.solver == 1)
@@ -694,6 +702,8 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
                 std::to_string(pol->hidden) +
                 ") does not fit the fused forward (obs_dim = the batch's, a multiple of 4 and <= 512; act_dim = nu "
                 "<= 32; two hidden layers of 64, 128 or 256 (hidden = 0: 256); ld1 >= hidden, a multiple of 4)");
+  if (act != HS_ACT_RELU && act != HS_ACT_TANH)
+    return fail("hs_rollout: activation " + std::to_string(act) + " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
   if (n_steps < 1 || t_begin < 0 || t_begin + n_steps > t_total || n_steps > min_episode_len(b) ||
       n_steps > hs::QTAG_STEPS)
     return fail("hs_rollout: steps [t_begin, t_begin + n_steps) must lie in [0, t_total) and n_steps in [1, " +
@@ -713,7 +723,7 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
   hs::RolloutArgs ro{};
   ro.w1 = pol->w1; ro.b1 = pol->b1; ro.w2 = pol->w2; ro.b2 = pol->b2; ro.w3 = pol->w3; ro.b3 = pol->b3;
   ro.log_std = pol->log_std;
-  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden;
+  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden; ro.hact = act;
   ro.t_begin = t_begin; ro.t_total = t_total;
   ro.obs = rb->obs; ro.obs_last = rb->obs_last; ro.act = rb->actions; ro.logp = rb->log_probs;
   ro.start = rb->episode_starts; ro.rew = rb->rewards; ro.done = rb->dones; ro.epret = rb->episode_returns;
@@ -949,20 +959,29 @@ int hs_adam_clip(int nt, float* const* params, const float* const* grads, float*
              : -1;
 }
 
-int hs_mlp2_forward_h(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
-                      const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
-                      float* out, int ldo, void* stream) {
+int hs_mlp2_forward_act(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
+                        const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
+                        const float* b3, int A, float* out, int ldo, void* stream) {
+  if (act != HS_ACT_RELU && act != HS_ACT_TANH)
+    return fail("hs_mlp2_forward: activation " + std::to_string(act) +
+                " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
   if (H != 64 && H != 128 && H != 256) return fail("hs_mlp2_forward: need H = 64, 128 or 256");
   if (N < 0 || D < 1 || D > 512 || A < 1 || A > 32 || ld1 < D || ld2 < H || ld3 < H || ldx < D || ldo < A)
     return fail("hs_mlp2_forward: need N >= 0, 1 <= D <= 512, 1 <= A <= 32, ld1 >= D, ld2 >= " + std::to_string(H) +
                 ", ld3 >= " + std::to_string(H) + ", ldx >= D, ldo >= A");
   if (N == 0) return 0;
   if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out) return fail("hs_mlp2_forward: null buffer");
-  return hip_ok(hs::launch_mlp2_fwd(X, ldx, D, N, H, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo,
+  return hip_ok(hs::launch_mlp2_fwd(X, ldx, D, N, H, act, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo,
                                     (hipStream_t)stream),
                 "mlp2_fwd_kernel")
              ? 0
              : -1;
+}
+
+int hs_mlp2_forward_h(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
+                      const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
+                      float* out, int ldo, void* stream) {
+  return hs_mlp2_forward_act(X, ldx, D, N, H, HS_ACT_RELU, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, A, out, ldo, stream);
 }
 
 int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int ld1, const float* b1, const float* W2,
@@ -973,12 +992,22 @@ int hs_mlp2_forward(const float* X, int ldx, int D, int N, const float* W1, int 
 
 uint64_t hs_colsum_partial_rows(uint64_t rows, uint64_t cols) { return hs::colsum_partial_rows(rows, cols); }
 
+int hs_act_grad_colsum(const float* g, const float* y, uint64_t rows, uint64_t cols, int act, float* gm,
+                       float* partial, void* stream) {
+  if (act != HS_ACT_RELU && act != HS_ACT_TANH)
+    return fail("hs_act_grad_colsum: activation " + std::to_string(act) +
+                " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
+  if (!rows || !cols) return 0;
+  if (!g || !y || !gm || !partial) return fail("hs_act_grad_colsum: null buffer");
+  return hip_ok(hs::launch_relu_colsum(g, y, rows, cols, act, gm, partial, (hipStream_t)stream),
+                "relu_colsum_kernel")
+             ? 0
+             : -1;
+}
+
 int hs_relu_grad_colsum(const float* g, const float* y, uint64_t rows, uint64_t cols, float* gm, float* partial,
                         void* stream) {
-  if (!rows || !cols) return 0;
-  if (!g || !y || !gm || !partial) return fail("hs_relu_grad_colsum: null buffer");
-  return hip_ok(hs::launch_relu_colsum(g, y, rows, cols, gm, partial, (hipStream_t)stream), "relu_colsum_kernel") ? 0
-                                                                                                                 : -1;
+  return hs_act_grad_colsum(g, y, rows, cols, HS_ACT_RELU, gm, partial, stream);
 }
 
 uint64_t hs_dgrad_mask_partial_rows(int B, int K) { return hs::dgrad_mask_partial_rows(B, K); }
@@ -986,6 +1015,13 @@ uint64_t hs_dgrad_mask_workspace(int K) { return hs::dgrad_mask_workspace(K); }
 
 int hs_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B, int N,
                   float* GX, float* partial, float* workspace, void* stream) {
+  return hs_dgrad_act(G, ldg, K, W, ldw, X, ldx, B, N, HS_ACT_RELU, GX, partial, workspace, stream);
+}
+
+int hs_dgrad_act(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B, int N,
+                 int act, float* GX, float* partial, float* workspace, void* stream) {
+  if (act != HS_ACT_RELU && act != HS_ACT_TANH)
+    return fail("hs_dgrad_act: activation " + std::to_string(act) + " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
   if (B < 0 || N != 256 || K < 1 || (K > 32 && (K % 16 != 0 || K > 512)) || ldg < K || ldw < N || ldx < N)
     return fail("hs_dgrad_mask: need B >= 0, N == 256, K <= 32 or K % 16 == 0 with K <= 512, ldg >= K, ldw >= N, "
                 "ldx >= N");
@@ -993,7 +1029,7 @@ int hs_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const
   if (!G || !W || !X || !GX || !partial) return fail("hs_dgrad_mask: null buffer");
   if (K > 32 && (((uintptr_t)G & 15) || (ldg & 3))) return fail("hs_dgrad_mask: K > 32 needs 16-byte aligned G rows");
   if (hs::dgrad_mask_workspace(K) && !workspace) return fail("hs_dgrad_mask: workspace required");
-  return hip_ok(hs::launch_dgrad_mask(G, ldg, K, W, ldw, X, ldx, B, N, GX, partial, workspace, (hipStream_t)stream),
+  return hip_ok(hs::launch_dgrad_mask(G, ldg, K, W, ldw, X, ldx, B, N, act, GX, partial, workspace, (hipStream_t)stream),
                 "dgrad_mask kernel")
              ? 0
              : -1;

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "hs_act.h"
 #include "hs_philox.h"
 #include "hs_stepper.h"
 
@@ -241,7 +242,8 @@ __device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int
 
 // Fused rollout: the SB3 MlpPolicy's pi net (mlp_extractor.policy_net + action_net, fp32 as SB3's
 // policy) on the wave's two envs at once (the lower half-wave's env and the upper's; a ghost half
-// mirrors its partner).  Two hidden layers of H = 64 R (R = 1, 2, 4: RolloutArgs::H = 64, 128, 256):
+// mirrors its partner).  Two hidden layers of H = 64 R (R = 1, 2, 4: RolloutArgs::H = 64, 128, 256) with
+// the activation ACT (RolloutArgs::hact: ReLU or Tanh, hs_act.h -- the function of mlp2_fwd_kernel):
 // lane L (of 64) owns outputs R L .. R L + R - 1 for BOTH envs, so each input costs one 4 R-byte weight
 // load per lane (coalesced: the wave reads each weight row once) and two LDS broadcasts (the two envs'
 // inputs).  Every output sums its inputs in ascending index, whatever R.  The head: sub-lane sl < A of
@@ -266,7 +268,7 @@ __device__ __forceinline__ void pol_load(const float* p, float (&u)[R]) {
     u[0] = p[0];
   }
 }
-template <int R, typename T, typename C>
+template <int R, int ACT, typename T, typename C>
 __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   constexpr int H = 64 * R;
   const bool up = lane >= HL;
@@ -304,8 +306,8 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
     WSYNC();   // every lane has read the inputs (the outputs may alias them)
 #pragma unroll
     for (int j = 0; j < R; j++) {
-      outa[R * lane + j] = fmaxf(a[j], 0.f);
-      outb[R * lane + j] = fmaxf(c[j], 0.f);
+      outa[R * lane + j] = hs_act<ACT>(a[j]);
+      outb[R * lane + j] = hs_act<ACT>(c[j]);
     }
     WSYNC();
   };
@@ -320,19 +322,27 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
   }
   return mean;
 }
-// The narrow instances are calls, not inlined: inlined beside the 256 one they cost the rollout kernel
+// The narrow instances are calls, not inlined: inlined beside the 256 ones they cost the rollout kernel
 // registers (4 AGPRs more, profiles/rollout_widths.md), and a call per env step is noise next to the step.
-template <int R, typename T, typename C>
+// The two 256-wide bodies (ReLU and Tanh) are inlined: together they leave every figure of the kernel
+// where it was, and as a call the Tanh one ran the rollout 5 % slower (profiles/tanh_policy.md).
+template <int R, int ACT, typename T, typename C>
 __device__ __noinline__ float policy_mean_call(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  return policy_mean_body<R>(k, obs, smem, lane);
+  return policy_mean_body<R, ACT>(k, obs, smem, lane);
 }
-// one wave-uniform dispatch on the hidden width (hs_rollout admits 64, 128 and 256 only)
+// one wave-uniform dispatch on the hidden width and the activation (hs_rollout_act admits 64, 128 and 256,
+// ReLU and Tanh only)
 template <typename T, typename C>
 __device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   const int H = k->ro.H;
-  if (H == 256) return policy_mean_body<4>(k, obs, smem, lane);
-  if (H == 128) return policy_mean_call<2>(k, obs, smem, lane);
-  return policy_mean_call<1>(k, obs, smem, lane);
+  if (k->ro.hact == ACT_TANH) {
+    if (H == 256) return policy_mean_body<4, ACT_TANH>(k, obs, smem, lane);
+    if (H == 128) return policy_mean_call<2, ACT_TANH>(k, obs, smem, lane);
+    return policy_mean_call<1, ACT_TANH>(k, obs, smem, lane);
+  }
+  if (H == 256) return policy_mean_body<4, ACT_RELU>(k, obs, smem, lane);
+  if (H == 128) return policy_mean_call<2, ACT_RELU>(k, obs, smem, lane);
+  return policy_mean_call<1, ACT_RELU>(k, obs, smem, lane);
 }
 
 template <typename T, int NV, typename C>

@@ -136,7 +136,7 @@ enum Solver { SOLVER_NEWTON = 0, SOLVER_PGS = 1 };
 // noise_qpos/noise_qvel: [N][nq]/[N][nv] host-supplied reset noise (null = device RNG).
 // Fused PPO rollout (hs_rollout, fp64 engine): a tape launch whose actions come from the policy.
 // After each env step the env's wave runs the SB3 MlpPolicy's pi net (2 hidden layers of H = 64, 128
-// or 256, ReLU) on the new obs, draws the action (the Philox stream of ppo_act_kernel) and does the
+// or 256, ReLU or Tanh) on the new obs, draws the action (the Philox stream of ppo_act_kernel) and does the
 // rollout buffer bookkeeping of ppo_post_kernel, so a K-step rollout is one launch.  Rollout buffers
 // are indexed by the global step g = t_begin + t.
 struct RolloutArgs {
@@ -149,6 +149,7 @@ struct RolloutArgs {
   const float* log_std; // [A]
   int ld1, D, A;
   int H;                // hidden width: 64, 128 or 256 (policy_mean dispatches on it)
+  int hact;             // hidden activation: ACT_RELU or ACT_TANH (hs_act.h; policy_mean dispatches on it)
   int t_begin, t_total; // global step of this launch's first step; rollout length (n_steps)
   float* obs;           // [t_total][N][D]: rows g + 1 written (row 0 is the caller's)
   float* obs_last;      // [N][D]: the obs after step t_total - 1 (the next rollout's first obs)
@@ -236,10 +237,11 @@ hipError_t launch_ppo_post(const float* reward, const uint8_t* terminated, const
                            uint8_t* boot_out, int obs_dim, float gamma, const float* obs, float* obs_out,
                            size_t obs_floats, float* reward_out, uint8_t* done_out, double* ep_acc,
                            double* ep_return_out, float* episode_start, int N, hipStream_t stream);
-// fused 2-hidden-layer (H = 64, 128 or 256) ReLU MLP forward of one packed policy net (ppo.hip mlp2_fwd_kernel)
-hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
-                           const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
-                           float* out, int ldo, hipStream_t stream);
+// fused 2-hidden-layer (H = 64, 128 or 256; act = ACT_RELU or ACT_TANH, hs_act.h) MLP forward of one packed
+// policy net (ppo.hip mlp2_fwd_kernel)
+hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
+                           const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
+                           const float* b3, int A, float* out, int ldo, hipStream_t stream);
 // column sums of a row-major [rows][cols] float32 matrix (ppo.hip); workspace of
 // colsum_workspace(rows, cols) floats (0: none needed)
 size_t colsum_workspace(size_t rows, size_t cols);
@@ -264,16 +266,18 @@ int adam_partials(long long total);
 hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
                             float* const* step, const long long* numel, float* part, float max_norm, double lr,
                             double b1, double b2, double eps, hipStream_t stream);
-// ReLU-backward + bias-gradient first pass, and a paired single-pass column sum (ppo.hip)
+// activation-backward (act = ACT_RELU or ACT_TANH) + bias-gradient first pass, and a paired single-pass column
+// sum (ppo.hip)
 size_t colsum_partial_rows(size_t rows, size_t cols);
-// (G W) masked by X > 0 and its per-workgroup column sums (ppo.hip dgrad_mask_*_kernel): the input
-// gradient of a Linear layer fed by a ReLU, fused with that ReLU's backward; N = 256
+// (G W) times act'(X) (X > 0 for ReLU, 1 - X^2 for Tanh) and its per-workgroup column sums (ppo.hip
+// dgrad_mask_*_kernel): the input gradient of a Linear layer fed by an activation, fused with that
+// activation's backward; N = 256
 hipError_t launch_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B,
-                             int N, float* GX, float* partial, float* workspace, hipStream_t stream);
+                             int N, int act, float* GX, float* partial, float* workspace, hipStream_t stream);
 size_t dgrad_mask_partial_rows(int B, int K);
 size_t dgrad_mask_workspace(int K);
-hipError_t launch_relu_colsum(const float* g, const float* y, size_t rows, size_t cols, float* gm, float* partial,
-                              hipStream_t stream);
+hipError_t launch_relu_colsum(const float* g, const float* y, size_t rows, size_t cols, int act, float* gm,
+                              float* partial, hipStream_t stream);
 hipError_t launch_colsum_pair(const float* x0, size_t rows0, size_t cols0, float* out0, const float* x1, size_t rows1,
                               size_t cols1, float* out1, hipStream_t stream);
 // GAE reverse scan over [T][N] float32 rollout arrays (gae.hip)

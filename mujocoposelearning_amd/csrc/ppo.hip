@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "hs_act.h"
 #include "hs_philox.h"
 
 namespace hs {
@@ -450,11 +451,20 @@ __global__ __launch_bounds__(CS_COLS* CS_PHASES) void colsum_kernel(const float*
   }
 }
 
-// ReLU backward fused with the bias gradient's first reduction pass: gm = (y > 0) ? g : 0 is
+// Activation backward fused with the bias gradient's first reduction pass: gm = (y > 0) ? g : 0
+// (ReLU) or g (1 - y^2) (Tanh; y is the activation's output either way, hs_act_grad) is
 // written for the GEMMs that follow, and its per-chunk column sums go to `partial`
 // ([gridDim.y][cols], the same tiling as colsum_kernel), finished by colsum_pair_kernel together
 // with the split-K weight-gradient slices -- one pass over g instead of threshold_backward + a
 // separate colsum read.
+// gm of element i: the ReLU form reads g[i] under the y[i] > 0 select
+template <int ACT>
+__device__ __forceinline__ float act_grad_at(const float* __restrict__ g, const float* __restrict__ y, size_t i) {
+  if constexpr (ACT == ACT_RELU) return y[i] > 0.f ? g[i] : 0.f;
+  else return hs_act_grad<ACT>(g[i], y[i]);
+}
+
+template <int ACT>
 __global__ __launch_bounds__(CS_COLS* CS_PHASES) void relu_colsum_kernel(const float* __restrict__ g,
                                                                           const float* __restrict__ y,
                                                                           size_t rows, size_t cols,
@@ -471,7 +481,7 @@ __global__ __launch_bounds__(CS_COLS* CS_PHASES) void relu_colsum_kernel(const f
     size_t r = r0 + ph;
     for (; r + CS_PHASES < r1; r += 2 * CS_PHASES) {
       const size_t i0 = r * cols + c, i1 = (r + CS_PHASES) * cols + c;
-      const float v0 = y[i0] > 0.f ? g[i0] : 0.f, v1 = y[i1] > 0.f ? g[i1] : 0.f;
+      const float v0 = act_grad_at<ACT>(g, y, i0), v1 = act_grad_at<ACT>(g, y, i1);
       gm[i0] = v0;
       gm[i1] = v1;
       a0 += v0;
@@ -479,7 +489,7 @@ __global__ __launch_bounds__(CS_COLS* CS_PHASES) void relu_colsum_kernel(const f
     }
     for (; r < r1; r += CS_PHASES) {
       const size_t i = r * cols + c;
-      const float v = y[i] > 0.f ? g[i] : 0.f;
+      const float v = act_grad_at<ACT>(g, y, i);
       gm[i] = v;
       a0 += v;
     }
@@ -534,14 +544,14 @@ __global__ __launch_bounds__(CS_COLS* CS_PHASES) void colsum_pair_kernel(const f
 }
 
 // ------------------------------------------------------------------ fused 2-hidden-layer MLP forward
-// out = relu(relu(X W1' + b1) W2' + b2) W3' + b3 for one policy net (PPO rollout: the pi net's mean per
+// out = act(act(X W1' + b1) W2' + b2) W3' + b3 (act = ReLU or Tanh, hs_act.h) for one policy net (PPO rollout: the pi net's mean per
 // env step, the vf net's values once per rollout).  The weights come as nn.Linear stores them,
 // [out][in] row-major (W1 [H][ld1], W2 [H][ld2], W3 [A][ld3]): the reduction index k is
 // contiguous, so one 16-byte load fetches a lane's B operand for four v_mfma_f32_16x16x4_f32 steps.
 // Within each group of 16 k the MFMA steps run over a permuted k (step j of lane group ak takes
 // k = 16 q + 4 ak + j) so that A (from LDS) and B (from global) are both one b128 per lane per
 // group -- the sum over k is the same, only its order differs from the GEMM's.
-// The hidden width H is a template parameter (64, 128 or 256).
+// The hidden width H (64, 128 or 256) and the activation ACT are template parameters.
 // One workgroup per 16 RB rows, H / 32 waves (8 at H = 256): wave w owns output columns
 // [32 w, 32 w + 32) of a hidden layer for all the rows (RB row blocks x 2 column tiles of
 // accumulators).  Its weight rows are read by no other wave, so they stream straight into VGPRs (the MI355X guide's GEMV rule: no LDS round
@@ -623,7 +633,7 @@ __host__ __device__ constexpr size_t mlp_lds_bytes(int RB, int D, int H) {
   return (size_t)16 * RB * (mlp_xs_stride(D, H) + mlp_sh(H)) * 4;
 }
 
-template <bool VEC, int RB, int H>
+template <bool VEC, int RB, int H, int ACT>
 __global__ __launch_bounds__(2 * H) void mlp2_fwd_kernel(const float* __restrict__ X, int ldx, int D, int N,
                                                            const float* __restrict__ W1, int ld1,
                                                            const float* __restrict__ b1,
@@ -667,7 +677,7 @@ __global__ __launch_bounds__(2 * H) void mlp2_fwd_kernel(const float* __restrict
       for (int rb = 0; rb < RB; rb++)
 #pragma unroll
         for (int r = 0; r < 4; r++)
-          dst[(16 * rb + 4 * ak + r) * SH + c0 + 16 * t] = fmaxf(acc[rb][t][r] + bb, 0.f);
+          dst[(16 * rb + 4 * ak + r) * SH + c0 + 16 * t] = hs_act<ACT>(acc[rb][t][r] + bb);
     }
   };
   {   // layer 1: K = D (full groups pipelined, a partial last group with masked loads)
@@ -734,9 +744,10 @@ __global__ __launch_bounds__(2 * H) void mlp2_fwd_kernel(const float* __restrict
   }
 }
 
-// ------------------------------------------------------------------ input gradient + ReLU mask
-// The backward of a Linear layer whose input x is the previous layer's ReLU output:
-//   GX = (G W) ⊙ (X > 0),  partial[wg][n] = sum of GX over the workgroup's rows
+// ------------------------------------------------------------------ input gradient + activation backward
+// The backward of a Linear layer whose input x is the previous layer's activation output:
+//   GX = (G W) ⊙ act'(X),  partial[wg][n] = sum of GX over the workgroup's rows
+// with act' from the activation's output (hs_act_grad): X > 0 for ReLU, 1 - X^2 for Tanh.
 // G [B][K] (ldg) is the layer's output gradient, W [K][N] its nn.Linear weight ([out][in]), X [B][N]
 // (ldx) its input.  The mask is the previous layer's ReLU backward and the partial sums its bias
 // gradient's first pass, so that layer needs no separate pass over [B][N] (autograd writes G W,
@@ -764,7 +775,7 @@ __global__ __launch_bounds__(256) void dg_transpose_kernel(const float* __restri
 // mask, store and column-sum an [R][DG_N] gradient tile held in LDS (row stride st): thread t owns
 // columns 4 (t % 64) .. + 3 of rows t / 64 + TPB / 64 i; the per-thread sums reduce through `red`
 // ([TPB / 64][64] float4, may alias the tile after the barrier)
-template <int R, int TPB, bool XVEC>
+template <int R, int TPB, bool XVEC, int ACT>
 __device__ __forceinline__ void dg_finish(const float* tile, int st, const float* __restrict__ X, int ldx, int B,
                                           int row0, float* __restrict__ GX, float* __restrict__ part, f32x4* red) {
   constexpr int P = TPB / 64;
@@ -783,7 +794,7 @@ __device__ __forceinline__ void dg_finish(const float* tile, int st, const float
     const int row = row0 + rp + P * i;
     f32x4 v;
 #pragma unroll
-    for (int q = 0; q < 4; q++) v[q] = xv[i][q] > 0.f ? gv[i][q] : 0.f;
+    for (int q = 0; q < 4; q++) v[q] = hs_act_grad<ACT>(gv[i][q], xv[i][q]);
     if (row < B) {
       *reinterpret_cast<f32x4*>(GX + (size_t)row * DG_N + 4 * c4) = v;
       cs += v;
@@ -802,7 +813,7 @@ __device__ __forceinline__ void dg_finish(const float* tile, int st, const float
 
 __host__ __device__ constexpr int dg_stride(int K) { return (K > DG_N ? K : DG_N) + 4; }
 
-template <int RB, bool XVEC>
+template <int RB, bool XVEC, int ACT>
 __global__ __launch_bounds__(MLP_TPB) void dgrad_mask_mfma_kernel(const float* __restrict__ G, int ldg, int K,
                                                                   const float* __restrict__ Wt,
                                                                   const float* __restrict__ X, int ldx, int B,
@@ -833,13 +844,13 @@ __global__ __launch_bounds__(MLP_TPB) void dgrad_mask_mfma_kernel(const float* _
 #pragma unroll
       for (int r = 0; r < 4; r++) dg_lds[(16 * rb + 4 * ak + r) * sg + c0 + 16 * t] = acc[rb][t][r];
   __syncthreads();
-  dg_finish<R, MLP_TPB, XVEC>(dg_lds, sg, X, ldx, B, row0, GX, part, reinterpret_cast<f32x4*>(dg_lds));
+  dg_finish<R, MLP_TPB, XVEC, ACT>(dg_lds, sg, X, ldx, B, row0, GX, part, reinterpret_cast<f32x4*>(dg_lds));
 }
 
 // K <= 32: 32 rows per workgroup; the G tile in LDS (each wave's row of it read as a broadcast),
 // W[k][4 c4 .. + 3] one load per k, k outer over the thread's 8 rows
 constexpr int DG_SMALL_K = 32, DG_SMALL_R = 32, DG_SMALL_TPB = 256;
-template <bool XVEC>
+template <bool XVEC, int ACT>
 __global__ __launch_bounds__(DG_SMALL_TPB) void dgrad_mask_small_kernel(const float* __restrict__ G, int ldg, int K,
                                                                         const float* __restrict__ W, int ldw,
                                                                         const float* __restrict__ X, int ldx, int B,
@@ -864,7 +875,7 @@ __global__ __launch_bounds__(DG_SMALL_TPB) void dgrad_mask_small_kernel(const fl
 #pragma unroll
   for (int i = 0; i < RR; i++) tile[(rp + P * i) * 64 + c4] = v[i];
   __syncthreads();
-  dg_finish<DG_SMALL_R, DG_SMALL_TPB, XVEC>(reinterpret_cast<const float*>(tile), DG_N, X, ldx, B, row0, GX, part,
+  dg_finish<DG_SMALL_R, DG_SMALL_TPB, XVEC, ACT>(reinterpret_cast<const float*>(tile), DG_N, X, ldx, B, row0, GX, part,
                                             tile);
 }
 
@@ -1032,14 +1043,19 @@ hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, floa
 
 size_t colsum_partial_rows(size_t rows, size_t cols) { return colsum_chunks(rows, cols); }
 
-hipError_t launch_relu_colsum(const float* g, const float* y, size_t rows, size_t cols, float* gm, float* partial,
-                              hipStream_t stream) {
+hipError_t launch_relu_colsum(const float* g, const float* y, size_t rows, size_t cols, int act, float* gm,
+                              float* partial, hipStream_t stream) {
+  if (act != ACT_RELU && act != ACT_TANH) return hipErrorInvalidValue;
   if (cols == 0 || rows == 0) return hipSuccess;
   const size_t chunks = colsum_chunks(rows, cols);
   const size_t rpc = (rows + chunks - 1) / chunks;
   const unsigned ctiles = (unsigned)((cols + CS_COLS - 1) / CS_COLS);
-  hipLaunchKernelGGL(relu_colsum_kernel, dim3(ctiles, (unsigned)chunks), dim3(CS_COLS, CS_PHASES), 0, stream, g, y,
-                     rows, cols, rpc, gm, partial);
+  if (act == ACT_TANH)
+    hipLaunchKernelGGL(relu_colsum_kernel<ACT_TANH>, dim3(ctiles, (unsigned)chunks), dim3(CS_COLS, CS_PHASES), 0,
+                       stream, g, y, rows, cols, rpc, gm, partial);
+  else
+    hipLaunchKernelGGL(relu_colsum_kernel<ACT_RELU>, dim3(ctiles, (unsigned)chunks), dim3(CS_COLS, CS_PHASES), 0,
+                       stream, g, y, rows, cols, rpc, gm, partial);
   return hipGetLastError();
 }
 
@@ -1054,10 +1070,10 @@ hipError_t launch_colsum_pair(const float* x0, size_t rows0, size_t cols0, float
 }
 
 
-hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, const float* W1, int ld1, const float* b1,
-                           const float* W2, int ld2, const float* b2, const float* W3, int ld3, const float* b3, int A,
-                           float* out, int ldo, hipStream_t stream) {
-  if ((H != 64 && H != 128 && H != 256) || D < 1 || D > MLP_MAXD || A < 1 || A > 32 || N < 0 || ld1 < D || ld2 < H ||
+hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
+                           const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
+                           const float* b3, int A, float* out, int ldo, hipStream_t stream) {
+  if ((act != ACT_RELU && act != ACT_TANH) || (H != 64 && H != 128 && H != 256) || D < 1 || D > MLP_MAXD || A < 1 || A > 32 || N < 0 || ld1 < D || ld2 < H ||
       ld3 < H || ldx < D || ldo < A)
     return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
@@ -1069,24 +1085,29 @@ hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, const f
   const dim3 grid((N + 16 * RB - 1) / (16 * RB));
   const size_t lds = mlp_lds_bytes(RB, D, H);
   // dynamic LDS above 64 KiB needs the per-kernel opt-in (once per instance)
-#define MLP_LAUNCH(V, B, HH)                                                                                      \
+#define MLP_LAUNCH(V, B, HH, AC)                                                                                  \
   do {                                                                                                           \
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp2_fwd_kernel<V, B, HH>), \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,               \
-                                                       (int)mlp_lds_bytes(B, MLP_MAXD, HH));                     \
+    static const hipError_t attr =                                                                               \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp2_fwd_kernel<V, B, HH, AC>),                       \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_lds_bytes(B, MLP_MAXD, HH));    \
     if (attr != hipSuccess) return attr;                                                                         \
-    mlp2_fwd_kernel<V, B, HH><<<grid, 2 * HH, lds, stream>>>(X, ldx, D, N, W1, ld1, b1, W2, ld2, b2, W3, ld3, b3, \
-                                                             A, out, ldo);                                       \
+    mlp2_fwd_kernel<V, B, HH, AC><<<grid, 2 * HH, lds, stream>>>(X, ldx, D, N, W1, ld1, b1, W2, ld2, b2, W3, ld3, \
+                                                                 b3, A, out, ldo);                               \
+  } while (0)
+#define MLP_LAUNCH_A(V, B, HH)                                                         \
+  do {                                                                                \
+    if (act == ACT_TANH) MLP_LAUNCH(V, B, HH, ACT_TANH); else MLP_LAUNCH(V, B, HH, ACT_RELU); \
   } while (0)
 #define MLP_LAUNCH_H(HH)                                                      \
   do {                                                                       \
-    if (vec) { if (RB == 2) MLP_LAUNCH(true, 2, HH); else MLP_LAUNCH(true, 1, HH); }   \
-    else { if (RB == 2) MLP_LAUNCH(false, 2, HH); else MLP_LAUNCH(false, 1, HH); }     \
+    if (vec) { if (RB == 2) MLP_LAUNCH_A(true, 2, HH); else MLP_LAUNCH_A(true, 1, HH); }   \
+    else { if (RB == 2) MLP_LAUNCH_A(false, 2, HH); else MLP_LAUNCH_A(false, 1, HH); }     \
   } while (0)
   if (H == 256) MLP_LAUNCH_H(256);
   else if (H == 128) MLP_LAUNCH_H(128);
   else MLP_LAUNCH_H(64);
 #undef MLP_LAUNCH_H
+#undef MLP_LAUNCH_A
 #undef MLP_LAUNCH
   return hipGetLastError();
 }
@@ -1113,34 +1134,43 @@ size_t dgrad_mask_partial_rows(int B, int K) {
 size_t dgrad_mask_workspace(int K) { return K <= DG_SMALL_K ? 0 : (size_t)DG_N * K; }
 
 hipError_t launch_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B,
-                             int N, float* GX, float* partial, float* workspace, hipStream_t stream) {
-  if (B < 0 || N != DG_N || K < 1 || (K > DG_SMALL_K && (K % 16 != 0 || K > MLP_MAXD)) || ldg < K || ldw < N ||
+                             int N, int act, float* GX, float* partial, float* workspace, hipStream_t stream) {
+  if ((act != ACT_RELU && act != ACT_TANH) || B < 0 || N != DG_N || K < 1 || (K > DG_SMALL_K && (K % 16 != 0 || K > MLP_MAXD)) || ldg < K || ldw < N ||
       ldx < N)
     return hipErrorInvalidValue;
   if (B == 0) return hipSuccess;
   const bool xvec = ((uintptr_t)X & 15) == 0 && (ldx & 3) == 0;
   if (K <= DG_SMALL_K) {
     const bool vec = xvec && ((uintptr_t)W & 15) == 0 && (ldw & 3) == 0;   // X and W rows 16-byte aligned
-    if (vec)
-      hipLaunchKernelGGL(dgrad_mask_small_kernel<true>, dim3((B + DG_SMALL_R - 1) / DG_SMALL_R), dim3(DG_SMALL_TPB), 0,
-                         stream, G, ldg, K, W, ldw, X, ldx, B, GX, partial);
-    else
-      hipLaunchKernelGGL(dgrad_mask_small_kernel<false>, dim3((B + DG_SMALL_R - 1) / DG_SMALL_R), dim3(DG_SMALL_TPB),
-                         0, stream, G, ldg, K, W, ldw, X, ldx, B, GX, partial);
+#define DG_SMALL(V, AC)                                                                                          \
+  hipLaunchKernelGGL((dgrad_mask_small_kernel<V, AC>), dim3((B + DG_SMALL_R - 1) / DG_SMALL_R), dim3(DG_SMALL_TPB), 0, \
+                     stream, G, ldg, K, W, ldw, X, ldx, B, GX, partial)
+    if (act == ACT_TANH) {
+      if (vec) DG_SMALL(true, ACT_TANH);
+      else DG_SMALL(false, ACT_TANH);
+    } else {
+      if (vec) DG_SMALL(true, ACT_RELU);
+      else DG_SMALL(false, ACT_RELU);
+    }
+#undef DG_SMALL
     return hipGetLastError();
   }
   if (((uintptr_t)G & 15) || (ldg & 3) || !workspace) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dg_transpose_kernel, dim3(DG_N / 32, (K + 31) / 32), dim3(256), 0, stream, W, ldw, K, N, workspace);
   const int RB = dg_rb(B);
   const size_t lds = (size_t)16 * RB * dg_stride(K) * 4;
-#define DG_LAUNCH(BB, XV)                                                                                     \
+#define DG_LAUNCH_A(BB, XV, AC)                                                                               \
   do {                                                                                                        \
     static const hipError_t attr =                                                                            \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_mask_mfma_kernel<BB, XV>),                   \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&dgrad_mask_mfma_kernel<BB, XV, AC>),               \
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)16 * BB * dg_stride(MLP_MAXD) * 4)); \
     if (attr != hipSuccess) return attr;                                                                      \
-    dgrad_mask_mfma_kernel<BB, XV><<<dim3((B + 16 * BB - 1) / (16 * BB)), MLP_TPB, lds, stream>>>(            \
+    dgrad_mask_mfma_kernel<BB, XV, AC><<<dim3((B + 16 * BB - 1) / (16 * BB)), MLP_TPB, lds, stream>>>(        \
         G, ldg, K, workspace, X, ldx, B, GX, partial);                                                        \
+  } while (0)
+#define DG_LAUNCH(BB, XV)                                                                    \
+  do {                                                                                       \
+    if (act == ACT_TANH) DG_LAUNCH_A(BB, XV, ACT_TANH); else DG_LAUNCH_A(BB, XV, ACT_RELU);   \
   } while (0)
   if (RB == 4) {
     if (xvec) DG_LAUNCH(4, true);
@@ -1153,6 +1183,7 @@ hipError_t launch_dgrad_mask(const float* G, int ldg, int K, const float* W, int
     else DG_LAUNCH(1, false);
   }
 #undef DG_LAUNCH
+#undef DG_LAUNCH_A
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """On-device PPO (PyTorch-ROCm) restating SB3 2.3.2's PPO/MlpPolicy semantics (the reference's
 trainer, train_sb3.py:208-231) so rollouts never leave HBM.
 
-* ActorCritic: separate pi / vf MLPs (net_arch dict, ReLU -- main.py:16,100), diagonal Gaussian
+* ActorCritic: separate pi / vf MLPs (net_arch dict, ReLU -- main.py:16,100 -- or Tanh), diagonal Gaussian
   with state-independent log_std (init 0), orthogonal init (gain sqrt(2) hidden, 0.01 action
   head, 1 value head) -- SB3 ActorCriticPolicy defaults.
 * Rollout: n_steps x n_envs on device; actions clipped to the action space before stepping
@@ -26,9 +26,10 @@ import torch.nn as nn
 
 
 from . import batch as _batch_mod
+from ._lib import HS_ACT_RELU, HS_ACT_TANH
 from .ppo_ops import (FUSED_WIDTHS, Linear, _GaussLogpFn, _PPOLossFn, _SplitKLinearFn, _SplitKLinearReLUFn,  # noqa: F401
-                      _SPLITK_ROWS, adam_clip_step, colsum, gae_device, mlp2_forward, mlp_forward,
-                      mlp_head_forward, ppo_act, ppo_loss, ppo_post)
+                      _SPLITK_ROWS, adam_clip_step, colsum, gae_device, activation_id, mlp2_forward,
+                      mlp_forward, mlp_head_forward, ppo_act, ppo_loss, ppo_post)
 
 FUSED_MLP = True      # rollout forward through the fused hs_mlp2_forward kernel where it applies
 FUSED_MLP_MAX_ROWS = None   # ... up to this many rows (None: any)
@@ -67,6 +68,7 @@ class ActorCritic(nn.Module):
         self.value_net = Linear(dv, 1)
         self.log_std = nn.Parameter(torch.full((act_dim,), float(log_std_init)))
         self._packed = None      # pack_heads() cache, rebuilt at the start of every rollout
+        self._packed_act = None  # the packed nets' activation (HS_ACT_RELU / HS_ACT_TANH), set with _packed
         for mod, gain in ((self.pi_net, math.sqrt(2)), (self.vf_net, math.sqrt(2)), (self.action_net, 0.01),
                           (self.value_net, 1.0)):
             for m in mod.modules() if isinstance(mod, nn.Sequential) else [mod]:
@@ -118,14 +120,15 @@ class ActorCritic(nn.Module):
         (weights are constant over a rollout, so this runs once per collect_rollouts): layer 1 is
         one [obs_dim x (h_pi + h_vf)] GEMM (both nets read the same obs), deeper layers one
         2-batch GEMM each, and the heads one 2-batch GEMM whose vf half carries the value column
-        in column 0 of an A-wide block.  Needs equal pi/vf widths and ReLU; otherwise None and
-        heads() runs the two nets."""
+        in column 0 of an A-wide block.  Needs equal pi/vf widths and one activation throughout,
+        nn.ReLU or nn.Tanh (recorded in _packed_act); otherwise None and heads() runs the two nets."""
         lp, lv = self._hidden(self.pi_net), self._hidden(self.vf_net)
-        acts = {type(m) for m in list(self.pi_net) + list(self.vf_net) if not isinstance(m, nn.Linear)}
+        act = activation_id([m for m in list(self.pi_net) + list(self.vf_net) if not isinstance(m, nn.Linear)])
         same = len(lp) == len(lv) >= 1 and all(a.weight.shape == b.weight.shape for a, b in zip(lp, lv))
-        if not same or acts != {nn.ReLU}:
-            self._packed = None
+        if not same or act is None:
+            self._packed = self._packed_act = None
             return None
+        self._packed_act = act
         A, H = self.action_net.out_features, lp[-1].out_features
         w1 = torch.cat([lp[0].weight, lv[0].weight]).t().contiguous()
         b1 = torch.cat([lp[0].bias, lv[0].bias])
@@ -146,6 +149,17 @@ class ActorCritic(nn.Module):
         self._packed = new
         return self._packed
 
+    def _act_id(self):
+        """The packed nets' activation (a module packed before the attribute existed: ReLU)."""
+        act = getattr(self, "_packed_act", None)
+        return HS_ACT_RELU if act is None else act
+
+    def _act_addmm(self, b, x, w):
+        """act(x w + b) of the packed chain: ReLU in the GEMM epilogue on a device, Tanh in place."""
+        if self._act_id() == HS_ACT_TANH:
+            return torch.addmm(b, x, w).tanh_()
+        return torch._addmm_activation(b, x, w) if x.is_cuda else torch.addmm(b, x, w).relu_()
+
     @torch.no_grad()
     def heads(self, obs):
         """Rollout forward: (mean [N, A] view, value [N] strided view) from the packed GEMM chain
@@ -158,17 +172,19 @@ class ActorCritic(nn.Module):
             return self.net_forward(obs, 0), self.net_forward(obs, 1)
         w1, b1, mid, w3, b3 = pk
         n = obs.shape[0]
-        # [N, 2H]: layer 1 of both nets, ReLU in the GEMM epilogue on a device
-        h = torch._addmm_activation(b1, obs, w1) if obs.is_cuda else torch.addmm(b1, obs, w1).relu_()
+        # [N, 2H]: layer 1 of both nets, ReLU in the GEMM epilogue on a device (Tanh: in place)
+        tanh = self._act_id() == HS_ACT_TANH
+        h = self._act_addmm(b1, obs, w1)
         h = h.view(n, 2, -1).transpose(0, 1)                      # [2, N, H] (strided)
         for w, b in mid:
-            h = torch.baddbmm(b, h, w).relu_()
+            h = torch.baddbmm(b, h, w)
+            h = h.tanh_() if tanh else h.relu_()
         out = torch.baddbmm(b3, h, w3)                            # [2, N, A]
         return out[0], out[1, :, 0]
 
     def _fused_mlp_ok(self, obs):
-        """The fused hs_mlp2_forward_h kernel applies: packed equal pi / vf nets of two hidden layers of
-        the same width, 64, 128 or 256 (ReLU), <= 512 inputs and <= 32 actions, fp32 rows with unit stride on a device, and at
+        """The fused hs_mlp2_forward_act kernel applies: packed equal pi / vf nets of two hidden layers of
+        the same width, 64, 128 or 256 (ReLU or Tanh: _packed_act), <= 512 inputs and <= 32 actions, fp32 rows with unit stride on a device, and at
         most FUSED_MLP_MAX_ROWS rows (above, the library GEMM chain is faster)."""
         pk = getattr(self, "_packed", None)
         if pk is None or not FUSED_MLP or not obs.is_cuda:
@@ -181,7 +197,8 @@ class ActorCritic(nn.Module):
     @torch.no_grad()
     def net_forward(self, obs, which):
         """One of the two nets on its own from the packed weights (which = 0: pi -> mean [N, A],
-        1: vf -> value [N]); hidden layers with the ReLU in the GEMM epilogue on a device.  The
+        1: vf -> value [N]); hidden layers with the ReLU in the GEMM epilogue on a device (Tanh nets: an
+        in-place tanh after each GEMM).  The
         device rollout samples with the pi net per step and evaluates the vf net once per rollout
         over the whole [T*N] buffer (the policy is fixed during a rollout)."""
         pk = getattr(self, "_packed", None)
@@ -194,10 +211,10 @@ class ActorCritic(nn.Module):
             # nn.Linear weights as they are ([out][in]: the reduction index contiguous)
             net, head = (self.pi_net, self.action_net) if which == 0 else (self.vf_net, self.value_net)
             l1, l2 = self._hidden(net)
-            out = mlp2_forward(obs, l1.weight, l1.bias, l2.weight, l2.bias, head.weight, head.bias)
+            out = mlp2_forward(obs, l1.weight, l1.bias, l2.weight, l2.bias, head.weight, head.bias,
+                               act=self._act_id())
             return out if which == 0 else out[:, 0]
-        act = (lambda b, x, w: torch._addmm_activation(b, x, w)) if obs.is_cuda else (  # noqa: E731
-            lambda b, x, w: torch.addmm(b, x, w).relu_())
+        act = self._act_addmm
         h = act(b1[which * H:(which + 1) * H], obs, w1[:, which * H:(which + 1) * H])
         for w, b in mid:
             h = act(b[which, 0], h, w[which])
@@ -366,10 +383,11 @@ class PPO:
         return gae(b["rew"], b["val"], b["start"], last_v, self.episode_start, self.gamma, self.gae_lambda)
 
     def _fused_rollout_args(self):
-        """(batch handle, hs_policy) when the whole rollout can run as hs_rollout launches -- the env's
-        fp64 engine with the device reward (HumanoidVecEnv.rollout_handle) and a pi net of two ReLU
-        layers of the same width, 64, 128 or 256 (the reference's config.py net_arch is [64, 64], its
-        README.md:44-50 results' [256, 256]) -- else None."""
+        """(batch handle, hs_policy) when the whole rollout can run as hs_rollout_act launches -- the env's
+        fp64 engine with the device reward (HumanoidVecEnv.rollout_handle) and a pi net of two ReLU or
+        two Tanh layers (policy._packed_act, passed beside the struct) of the same width, 64, 128 or 256
+        (the reference's config.py net_arch is [64, 64] with ReLU, its README.md:44-50 results'
+        [256, 256]; Tanh is the default of SB3's MlpPolicy and of PPO here) -- else None."""
         if not FUSED_ROLLOUT or self.device.type != "cuda":
             return None
         handle = self.env.rollout_handle() if hasattr(self.env, "rollout_handle") else None
@@ -391,7 +409,7 @@ class PPO:
         return handle, pol, keep
 
     def _rollout_fused(self):
-        """collect_rollouts as hs_rollout launches: this method samples step 0's action on the first obs
+        """collect_rollouts as hs_rollout_act launches: this method samples step 0's action on the first obs
         (the per-step sampler, as _rollout_body), then each launch runs up to hs_rollout_max_steps env
         steps with the policy forward, sampling and buffer bookkeeping inside the env kernel
         (hs_env_step.h step_pair), each env pair's step t + 1 starting when its own step t is done.
@@ -420,7 +438,8 @@ class PPO:
         t0 = 0
         while t0 < T:
             k = min(L, T - t0)
-            rc = _lib.check(_lib.lib().hs_rollout(handle, C.byref(cpol), C.byref(rb), t0, k, T, stream))
+            rc = _lib.check(_lib.lib().hs_rollout_act(handle, C.byref(cpol), pol._act_id(), C.byref(rb), t0, k, T,
+                                                      stream))
             if rc == 0:                       # (env steps, kernel ms by HIP events) of the last launches
                 ms = C.c_double(0)
                 _lib.check(_lib.lib().hs_last_tape_ms(handle, C.byref(ms)))

@@ -7,14 +7,16 @@ restatement for CPU tensors (toy envs, tests).
   dones, returns, next obs), gae_device (GAE reverse scan)
 * update: _GaussLogpFn (log-prob fwd/bwd), _PPOLossFn / ppo_loss (clipped surrogate + value MSE
   fwd/bwd), _SplitKLinearFn / _SplitKLinearReLUFn / Linear / mlp_forward (split-K weight
-  gradients, ReLU in the GEMM epilogue), _MLPChainFn / mlp_head_forward (a whole net as one node:
-  input gradient + ReLU mask + bias sum fused, hs_dgrad_mask), colsum (deterministic column sums), adam_clip_step
+  gradients, ReLU in the GEMM epilogue or an in-place Tanh), _MLPChainFn / mlp_head_forward (a whole
+  net as one node: input gradient + activation backward + bias sum fused, hs_dgrad_act), colsum (deterministic column sums), adam_clip_step
   (clip_grad_norm_ + Adam on a torch Adam's own state)
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+from ._lib import HS_ACT_RELU, HS_ACT_TANH
 
 _SPLITK_ROWS = 2048      # rows per split-K slice of a weight gradient
 SPLIT_K = True           # module switch (A/B probes)
@@ -165,23 +167,45 @@ def adam_clip_step(opt, params, max_norm, workspace=None):
     return workspace
 
 
-def relu_grad_colsum(g, y):
-    """(g masked by y > 0, per-chunk column sums of it) through hs_relu_grad_colsum."""
+_ACT_OF = {nn.ReLU: HS_ACT_RELU, nn.Tanh: HS_ACT_TANH}
+
+
+def activation_id(mods):
+    """HS_ACT_RELU / HS_ACT_TANH when every module of ``mods`` (at least one) is exactly nn.ReLU or
+    every one exactly nn.Tanh (no subclasses); None otherwise (mixed, another activation)."""
+    kinds = {type(m) for m in mods}
+    if len(kinds) != 1:
+        return None
+    return _ACT_OF.get(kinds.pop())
+
+
+def _act_linear(act, b, h, w):
+    """act(h W^T + b): ReLU in the GEMM's epilogue; Tanh one in-place pass over the GEMM's output
+    (hipBLASLt has no tanh epilogue)."""
+    if act == HS_ACT_TANH:
+        return torch.addmm(b, h, w.t()).tanh_()
+    return torch._addmm_activation(b, h, w.t())
+
+
+def relu_grad_colsum(g, y, act=HS_ACT_RELU):
+    """(g masked by y > 0 -- or, act = HS_ACT_TANH, g (1 - y^2) -- and per-chunk column sums of it)
+    through hs_act_grad_colsum; y is the activation's output."""
     from . import _lib
     assert g.is_contiguous() and y.is_contiguous() and g.shape == y.shape and g.dim() == 2
     rows, cols = g.shape
     L = _lib.lib()
     gm = torch.empty_like(g)
     part = torch.empty(int(L.hs_colsum_partial_rows(rows, cols)), cols, dtype=torch.float32, device=g.device)
-    _lib.check(L.hs_relu_grad_colsum(g.data_ptr(), y.data_ptr(), rows, cols, gm.data_ptr(), part.data_ptr(),
-                                     torch.cuda.current_stream(g.device).cuda_stream))
+    _lib.check(L.hs_act_grad_colsum(g.data_ptr(), y.data_ptr(), rows, cols, int(act), gm.data_ptr(), part.data_ptr(),
+                                    torch.cuda.current_stream(g.device).cuda_stream))
     return gm, part
 
 
-def dgrad_mask(g, w, x):
-    """(g @ w masked by x > 0, per-row-block column sums of it) through hs_dgrad_mask: the input
-    gradient of a Linear layer (weight w [K, 256], output gradient g [B, K]) whose input x [B, 256]
-    is a ReLU output, fused with that ReLU's backward and its bias sum's first pass."""
+def dgrad_mask(g, w, x, act=HS_ACT_RELU):
+    """(g @ w masked by x > 0 -- or, act = HS_ACT_TANH, times 1 - x^2 -- and per-row-block column sums
+    of it) through hs_dgrad_act: the input gradient of a Linear layer (weight w [K, 256], output
+    gradient g [B, K]) whose input x [B, 256] is a ReLU (Tanh) output, fused with that activation's
+    backward and its bias sum's first pass."""
     from . import _lib
     B, K = g.shape
     assert w.shape == (K, 256) and x.shape == (B, 256) and g.stride(1) == 1 and w.stride(1) == 1 and x.stride(1) == 1
@@ -190,9 +214,9 @@ def dgrad_mask(g, w, x):
     part = torch.empty(int(L.hs_dgrad_mask_partial_rows(B, K)), 256, dtype=torch.float32, device=g.device)
     nws = int(L.hs_dgrad_mask_workspace(K))
     ws = torch.empty(nws, dtype=torch.float32, device=g.device) if nws else None
-    _lib.check(L.hs_dgrad_mask(g.data_ptr(), g.stride(0), K, w.data_ptr(), w.stride(0), x.data_ptr(), x.stride(0), B,
-                               256, gx.data_ptr(), part.data_ptr(), None if ws is None else ws.data_ptr(),
-                               torch.cuda.current_stream(g.device).cuda_stream))
+    _lib.check(L.hs_dgrad_act(g.data_ptr(), g.stride(0), K, w.data_ptr(), w.stride(0), x.data_ptr(), x.stride(0), B,
+                              256, int(act), gx.data_ptr(), part.data_ptr(), None if ws is None else ws.data_ptr(),
+                              torch.cuda.current_stream(g.device).cuda_stream))
     return gx, part
 
 
@@ -228,52 +252,55 @@ def colsum(x, row_weight=None):
 
 
 class _SplitKLinearReLUFn(torch.autograd.Function):
-    """relu(x W^T + b) with the ReLU in the GEMM's epilogue (hipBLASLt bias+ReLU through
-    torch._addmm_activation: no separate activation pass over [B, out]); backward masks the
-    upstream gradient with y > 0, then takes _SplitKLinearFn's split-K gradients."""
+    """act(x W^T + b): ReLU in the GEMM's epilogue (hipBLASLt bias+ReLU through
+    torch._addmm_activation: no separate activation pass over [B, out]), Tanh as one in-place pass
+    over the GEMM's output; backward applies the activation's derivative from y to the upstream
+    gradient (y > 0, or 1 - y^2), then takes _SplitKLinearFn's split-K gradients."""
 
     @staticmethod
-    def forward(ctx, x, w, b, s):
-        y = torch._addmm_activation(b, x, w.t())
+    def forward(ctx, x, w, b, s, act=HS_ACT_RELU):
+        y = _act_linear(act, b, x, w)
         ctx.save_for_backward(x, w, y)
-        ctx.s = s
+        ctx.s, ctx.act = s, act
         return y
 
     @staticmethod
     def backward(ctx, g):
         x, w, y = ctx.saved_tensors
         s = ctx.s
-        g, bias_part = relu_grad_colsum(g.contiguous(), y)  # ReLU mask + the bias sum's first pass
+        g, bias_part = relu_grad_colsum(g.contiguous(), y, ctx.act)  # activation backward + the bias sum's first pass
         gx = g @ w if ctx.needs_input_grad[0] else None
         part = torch.bmm(g.view(s, -1, g.shape[1]).transpose(1, 2), x.view(s, -1, x.shape[1]))
         gw, gb = colsum_pair(part.view(s, -1), bias_part)    # both finishes in one launch
-        return gx, gw.view_as(w), gb, None
+        return gx, gw.view_as(w), gb, None, None
 
 
 class _MLPChainFn(torch.autograd.Function):
-    """head(relu(... relu(x W1^T + b1) ...)) for one SB3 MlpPolicy net (mlp_extractor's pi or vf
-    half + action_net / value_net, policies.py, SB3 2.3.2) with hidden widths 256, as one autograd
-    node.  Forward: each hidden layer one GEMM with the ReLU in its epilogue, the head one GEMM.
-    Backward by hand, so that a layer's input gradient, the ReLU mask of the layer below and that
-    layer's bias sum come out of one hs_dgrad_mask pass (autograd would write g @ w, read it back
-    with the ReLU output for the mask and again for the bias sum); weight gradients split-K as
-    _SplitKLinearFn, each layer's weight and bias finishes in one colsum_pair launch."""
+    """head(act(... act(x W1^T + b1) ...)) for one SB3 MlpPolicy net (mlp_extractor's pi or vf
+    half + action_net / value_net, policies.py, SB3 2.3.2) with hidden widths 256 and act = ReLU or
+    Tanh, as one autograd node.  Forward: each hidden layer one GEMM with the ReLU in its epilogue
+    (Tanh: an in-place pass over its output), the head one GEMM.
+    Backward by hand, so that a layer's input gradient, the activation backward of the layer below
+    and that layer's bias sum come out of one hs_dgrad_act pass (autograd would write g @ w, read it
+    back with the activation's output for threshold_backward / tanh_backward and again for the bias
+    sum); weight gradients split-K as _SplitKLinearFn, each layer's weight and bias finishes in one
+    colsum_pair launch."""
 
     @staticmethod
-    def forward(ctx, x, s, *params):
+    def forward(ctx, x, s, act, *params):
         ws, bs = params[0::2], params[1::2]
         ys, h = [], x
         for w, b in zip(ws[:-1], bs[:-1]):
-            h = torch._addmm_activation(b, h, w.t())
+            h = _act_linear(act, b, h, w)
             ys.append(h)
         out = torch.addmm(bs[-1], h, ws[-1].t())
         ctx.save_for_backward(x, *ys, *ws)
-        ctx.s, ctx.nl = s, len(ws)
+        ctx.s, ctx.nl, ctx.act = s, len(ws), act
         return out
 
     @staticmethod
     def backward(ctx, g):
-        s, nl = ctx.s, ctx.nl
+        s, nl, act = ctx.s, ctx.nl, ctx.act
         saved = ctx.saved_tensors
         x, ys, ws = saved[0], saved[1:nl], saved[nl:]
         g = g.contiguous()
@@ -285,7 +312,7 @@ class _MLPChainFn(torch.autograd.Function):
             part = torch.bmm(g.view(s, -1, A).transpose(1, 2), yl.view(s, -1, yl.shape[1]))
             grads[-2] = colsum(part.view(s, -1)).view_as(ws[-1])
         grads[-1] = colsum(g)
-        g, bias_part = dgrad_mask(g, ws[-1], yl)
+        g, bias_part = dgrad_mask(g, ws[-1], yl, act)
         gx = None
         for li in range(nl - 2, -1, -1):
             xin = ys[li - 1] if li else x
@@ -293,27 +320,27 @@ class _MLPChainFn(torch.autograd.Function):
             gw, grads[2 * li + 1] = colsum_pair(part.view(s, -1), bias_part)
             grads[2 * li] = gw.view_as(ws[li])
             if li:
-                g, bias_part = dgrad_mask(g, ws[li], ys[li - 1])
+                g, bias_part = dgrad_mask(g, ws[li], ys[li - 1], act)
             elif ctx.needs_input_grad[0]:
                 gx = g @ ws[0]
-        return (gx, None, *grads)
+        return (gx, None, None, *grads)
 
 
 FUSED_CHAIN = True       # module switch (A/B probes)
 
 
 def mlp_head_forward(seq, head, x):
-    """head(seq(x)) for an MlpPolicy net (seq = [Linear, ReLU] * L, head a Linear); a large device
-    minibatch with hidden widths 256 and a head of <= 32 outputs runs as one _MLPChainFn node, the
-    rest through mlp_forward."""
+    """head(seq(x)) for an MlpPolicy net (seq = [Linear, act] * L with act all nn.ReLU or all nn.Tanh,
+    head a Linear); a large device minibatch with hidden widths 256 and a head of <= 32 outputs runs
+    as one _MLPChainFn node, the rest through mlp_forward."""
     mods = list(seq)
     s = _splitk_rows(x)
     if (FUSED_CHAIN and s and x.dtype == torch.float32 and len(mods) >= 2 and len(mods) % 2 == 0
             and all(isinstance(m, nn.Linear) and m.out_features == 256 for m in mods[0::2])
-            and all(type(m) is nn.ReLU for m in mods[1::2]) and isinstance(head, nn.Linear)
+            and activation_id(mods[1::2]) is not None and isinstance(head, nn.Linear)
             and head.out_features <= 32 and x.stride(1) == 1):
         params = [t for m in mods[0::2] + [head] for t in (m.weight, m.bias)]
-        return _MLPChainFn.apply(x, s, *params)
+        return _MLPChainFn.apply(x, s, activation_id(mods[1::2]), *params)
     return head(mlp_forward(seq, x))
 
 
@@ -337,14 +364,16 @@ class Linear(nn.Linear):
 
 def mlp_forward(seq, x):
     """nn.Sequential forward that runs each (Linear, ReLU) pair of a large device minibatch as one
-    fused GEMM + epilogue (_SplitKLinearReLUFn); everything else module by module."""
+    fused GEMM + epilogue and each (Linear, Tanh) pair as a GEMM + an in-place Tanh with the fused
+    backward (_SplitKLinearReLUFn); everything else module by module."""
     mods = list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
-        if (isinstance(m, Linear) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                and _splitk_rows(x)):
-            x = _SplitKLinearReLUFn.apply(x, m.weight, m.bias, _splitk_rows(x))
+        if (isinstance(m, Linear) and i + 1 < len(mods)
+                and (isinstance(mods[i + 1], nn.ReLU) or type(mods[i + 1]) is nn.Tanh) and _splitk_rows(x)):
+            act = HS_ACT_TANH if type(mods[i + 1]) is nn.Tanh else HS_ACT_RELU
+            x = _SplitKLinearReLUFn.apply(x, m.weight, m.bias, _splitk_rows(x), act)
             i += 2
             continue
         x = m(x)
@@ -355,9 +384,10 @@ def mlp_forward(seq, x):
 FUSED_WIDTHS = (64, 128, 256)   # hidden widths of the fused forwards (hs_mlp2_forward_h, hs_rollout)
 
 
-def mlp2_forward(x, w1, b1, w2, b2, w3, b3):
-    """Fused forward of one 2-hidden-layer ReLU MLP of width H = w1.shape[0] (64, 128 or 256) through
-    hs_mlp2_forward_h (ppo.hip: MFMA tiles, one launch): x [N, D] (row stride >= D); w1 [H, D],
+def mlp2_forward(x, w1, b1, w2, b2, w3, b3, act=HS_ACT_RELU):
+    """Fused forward of one 2-hidden-layer MLP of width H = w1.shape[0] (64, 128 or 256) with hidden
+    activation ``act`` (HS_ACT_RELU or HS_ACT_TANH) through hs_mlp2_forward_act (ppo.hip: MFMA tiles,
+    one launch): x [N, D] (row stride >= D); w1 [H, D],
     w2 [H, H], w3 [A, H] in nn.Linear's [out][in] layout (unit column stride), b1 / b2 [H], b3 [A]
     contiguous; returns out [N, A] float32."""
     from . import _lib
@@ -366,10 +396,10 @@ def mlp2_forward(x, w1, b1, w2, b2, w3, b3):
     assert x.stride(1) == 1 and w1.stride(1) == 1 and w2.stride(1) == 1 and w3.stride(1) == 1
     assert H in FUSED_WIDTHS and w1.shape == (H, D) and w2.shape == (H, H) and w3.shape[1] == H
     out = torch.empty(N, A, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().hs_mlp2_forward_h(x.data_ptr(), x.stride(0), D, N, H, w1.data_ptr(), w1.stride(0),
-                                            b1.data_ptr(), w2.data_ptr(), w2.stride(0), b2.data_ptr(), w3.data_ptr(),
-                                            w3.stride(0), b3.data_ptr(), A, out.data_ptr(), A,
-                                            torch.cuda.current_stream(x.device).cuda_stream))
+    _lib.check(_lib.lib().hs_mlp2_forward_act(x.data_ptr(), x.stride(0), D, N, H, int(act), w1.data_ptr(),
+                                              w1.stride(0), b1.data_ptr(), w2.data_ptr(), w2.stride(0), b2.data_ptr(),
+                                              w3.data_ptr(), w3.stride(0), b3.data_ptr(), A, out.data_ptr(), A,
+                                              torch.cuda.current_stream(x.device).cuda_stream))
     return out
 
 

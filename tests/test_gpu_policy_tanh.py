@@ -1,0 +1,262 @@
+"""Tanh policy nets (SB3's MlpPolicy default, and PPO's here) on the fused rollout-time kernels:
+the shared device tanh (csrc/hs_act.h hs_tanh) through hs_mlp2_forward_act with identity weights,
+mlp2_fwd_kernel<.., ACT_TANH> against the packed GEMM chain, hs_rollout_act's in-kernel policy
+(hs_env_step.h policy_mean_body<R, ACT_TANH>) with the checks of tests/test_gpu_rollout.py, ReLU
+through the new entry point bitwise as through the old, the refusals, and the default-constructed
+trainer.  Every case asserts that it runs the fused path, not the fallback."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_rollout import _check_rollout, _copy_env, _env, _stagger
+
+pytestmark = pytest.mark.gpu
+
+
+def _kw(pi, act="Tanh"):
+    return dict(batch_size=1024, n_epochs=1, seed=0,
+                policy_kwargs={"activation_fn": act, "net_arch": {"pi": list(pi), "vf": list(pi)}})
+
+
+def _identity_forward(x, act):
+    """hs_mlp2_forward_act with H = D = 64, A = 21, W1 = W2 = I, W3 = the first 21 rows of I, zero biases,
+    on rows whose 64 columns all hold x[i]: every MFMA product and sum is exact (one non-zero term per
+    output), so out[i, j] = act(act(x[i]))."""
+    from mujocoposelearning_amd import _lib
+    H, A = 64, 21
+    eye = torch.eye(H, device="cuda")
+    zero = torch.zeros(H, device="cuda")
+    X = x[:, None].expand(-1, H).contiguous()
+    out = torch.full((x.numel(), A), float("nan"), device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().hs_mlp2_forward_act(X.data_ptr(), H, H, x.numel(), H, act, eye.data_ptr(), H, zero.data_ptr(),
+                                              eye.data_ptr(), H, zero.data_ptr(), eye.data_ptr(), H, zero.data_ptr(),
+                                              A, out.data_ptr(), A, st))
+    torch.cuda.synchronize()
+    assert torch.equal(out, out[:, :1].expand(-1, A))      # every column computes the same function
+    return out[:, 0].clone()
+
+
+def test_device_tanh_alone():
+    """hs_tanh through identity weights: finite everywhere (the grid spans both sides of where
+    exp(2|x|) and exp(|x|) overflow), exact at 0, odd bitwise, bounded by tanh(1) rounded up one ulp
+    (the second application sees |t| <= 1), and within 2 * 2^-22 of float64 tanh(tanh(x)) (two
+    applications, the second with slope <= 1).  The same call with HS_ACT_RELU is relu(x) bitwise."""
+    from mujocoposelearning_amd._lib import HS_ACT_RELU, HS_ACT_TANH
+    pos = np.concatenate([[0.0, 1e-30, 1e-6, 1e-3, 20.0, 44.0, 45.0, 89.0, 100.0, 1e4], np.linspace(-12, 12, 4001)])
+    grid = np.unique(np.concatenate([pos, -pos]).astype(np.float32))
+    x = torch.as_tensor(grid, device="cuda")
+    xn = (-x).contiguous()
+    assert 0.0 in grid and grid.size >= 4001 + 18
+    out, outn = _identity_forward(x, HS_ACT_TANH), _identity_forward(xn, HS_ACT_TANH)
+    assert torch.isfinite(out).all() and torch.isfinite(outn).all()
+    assert float(out[x == 0][0]) == 0.0
+    # odd, bitwise: float equality is bit equality for finite non-zero values, and only the sign of a zero
+    # is left out -- the identity product sums x * 1 with 63 x * 0 terms from +0, which loses the sign of -0
+    # before the activation sees it
+    assert torch.equal(outn, -out)
+    nz = out != 0
+    assert torch.equal(outn[nz].view(torch.int32), (-out[nz]).view(torch.int32))
+    bound = np.nextafter(np.float32(math.tanh(1.0)), np.float32(2.0))
+    print(f"max |out| {float(out.abs().max()):.9g}, tanh(1) + 1 ulp {float(bound):.9g}")
+    assert float(out.abs().max()) <= float(bound)
+    ref = torch.tanh(torch.tanh(x.double()))
+    err = float((out.double() - ref).abs().max())
+    print(f"max |hs_tanh(hs_tanh(x)) - tanh(tanh(x))| {err:.3e} = {err * 2 ** 22:.3f} * 2^-22")
+    assert err <= 2 * 2.0 ** -22
+    big = x.abs() >= 20          # saturated: exactly +-tanh-of-one-applied-to +-1, the same value for all
+    assert torch.equal(out[big].abs(), out[big].abs()[:1].expand(int(big.sum())))
+    relu = _identity_forward(x, HS_ACT_RELU)
+    ref_relu = torch.relu(x)
+    assert torch.equal(relu, ref_relu)
+    assert torch.equal(relu[ref_relu != 0].view(torch.int32), ref_relu[ref_relu != 0].view(torch.int32))
+
+
+@pytest.mark.parametrize("H", [64, 128, 256])
+@pytest.mark.parametrize("N,D,scale", [(33, 7, 2.0), (1000, 350, 2.0), (9001, 350, 2.0), (64, 352, 300.0)])
+def test_fused_tanh_forward_matches_gemm_chain(N, D, scale, H):
+    """hs_mlp2_forward_act (Tanh) == the packed GEMM chain of ActorCritic.net_forward (addmm + tanh_) for
+    the pi mean and the vf value at the bar of test_fused_mlp_forward_matches_gemm_chain_at_narrow_widths:
+    no full k-group (7), a partial last group with element loads (350), the two-row-block instance
+    (9001 rows), and a saturating case (obs = 300 randn: layer-1 pre-activations beyond +-100)."""
+    from mujocoposelearning_amd import ppo as P
+    from mujocoposelearning_amd._lib import HS_ACT_TANH
+    torch.manual_seed(0)
+    pol = P.ActorCritic(D, 21, [H, H], [H, H], torch.nn.Tanh).cuda()
+    with torch.no_grad():
+        for p in pol.parameters():
+            p.add_(0.05 * torch.randn_like(p))
+    assert pol.pack_heads() is not None and pol._packed_act == HS_ACT_TANH
+    obs = torch.randn(N, D, device="cuda") * scale
+    if scale > 100:
+        with torch.no_grad():
+            pre = torch.addmm(pol._packed[1], obs, pol._packed[0])
+        assert float(pre.abs().max()) > 100, float(pre.abs().max())
+    assert pol._fused_mlp_ok(obs)
+    outs = {}
+    for fused in (True, False):
+        P.FUSED_MLP = fused
+        try:
+            assert pol._fused_mlp_ok(obs) == fused
+            outs[fused] = [pol.net_forward(obs, 0).clone(), pol.net_forward(obs, 1).clone()]
+        finally:
+            P.FUSED_MLP = True
+    with torch.no_grad():
+        mods = pol(obs)                        # the autograd modules: the chain really is the Tanh net
+    for a, b, m in zip(outs[True], outs[False], mods):
+        assert a.shape == b.shape
+        err = float((a - b).abs().max())
+        print(f"H {H} N {N} D {D}: max |fused - chain| {err:.3e}, max |chain| {float(b.abs().max()):.3e}")
+        assert torch.isfinite(a).all()
+        assert torch.allclose(a, b, rtol=1e-4, atol=1e-4 * (1 + float(b.abs().max()))), err
+        assert torch.allclose(b, m, rtol=1e-4, atol=1e-4 * (1 + float(m.abs().max())))
+
+
+def _pair_path_envs():
+    """The smallest odd batch r + 257 (r = the resident waves, from a 2-env probe batch): more envs
+    than resident waves, so the rollout queues env pairs, and the last pair has a ghost half."""
+    probe = _env(2)
+    r = probe.batch.resident_waves
+    probe.close()
+    assert r > 0
+    return (r + 257) | 1
+
+
+@pytest.mark.parametrize("case", ["tanh_h64_pairs", "tanh_h256_single", "tanh_h128_three_launches"])
+def test_fused_tanh_rollout(case):
+    """Two consecutive fused rollouts of a Tanh policy per case, checked as
+    test_fused_rollout_matches_env_replay_and_policy checks the ReLU [256, 256] net.  tanh_h64_pairs: the
+    pair-per-wave queue with a ghost half; tanh_h256_single: the env-per-wave queue, the R = 4 Tanh
+    body; tanh_h128_three_launches: 0.5 s episodes, hs_rollout_max_steps < T // 2, every env auto-resets."""
+    from mujocoposelearning_amd import _lib
+    from mujocoposelearning_amd.ppo import PPO
+    H, n, T, duration = {"tanh_h64_pairs": (64, None, 12, 10.0),
+                         "tanh_h256_single": (256, 777, 12, 10.0),
+                         "tanh_h128_three_launches": (128, 512, 80, 0.5)}[case]
+    if n is None:
+        n = _pair_path_envs()
+    env, replay = _env(n, duration=duration), _env(n, duration=duration)
+    if case == "tanh_h64_pairs":
+        assert n % 2 == 1 and n > env.batch.resident_waves
+    if case == "tanh_h256_single":
+        assert n <= env.batch.resident_waves
+    ppo = PPO(env, n_steps=T, **_kw([H, H]))
+    assert all(type(m) is torch.nn.Tanh for m in list(ppo.policy.pi_net)[1::2])
+    ppo.policy.pack_heads()
+    args = ppo._fused_rollout_args()
+    assert args is not None and args[1].hidden == H and ppo.policy._packed_act == _lib.HS_ACT_TANH
+    if duration < 1.0:
+        assert _lib.check(_lib.lib().hs_rollout_max_steps(env.rollout_handle())) < T // 2
+    _stagger(env, round(duration / 0.015))
+    for it in range(2):            # the second rollout continues from the first (obs, ep_acc, starts, noise)
+        _copy_env(env, replay)
+        ep_acc0, start0, ctr0 = ppo.ep_acc.clone(), ppo.episode_start.clone(), int(ppo._noise_ctr.item())
+        ppo.collect_rollouts()
+        torch.cuda.synchronize()
+        assert ppo._fused_rollout_args() is not None
+        assert getattr(ppo, "fused_fallbacks", 0) == 0
+        assert len(getattr(ppo, "rollout_launches", [])) > 0
+        assert int(ppo.buf["done"].sum()) > 0                     # episodes ended inside the rollout
+        _check_rollout(ppo, replay, ep_acc0, start0, ctr0)
+    env.close()
+    replay.close()
+
+
+def _rollout_bufs(p):
+    from mujocoposelearning_amd import _lib
+    b = p.buf
+    return _lib.hs_rollout_bufs(b["obs"].data_ptr(), p.obs.data_ptr(), b["act"].data_ptr(), b["logp"].data_ptr(),
+                                b["start"].data_ptr(), b["rew"].data_ptr(), b["done"].data_ptr(), b["epret"].data_ptr(),
+                                b["boot"].data_ptr(), b["tobs"].data_ptr(), p.ep_acc.data_ptr(),
+                                p.episode_start.data_ptr(), p._act_clip.data_ptr(), p._noise_ctr.data_ptr(),
+                                p._noise_seed, 0)
+
+
+def test_relu_through_the_new_entry_point_is_bitwise_the_old():
+    """One [64, 64] ReLU rollout of 64 envs, T = 4, through hs_rollout and one through
+    hs_rollout_act(..., HS_ACT_RELU, ...) from the same env state, buffers and noise counter: obs,
+    actions, log-probs, rewards and dones bitwise equal."""
+    from mujocoposelearning_amd import _lib
+    from mujocoposelearning_amd.ppo import PPO, ppo_act
+    T = 4
+    res = []
+    for entry in ("hs_rollout", "hs_rollout_act"):
+        env = _env(64)
+        _stagger(env)
+        p = PPO(env, n_steps=T, **_kw([64, 64], "ReLU"))
+        p.policy.pack_heads()
+        h, cpol, keep = p._fused_rollout_args()
+        assert p.policy._packed_act == _lib.HS_ACT_RELU
+        b = p.buf
+        b["obs"][0].copy_(p.obs)
+        ppo_act(p.policy.net_forward(b["obs"][0], 0), p._zero_n, p.policy.log_std.detach(), p.episode_start,
+                p._noise_seed, 0, False, b["act"][0], p._act_clip, b["logp"][0], p._val_scratch, b["start"][0],
+                counter_base=p._noise_ctr)
+        rb = _rollout_bufs(p)
+        if entry == "hs_rollout":
+            rc = _lib.lib().hs_rollout(h, C.byref(cpol), C.byref(rb), 0, T, T, None)
+        else:
+            rc = _lib.lib().hs_rollout_act(h, C.byref(cpol), _lib.HS_ACT_RELU, C.byref(rb), 0, T, T, None)
+        assert _lib.check(rc) == 0
+        torch.cuda.synchronize()
+        res.append({k: b[k].clone() for k in ("obs", "act", "logp", "rew", "done")} | {"last": p.obs.clone()})
+        del keep
+        env.close()
+    for k in res[0]:
+        assert torch.equal(res[0][k], res[1][k]), k
+    assert torch.isfinite(res[0]["rew"]).all() and float(res[0]["act"].abs().max()) > 0
+
+
+def test_refusals_and_fallbacks():
+    """hs_rollout_act and hs_mlp2_forward_act raise for an activation outside {0, 1}; a PPO whose nets
+    use nn.ELU is not packed, keeps the per-step path and still collects."""
+    from mujocoposelearning_amd import _lib
+    from mujocoposelearning_amd._lib import HsimError
+    from mujocoposelearning_amd.ppo import PPO
+    env = _env(64)
+    p = PPO(env, n_steps=4, **_kw([64, 64]))
+    p.policy.pack_heads()
+    h, cpol, keep = p._fused_rollout_args()
+    rb = _rollout_bufs(p)
+    with pytest.raises(HsimError, match="activation"):
+        _lib.check(_lib.lib().hs_rollout_act(h, C.byref(cpol), 2, C.byref(rb), 0, 4, 4, None))
+    x = torch.zeros(4, 64, device="cuda")
+    with pytest.raises(HsimError, match="activation"):
+        _lib.check(_lib.lib().hs_mlp2_forward_act(x.data_ptr(), 64, 64, 4, 64, 2, x.data_ptr(), 64, x.data_ptr(),
+                                                  x.data_ptr(), 64, x.data_ptr(), x.data_ptr(), 64, x.data_ptr(), 4,
+                                                  x.data_ptr(), 4, None))
+    env.close()
+    env2 = _env(64)
+    q = PPO(env2, n_steps=4, **_kw([64, 64], "ELU"))
+    assert q.policy.pack_heads() is None
+    assert q._fused_rollout_args() is None
+    assert not q.policy._fused_mlp_ok(q.obs)
+    q.collect_rollouts()
+    torch.cuda.synchronize()
+    assert not getattr(q, "rollout_launches", [])
+    assert torch.isfinite(q.buf["rew"]).all() and torch.isfinite(q.buf["act"]).all()
+    env2.close()
+
+
+def test_default_trainer_collects_fused_and_trains():
+    """PPO(env) with no policy_kwargs -- a Tanh [64, 64] policy, as SB3's MlpPolicy -- collects its
+    rollout as hs_rollout_act launches, and the update changes every parameter."""
+    from mujocoposelearning_amd._lib import HS_ACT_TANH
+    from mujocoposelearning_amd.ppo import PPO
+    env = _env(64)
+    ppo = PPO(env, n_steps=8, batch_size=256, n_epochs=1)
+    assert all(type(m) is torch.nn.Tanh for m in list(ppo.policy.pi_net)[1::2] + list(ppo.policy.vf_net)[1::2])
+    before = {k: v.detach().clone() for k, v in ppo.policy.named_parameters()}
+    adv, ret = ppo.collect_rollouts()
+    torch.cuda.synchronize()
+    assert ppo.policy._packed_act == HS_ACT_TANH and ppo._fused_rollout_args() is not None
+    assert len(getattr(ppo, "rollout_launches", [])) > 0
+    assert getattr(ppo, "fused_fallbacks", 0) == 0
+    ppo.train(adv, ret)
+    torch.cuda.synchronize()
+    for k, v in ppo.policy.named_parameters():
+        assert torch.isfinite(v).all(), k
+        assert not torch.equal(v.detach(), before[k]), k

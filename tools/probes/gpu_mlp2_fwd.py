@@ -1,9 +1,11 @@
 """Timing of the fused policy-MLP forward (ppo.hip mlp2_fwd_kernel) against the torch GEMM chain
-(addmm + ReLU epilogues) at the rollout's two shapes: the pi net per env step (4096 rows) and the
+(addmm + ReLU epilogues; with --activation Tanh, addmm + an in-place tanh) at the rollout's two shapes: the pi net per env step (4096 rows) and the
 vf net over a rollout buffer (32 x 4096 rows).  HIP events on the current stream; FLOP/s counts the
-three layers' 2 N (D H + H H + H A) multiply-adds.   python tools/probes/gpu_mlp2_fwd.py
+three layers' 2 N (D H + H H + H A) multiply-adds.
+    python tools/probes/gpu_mlp2_fwd.py [--activation ReLU|Tanh]
 (profiles/r5i/mlp2_probe_rb{1,2}.log were taken with a build that let HSIM_MLP_RB force the row
 blocks per wave; the launcher now picks them by row count, ppo.hip MLP_RB2_ROWS)"""
+import argparse
 import json
 import os
 import sys
@@ -12,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
+from mujocoposelearning_amd._lib import HS_ACT_RELU, HS_ACT_TANH  # noqa: E402
 from mujocoposelearning_amd.ppo_ops import mlp2_forward  # noqa: E402
 
 
@@ -28,9 +31,10 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
-def main():
+def main(activation):
     torch.manual_seed(0)
     D, H = 352, 256
+    act = HS_ACT_TANH if activation == "Tanh" else HS_ACT_RELU
     out = {}
     for N, A, reps in ((4096, 21, 200), (8192, 21, 100), (16384, 21, 50), (32768, 1, 40), (131072, 1, 20),
                        (131072, 21, 20)):
@@ -41,11 +45,15 @@ def main():
         w1t, w2t, w3t = w1.t().contiguous(), w2.t().contiguous(), w3.t().contiguous()
 
         def fused():
-            return mlp2_forward(x, w1, b1, w2, b2, w3, b3)
+            return mlp2_forward(x, w1, b1, w2, b2, w3, b3, act=act)
 
         def chain():
-            h = torch._addmm_activation(b1, x, w1t)
-            h = torch._addmm_activation(b2, h, w2t)
+            if act == HS_ACT_TANH:
+                h = torch.addmm(b1, x, w1t).tanh_()
+                h = torch.addmm(b2, h, w2t).tanh_()
+            else:
+                h = torch._addmm_activation(b1, x, w1t)
+                h = torch._addmm_activation(b2, h, w2t)
             return torch.addmm(b3, h, w3t)
 
         err = float((fused() - chain()).abs().max())
@@ -53,14 +61,14 @@ def main():
         tf, tc = timed(fused, reps), timed(chain, reps)
         out[f"N{N}_A{A}"] = {"fused_ms": tf, "chain_ms": tc, "fused_tflops": flop / tf / 1e9,
                              "chain_tflops": flop / tc / 1e9, "max_abs_diff": err}
-        print(json.dumps({f"N{N}_A{A}": out[f"N{N}_A{A}"]}), flush=True)
+        print(json.dumps({"activation": activation, f"N{N}_A{A}": out[f"N{N}_A{A}"]}), flush=True)
 
 
-def heads():
+def heads(activation):
     """ActorCritic.heads at 4096 rows: the packed pi+vf GEMM chain against two fused launches."""
     from mujocoposelearning_amd import ppo as P
     torch.manual_seed(0)
-    pol = P.ActorCritic(352, 21, [256, 256], [256, 256], torch.nn.ReLU).cuda()
+    pol = P.ActorCritic(352, 21, [256, 256], [256, 256], getattr(torch.nn, activation)).cuda()
     pol.pack_heads()
     obs = torch.randn(4096, 352, device="cuda")
     res = {}
@@ -72,9 +80,12 @@ def heads():
         P.FUSED_MLP = True
         res["net_forward_fused_ms"] = timed(lambda: (pol.net_forward(obs, 0), pol.net_forward(obs, 1)), 200)
         del chain
-    print(json.dumps({"heads_4096": res}), flush=True)
+    print(json.dumps({"activation": activation, "heads_4096": res}), flush=True)
 
 
 if __name__ == "__main__":
-    heads()
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--activation", choices=("ReLU", "Tanh"), default="ReLU")
+    a = ap.parse_args()
+    heads(a.activation)
+    main(a.activation)
