@@ -19,6 +19,8 @@
  *   hs_rollout(_act)     <- SB3 PPO.collect_rollouts' per-step loop (policy + env step + buffers), one launch;
  *                           pi nets of two layers of 64 (config.py's net_arch), 128 or 256, ReLU (config.py's
  *                           activation_fn) or Tanh (SB3's MlpPolicy default, policies.py)
+ *   hs_evaluate          <- render_policy.py:24-41's predict(deterministic=True) / env.step loop and SB3's
+ *                           evaluate_policy (common/evaluation.py): whole episodes, per-episode results
  *   hs_mlp2_forward(_h, _act) <- ActorCriticPolicy.forward's mlp_extractor + action_net / value_net GEMMs
  *                           of the same nets (policies.py, SB3 2.3.2), one launch per net
  *   hs_physics_step      <- raw `data.ctrl[:] = a; mujoco.mj_step(model, data)` custom_env.py:159-160
@@ -292,6 +294,51 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
 int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
                    int t_total, void* stream);
 int hs_rollout_max_steps(const hs_batch* b);
+
+/* Closed-loop policy evaluation over whole episodes (the fp64 Newton engine): what render_policy.py:24-41
+ * does one env.step at a time (obs -> model.predict(obs, deterministic=True) -> env.step, "make deterministic
+ * (critical)"), train_sb3.py:52-60's VideoRecorderCallback and generate_trajectories.py do the same way, and
+ * SB3's evaluate_policy sums up (common/evaluation.py, 2.3.2: per env the episode's rewards and its length).
+ * The struct must be zero-initialised before its fields are filled in.  Device arrays:
+ *   actions_clipped [N][act_dim] f32, in: step t_begin's clipped action; out: step t_begin + n_steps';
+ *   episode0 [N] u32: the batch's episode counters (hs_buffers.episode) when the evaluation began;
+ *   ep_return [max_episodes][N] f64, ep_length / ep_end_step [max_episodes][N] i32: when env i ends its
+ *     episode number e (counted from episode0[i]) at global step g, slot [e][i] gets the env's own sum of
+ *     rewards (info["total_reward"], custom_env.py:216-224), its step count, and g; e >= max_episodes: nothing;
+ *   trace (n_trace > 0; envs 0 .. n_trace - 1, row [g][env] of each): trace_qpos [t_total][n_trace][nq] and
+ *     trace_qvel [..][nv] in the batch precision -- the state the step's reward was computed from (on a done
+ *     step the terminal state, not the reset one) --, trace_actions [..][act_dim] f32 (the clipped action
+ *     step g ran with), trace_rewards [..] (batch precision), trace_dones [..] u8;
+ *   counter_base (device u64), seed, deterministic: hs_ppo_act's noise, step g draws counter g + *counter_base
+ *     (deterministic != 0: the action is the mean). */
+typedef struct hs_eval_bufs {
+  float* actions_clipped;
+  const uint32_t* episode0;
+  int max_episodes;
+  int n_trace;
+  double* ep_return;
+  int32_t* ep_length;
+  int32_t* ep_end_step;
+  void* trace_qpos;
+  void* trace_qvel;
+  float* trace_actions;
+  void* trace_rewards;
+  uint8_t* trace_dones;
+  const uint64_t* counter_base;
+  uint64_t seed;
+  int deterministic;
+} hs_eval_bufs;
+/* Steps [t_begin, t_begin + n_steps) of an evaluation of t_total steps in ONE launch: hs_step with the
+ * given clipped action for step t_begin, then for every later step the policy forward (hs_policy, `act` as
+ * hs_rollout_act) on the step's obs, the mean or its Gaussian sample, the clip -- on each env's wave, as
+ * hs_rollout_act, but with no rollout buffer: device memory does not grow with the number of steps (the
+ * trace aside; the step's obs is staged in one library-owned [N][obs_dim] f32 row per env).  Same
+ * preconditions and n_steps <= hs_rollout_max_steps(b) as hs_rollout_act.  Returns 0, or 1 when an env
+ * overflowed the resident contact tier: the env state and actions_clipped are restored to the call's start
+ * (result slots and trace rows of steps >= t_begin may hold anything), and the caller runs these steps one
+ * hs_step at a time.  < 0: error (hs_last_error).  Synchronizes; hs_last_tape_ms covers the launch. */
+int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
+                int t_total, void* stream);
 /* Auto-reset noise source of hs_step: [N][nq] / [N][nv] device arrays of the batch precision with
  * the raw U(-noise_scale, noise_scale) draws of the NEXT reset of each env (the kernel applies the
  * x0.1 height factor and zeroes the quaternion part, custom_env.py:109-114); NULL, NULL = the

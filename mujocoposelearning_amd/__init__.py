@@ -31,6 +31,9 @@ def __getattr__(name):
     if name == "train_humanoid":
         from .train import train_humanoid
         return train_humanoid
+    if name in ("evaluate_policy", "evaluate_policy_device", "EvalCallback", "EvalResult", "render_policy"):
+        from . import evaluation
+        return getattr(evaluation, name)
     if name == "HsBatch":
         from .batch import HsBatch
         return HsBatch

@@ -53,6 +53,14 @@ class hs_rollout_bufs(C.Structure):
                [("seed", C.c_uint64), ("deterministic", C.c_int)]
 
 
+class hs_eval_bufs(C.Structure):
+    _fields_ = [("actions_clipped", C.c_void_p), ("episode0", C.c_void_p), ("max_episodes", C.c_int),
+                ("n_trace", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("ep_return", "ep_length", "ep_end_step", "trace_qpos", "trace_qvel",
+                                          "trace_actions", "trace_rewards", "trace_dones", "counter_base")] + \
+               [("seed", C.c_uint64), ("deterministic", C.c_int)]
+
+
 class hs_batch_info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_envs", "precision", "nq", "nv", "nu", "nbody", "obs_dim", "elem_size",
                                        "resident_con", "resident_efc", "wide_con", "wide_efc", "resident_waves",
@@ -98,6 +106,7 @@ def lib():
         "hs_rollout": (i, [vp, vp, vp, i, i, i, vp]),
         "hs_rollout_act": (i, [vp, vp, i, vp, i, i, i, vp]),
         "hs_rollout_max_steps": (i, [vp]),
+        "hs_evaluate": (i, [vp, vp, i, vp, i, i, i, vp]),
         "hs_set_autoreset_noise": (i, [vp, vp, vp]),
         "hs_physics_step": (i, [vp, vp, i, vp]),
         "hs_state_io": (i, [vp, i, vp, vp, vp, vp, vp]),
@@ -148,7 +157,7 @@ def lib():
 
 
 EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create", "hs_batch_destroy",
-            "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_set_autoreset_noise",
+            "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_evaluate", "hs_set_autoreset_noise",
             "hs_physics_step", "hs_state_io", "hs_kinematics", "hs_set_debug", "hs_debug_lose_handoff", "hs_debug_queue_order", "hs_debug_queue_counters", "hs_get_debug", "hs_synchronize", "hs_batch_counters", "hs_gae",
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",
             "hs_ppo_act", "hs_ppo_post", "hs_gauss_logp", "hs_gauss_logp_grad",

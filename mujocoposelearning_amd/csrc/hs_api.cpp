@@ -33,6 +33,7 @@ struct hs_batch {
   int* redo = nullptr;                       // wide-tier work list [2 + n] (kernel-managed)
   unsigned long long* redo_total = nullptr;  // cumulative wide-tier re-runs
   void* mid = nullptr;                       // chunk-queue hand-off rows [n][MIDDIM] (kernel-managed)
+  void* eval_obs = nullptr;                  // hs_evaluate's obs staging rows [n][obs_dim] f32 (uncached; lazily)
   int* qsync = nullptr;                      // chunk queue claim / exit counters, pair flags (qsync_words)
   hs_env_config cfg{};
   bool ctrl_stale = false;                   // env steps ran with HS_OUT_CTRL off: buf.ctrl is not data.ctrl
@@ -194,7 +195,8 @@ hs::StepParams params_of(const hs_batch* b, int mode, int nsub) {
 }
 
 int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const void* nq, const void* nvz, int nsub,
-           void* stream, int nsteps = 1, const hs_tape_out* tape = nullptr, const hs::RolloutArgs* ro = nullptr) {
+           void* stream, int nsteps = 1, const hs_tape_out* tape = nullptr, const hs::RolloutArgs* ro = nullptr,
+           const hs::EvalArgs* ev = nullptr) {
   if (!b) return fail("null batch");
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
@@ -206,7 +208,7 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
     hs::TapeOut<double> to{tape ? (double*)tape->obs : nullptr, tape ? (double*)tape->reward : nullptr,
                            tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
     e = hs::launch_step<double>((const hs::DevModel<double>*)b->dmodel, nv, env_buffers<double>(b), act, mask,
-                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro);
+                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro, ev);
   } else {
     hs::TapeOut<float> to{tape ? (float*)tape->obs : nullptr, tape ? (float*)tape->reward : nullptr,
                           tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
@@ -514,6 +516,7 @@ void hs_batch_destroy(hs_batch* b) {
   if (b->redo_total) (void)hipFree(b->redo_total);
   if (b->mid) uc_release(b->device, (size_t)b->n * hs::MIDDIM * (b->precision == HS_FP64 ? 8 : 4), b->mid);
   if (b->qsync) uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
+  if (b->eval_obs) uc_release(b->device, (size_t)b->n * b->obs_dim * sizeof(float), b->eval_obs);
   if (b->tape_backup) (void)hipFree(b->tape_backup);
   if (b->order_ev) (void)hipEventDestroy(b->order_ev);
   for (auto& e : b->tape_ev)
@@ -684,30 +687,50 @@ int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int
   return hs_rollout_act(b, pol, HS_ACT_RELU, rb, t_begin, n_steps, t_total, stream);
 }
 
-int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
-                   int t_total, void* stream) {
-  if (!b || !pol || !rb) return fail("null argument");
+namespace {
+// what hs_rollout_act and hs_evaluate ask of the batch, the policy and the step range (`who`: the entry
+// point's name in the error text); `hidden` out: the pi net's width
+int fused_policy_check(const hs_batch* b, const hs_policy* pol, int act, int t_begin, int n_steps, int t_total,
+                       const std::string& who, int* hidden_out) {
   const auto& h = b->model->host;
   if (b->precision != HS_FP64 || h.solver == 1)
-    return fail("hs_rollout: the fused rollout runs on the fp64 Newton engine");
+    return fail(who + ": the fused rollout runs on the fp64 Newton engine");
   if (!b->cfg.autoreset || b->ar_qpos_noise || b->cfg.reward_id == HS_REWARD_NONE)
-    return fail("hs_rollout: needs auto-reset with the on-device reset noise and a device reward");
+    return fail(who + ": needs auto-reset with the on-device reset noise and a device reward");
   if (b->cfg.schedule != HS_SCHED_AUTO && b->cfg.schedule != HS_SCHED_FIXED_ORDER)
-    return fail("hs_rollout: needs the chunk-queue schedule (HS_SCHED_AUTO or HS_SCHED_FIXED_ORDER)");
+    return fail(who + ": needs the chunk-queue schedule (HS_SCHED_AUTO or HS_SCHED_FIXED_ORDER)");
   const int hidden = pol->hidden ? pol->hidden : 256;   // 0: a caller from before the field
   if (pol->obs_dim != b->obs_dim || pol->act_dim != h.nu || pol->act_dim > 32 || pol->obs_dim % 4 ||
       pol->obs_dim > 512 || (hidden != 64 && hidden != 128 && hidden != 256) || pol->ld1 < hidden || pol->ld1 % 4)
-    return fail("hs_rollout: policy shape (obs_dim " + std::to_string(pol->obs_dim) + ", act_dim " +
+    return fail(who + ": policy shape (obs_dim " + std::to_string(pol->obs_dim) + ", act_dim " +
                 std::to_string(pol->act_dim) + ", ld1 " + std::to_string(pol->ld1) + ", hidden " +
                 std::to_string(pol->hidden) +
                 ") does not fit the fused forward (obs_dim = the batch's, a multiple of 4 and <= 512; act_dim = nu "
                 "<= 32; two hidden layers of 64, 128 or 256 (hidden = 0: 256); ld1 >= hidden, a multiple of 4)");
   if (act != HS_ACT_RELU && act != HS_ACT_TANH)
-    return fail("hs_rollout: activation " + std::to_string(act) + " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
+    return fail(who + ": activation " + std::to_string(act) + " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
   if (n_steps < 1 || t_begin < 0 || t_begin + n_steps > t_total || n_steps > min_episode_len(b) ||
       n_steps > hs::QTAG_STEPS)
-    return fail("hs_rollout: steps [t_begin, t_begin + n_steps) must lie in [0, t_total) and n_steps in [1, " +
+    return fail(who + ": steps [t_begin, t_begin + n_steps) must lie in [0, t_total) and n_steps in [1, " +
                 std::to_string(std::min(min_episode_len(b), hs::QTAG_STEPS)) + "] (hs_rollout_max_steps)");
+  *hidden_out = hidden;
+  return 0;
+}
+
+hs::RolloutArgs policy_args(const hs_policy* pol, int hidden, int act) {
+  hs::RolloutArgs ro{};
+  ro.w1 = pol->w1; ro.b1 = pol->b1; ro.w2 = pol->w2; ro.b2 = pol->b2; ro.w3 = pol->w3; ro.b3 = pol->b3;
+  ro.log_std = pol->log_std;
+  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden; ro.hact = act;
+  return ro;
+}
+}  // namespace
+
+int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
+                   int t_total, void* stream) {
+  if (!b || !pol || !rb) return fail("null argument");
+  int hidden = 0;
+  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, "hs_rollout", &hidden)) return rc;
   for (const void* q : {(const void*)pol->w1, (const void*)pol->b1, (const void*)pol->w2, (const void*)pol->b2,
                         (const void*)pol->w3, (const void*)pol->b3, (const void*)pol->log_std, (const void*)rb->obs,
                         (const void*)rb->obs_last, (const void*)rb->actions, (const void*)rb->log_probs,
@@ -720,10 +743,7 @@ int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_
   if (order_streams(b, (hipStream_t)stream)) return -1;
   const int resident = hs::resident_waves<double>(false);
   if (resident <= 0 || !b->mid || !b->qsync) return fail("hs_rollout: no resident-wave count / queue buffers");
-  hs::RolloutArgs ro{};
-  ro.w1 = pol->w1; ro.b1 = pol->b1; ro.w2 = pol->w2; ro.b2 = pol->b2; ro.w3 = pol->w3; ro.b3 = pol->b3;
-  ro.log_std = pol->log_std;
-  ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden; ro.hact = act;
+  hs::RolloutArgs ro = policy_args(pol, hidden, act);
   ro.t_begin = t_begin; ro.t_total = t_total;
   ro.obs = rb->obs; ro.obs_last = rb->obs_last; ro.act = rb->actions; ro.logp = rb->log_probs;
   ro.start = rb->episode_starts; ro.rew = rb->rewards; ro.done = rb->dones; ro.epret = rb->episode_returns;
@@ -739,6 +759,55 @@ int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_
   int rc = guarded_tape(b, regs, st, [&] {
     return launch(b, hs::MODE_ENV_STEP, rb->actions_clipped, nullptr, nullptr, nullptr, b->cfg.frame_skip, stream,
                   n_steps, nullptr, &ro);
+  });
+  if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
+  return rc;
+}
+
+int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
+                int t_total, void* stream) {
+  if (!b || !pol || !eb) return fail("null argument");
+  int hidden = 0;
+  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, "hs_evaluate", &hidden)) return rc;
+  for (const void* q : {(const void*)pol->w1, (const void*)pol->b1, (const void*)pol->w2, (const void*)pol->b2,
+                        (const void*)pol->w3, (const void*)pol->b3, (const void*)pol->log_std,
+                        (const void*)eb->actions_clipped, (const void*)eb->episode0, (const void*)eb->ep_return,
+                        (const void*)eb->ep_length, (const void*)eb->ep_end_step, (const void*)eb->counter_base})
+    if (!q) return fail("hs_evaluate: every policy weight, actions_clipped, episode0, the three result arrays and "
+                        "counter_base must be given");
+  if (eb->max_episodes < 1) return fail("hs_evaluate: max_episodes must be >= 1");
+  if (eb->n_trace < 0 || eb->n_trace > b->n)
+    return fail("hs_evaluate: n_trace " + std::to_string(eb->n_trace) + " must lie in [0, n_envs = " +
+                std::to_string(b->n) + "]");
+  if (eb->n_trace > 0 && (!eb->trace_qpos || !eb->trace_qvel || !eb->trace_actions || !eb->trace_rewards ||
+                          !eb->trace_dones))
+    return fail("hs_evaluate: n_trace > 0 needs all five trace arrays");
+  DeviceGuard g(b->device);
+  if (order_streams(b, (hipStream_t)stream)) return -1;
+  const int resident = hs::resident_waves<double>(false);
+  if (resident <= 0 || !b->mid || !b->qsync) return fail("hs_evaluate: no resident-wave count / queue buffers");
+  // the staging rows: one [obs_dim] f32 row per env, rewritten every env step by waves on any XCD, so
+  // uncached memory like the hand-off rows (hs_env_step.h step_pair); allocated at the first evaluation
+  const size_t N = (size_t)b->n;
+  if (!b->eval_obs && !uc_alloc(b->device, N * (size_t)b->obs_dim * sizeof(float), &b->eval_obs)) {
+    b->eval_obs = nullptr;
+    return fail("hipExtMallocWithFlags(eval obs rows, uncached) failed");
+  }
+  hs::RolloutArgs ro = policy_args(pol, hidden, act);
+  ro.t_begin = t_begin; ro.t_total = t_total;
+  ro.obs = (float*)b->eval_obs;
+  ro.act_clip = eb->actions_clipped; ro.ctr_base = eb->counter_base;
+  ro.k0 = (uint32_t)eb->seed; ro.k1 = (uint32_t)(eb->seed >> 32); ro.deterministic = eb->deterministic;
+  hs::EvalArgs ev{};
+  ev.episode0 = eb->episode0; ev.max_episodes = eb->max_episodes; ev.n_trace = eb->n_trace;
+  ev.ep_return = eb->ep_return; ev.ep_length = eb->ep_length; ev.ep_end_step = eb->ep_end_step;
+  ev.tr_qpos = eb->trace_qpos; ev.tr_qvel = eb->trace_qvel; ev.tr_act = eb->trace_actions;
+  ev.tr_rew = eb->trace_rewards; ev.tr_done = eb->trace_dones;
+  std::vector<Region> regs = state_regions(b);
+  regs.push_back({eb->actions_clipped, N * (size_t)pol->act_dim * sizeof(float)});
+  int rc = guarded_tape(b, regs, (hipStream_t)stream, [&] {
+    return launch(b, hs::MODE_ENV_STEP, eb->actions_clipped, nullptr, nullptr, nullptr, b->cfg.frame_skip, stream,
+                  n_steps, nullptr, &ro, &ev);
   });
   if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
   return rc;

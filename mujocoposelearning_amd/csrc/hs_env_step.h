@@ -221,9 +221,15 @@ __device__ __forceinline__ T np_sum_half(T v, int off, int n, int lane) {
 }
 
 // custom_env.py:232-261 layout; qfrc_actuator comes from registers (sub-lane i holds dof i)
-template <typename T, typename C, typename O>
+// UC: the row lies in uncached memory and is rewritten every env step (the fused evaluation's staging
+// row): agent-scope stores, as the hand-off rows (row_st)
+template <bool UC = false, typename T, typename C, typename O>
 __device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int sl, T qfa, O* out,
                           int obs_dim) {
+  auto put = [&](int i, O v) {
+    if constexpr (UC) row_st(out + i, v);
+    else out[i] = v;
+  };
   int nq = m->nq, nv = m->nv;
   int o1 = nq - 2, o2 = o1 + nv, o3 = o2 + 10 * m->nbody, o4 = o3 + 6 * m->nbody;
   for (int k = sl; k < o4; k += HL) {
@@ -232,12 +238,12 @@ __device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int
     else if (k < o2) v = s.qvel[k - o1];
     else if (k < o3) { int q = k - o2; v = s.cinert[q / 10][q % 10]; }
     else { int q = k - o3; v = s.cvel[q / 6][q % 6]; }
-    out[k] = (O)v;
+    put(k, (O)v);
   }
-  if (sl < nv && o4 + sl < obs_dim) out[o4 + sl] = (O)qfa;
+  if (sl < nv && o4 + sl < obs_dim) put(o4 + sl, (O)qfa);
   const int o5 = o4 + nv, nf = 6 * (m->nbody - 1);
   if (obs_dim >= o5 + nf)    // full_state: + cfrc_ext[1:] (custom_env.py:247,255, commented out there)
-    for (int k = sl; k < nf; k += HL) out[o5 + k] = (O)s.u.n.cfrc[1 + k / 6][k % 6];
+    for (int k = sl; k < nf; k += HL) put(o5 + k, (O)s.u.n.cfrc[1 + k / 6][k % 6]);
 }
 
 // Fused rollout: the SB3 MlpPolicy's pi net (mlp_extractor.policy_net + action_net, fp32 as SB3's
@@ -268,7 +274,9 @@ __device__ __forceinline__ void pol_load(const float* p, float (&u)[R]) {
     u[0] = p[0];
   }
 }
-template <int R, int ACT, typename T, typename C>
+// UC: the obs row is the fused evaluation's staging row (uncached memory, rewritten every env step): read
+// at agent scope, as the hand-off rows (row_ld)
+template <int R, int ACT, bool UC = false, typename T, typename C>
 __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   constexpr int H = 64 * R;
   const bool up = lane >= HL;
@@ -279,7 +287,11 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
   float* hb = smem[1].u.pol.h;
   const int D = k->ro.D, A = k->ro.A, ld1 = k->ro.ld1;
   float* xo = up ? xb : xa;
-  for (int i = sl; i < D; i += HL) xo[i] = obs[i];
+  if constexpr (UC) {
+    for (int i = sl; i < D; i += HL) xo[i] = row_ld(obs + i);
+  } else {
+    for (int i = sl; i < D; i += HL) xo[i] = obs[i];
+  }
   WSYNC();
   auto layer = [&](const float* w, int ld, const float* b, const float* ina, const float* inb, int n, float* outa,
                    float* outb) {
@@ -326,23 +338,23 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
 // registers (4 AGPRs more, profiles/rollout_widths.md), and a call per env step is noise next to the step.
 // The two 256-wide bodies (ReLU and Tanh) are inlined: together they leave every figure of the kernel
 // where it was, and as a call the Tanh one ran the rollout 5 % slower (profiles/tanh_policy.md).
-template <int R, int ACT, typename T, typename C>
+template <int R, int ACT, bool UC = false, typename T, typename C>
 __device__ __noinline__ float policy_mean_call(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  return policy_mean_body<R, ACT>(k, obs, smem, lane);
+  return policy_mean_body<R, ACT, UC>(k, obs, smem, lane);
 }
 // one wave-uniform dispatch on the hidden width and the activation (hs_rollout_act admits 64, 128 and 256,
 // ReLU and Tanh only)
-template <typename T, typename C>
+template <bool UC = false, typename T, typename C>
 __device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   const int H = k->ro.H;
   if (k->ro.hact == ACT_TANH) {
-    if (H == 256) return policy_mean_body<4, ACT_TANH>(k, obs, smem, lane);
-    if (H == 128) return policy_mean_call<2, ACT_TANH>(k, obs, smem, lane);
-    return policy_mean_call<1, ACT_TANH>(k, obs, smem, lane);
+    if (H == 256) return policy_mean_body<4, ACT_TANH, UC>(k, obs, smem, lane);
+    if (H == 128) return policy_mean_call<2, ACT_TANH, UC>(k, obs, smem, lane);
+    return policy_mean_call<1, ACT_TANH, UC>(k, obs, smem, lane);
   }
-  if (H == 256) return policy_mean_body<4, ACT_RELU>(k, obs, smem, lane);
-  if (H == 128) return policy_mean_call<2, ACT_RELU>(k, obs, smem, lane);
-  return policy_mean_call<1, ACT_RELU>(k, obs, smem, lane);
+  if (H == 256) return policy_mean_body<4, ACT_RELU, UC>(k, obs, smem, lane);
+  if (H == 128) return policy_mean_call<2, ACT_RELU, UC>(k, obs, smem, lane);
+  return policy_mean_call<1, ACT_RELU, UC>(k, obs, smem, lane);
 }
 
 template <typename T, int NV, typename C>
@@ -444,7 +456,11 @@ __device__ __forceinline__ bool resets_next(KPtr<T> k, MPtr<T> m, T time, int st
 // substeps.
 // ghost: this half-wave mirrors env idx (the single-env schedule's upper half) and commits nothing.
 // HINTS (the chunk queue): *hint = STEP_* bits of this call.
-template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false>
+// EVAL (with ROLL): the fused evaluation (hs_evaluate, EvalArgs) -- the rollout's loop without the
+// RolloutBuffer: the step's obs goes to the env's one staging row (ro.obs, [N][D], uncached), the policy
+// reads it back, the clipped action goes to the pair's next step; a finished episode writes its three
+// result slots, a traced env one trace row.
+template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false, bool EVAL = false>
 __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCache<T, C>* pcache, int idx,
                                           int nidx, const int* list, int s0, int s1, int pair, bool ghost = false,
                                           int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false,
@@ -509,7 +525,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
       total = row_ld(r + MID_TOT);
       if (rollout) {
         if (sl < nu) act_row = row_ld(r + MID_ACT + sl);
-        epacc = (double)row_ld(r + MID_EPACC);
+        if constexpr (!EVAL) epacc = (double)row_ld(r + MID_EPACC);
       }
       // never seen in practice; if it were, the state is poisoned so that the substep's mj_checkPos
       // resets the env (mj_resetData, ctrl 0 for that substep) -- counted in its own slot,
@@ -529,7 +545,8 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
       step_count = ka->b.step_count[env_id];
       episode = ka->b.episode[env_id];
       total = ka->b.total_reward[env_id];
-      if (rollout) epacc = ka->ro.ep_acc[env_id];
+      if constexpr (!EVAL)
+        if (rollout) epacc = ka->ro.ep_acc[env_id];
     }
     // data.ctrl is an input only to a raw physics call that keeps the current ctrl; env steps set
     // it from the action, resets zero it
@@ -679,7 +696,37 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
           // fused rollout: SB3 collect_rollouts' bookkeeping of this step (ppo_post_kernel): reward and
           // done rows, the episode return, TimeLimit.truncated envs' terminal obs for the bootstrap,
           // and the returned obs (an env that auto-resets returns its reset obs, written below)
-          if (rollout && active) {
+          if constexpr (EVAL) {
+            // fused evaluation: no RolloutBuffer rows.  A finished episode's result slots (one address per
+            // episode, written once), a traced env's row of this step (written once), and the step's obs
+            // into the env's staging row for the policy forward below
+            if (rollout && active) {
+              rdone = term || trunc;
+              const int g = k->ro.t_begin + tstep;
+              if (rdone && sl == 0) {
+                const uint32_t e = episode - k->ev.episode0[env];
+                if (e < (uint32_t)k->ev.max_episodes) {
+                  const size_t o = (size_t)e * k->nenv + env;
+                  k->ev.ep_return[o] = (double)total;
+                  k->ev.ep_length[o] = step_count;
+                  k->ev.ep_end_step[o] = g;
+                }
+              }
+              if (env < k->ev.n_trace) {   // the state the reward was computed from (terminal on a done step)
+                const size_t row = (size_t)g * k->ev.n_trace + env;
+                T* tq = (T*)k->ev.tr_qpos + row * nq;
+                if (sl < nq) tq[sl] = s.qpos[sl];
+                if (sl + HL < nq) tq[sl + HL] = s.qpos[sl + HL];
+                if (sl < nv) ((T*)k->ev.tr_qvel)[row * nv + sl] = s.qvel[sl];
+                if (sl < nu) k->ev.tr_act[row * nu + sl] = (float)act;
+                if (sl == 0) {
+                  ((T*)k->ev.tr_rew)[row] = r;
+                  k->ev.tr_done[row] = rdone;
+                }
+              }
+              if (!rdone) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
+            }
+          } else if (rollout && active) {
             const float rf = (float)r;
             const double acc = epacc + (double)rf;
             rdone = term || trunc;
@@ -745,7 +792,9 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
         const int obs_dim = k->p.obs_dim;
         T* orow = obs_row(k, env, obs_dim);
         if (orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
-        if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);   // the reset obs
+        if constexpr (EVAL) {
+          if (rollout) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
+        } else if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);   // the reset obs
         if (!defer(k)) {
           if (tape_final) commit(st.m, k, st, env, time, xws, 0, episode, T(0), warn, k->p.full_state != 0);
           if (tape_handoff) handoff(k, env, time, xws, 0, episode, T(0));
@@ -766,7 +815,34 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
 #endif
     if (st.dbg && active && !in_reset) dump_debug(st, st.dbg);
   }
-  if constexpr (ROLL) {
+  if constexpr (EVAL) {
+    // The policy acts on the step's obs in the env's staging row: step g + 1's action, the mean or the
+    // hs_ppo_act draw of counter g + 1 + *ctr_base, clipped, into the hand-off row (or act_clip after the
+    // launch's last step).  The row is uncached memory, written above with agent-scope stores by this
+    // wave (both halves' rows; a ghost half reads its partner's) and read back at agent scope after the
+    // wait below: no L1 / L2 line of an earlier step of this env, on whatever XCD it ran, can be returned.
+    if (rollout) {
+      KPtr<T> k = opaque(ka);
+      const int g = k->ro.t_begin + tstep, A = k->ro.A;
+      const bool last_of_launch = tstep == k->p.nsteps - 1;
+      T* r = k->b.mid + (size_t)env_id * MIDDIM;
+      if (g + 1 < k->ro.t_total) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
+        const float mean = policy_mean<true>(k, k->ro.obs + (size_t)env_id * k->ro.D, smem, lane);
+        float z = 0.f;
+        if (!k->ro.deterministic && sl < A)
+          z = policy_noise((uint32_t)env_id, (uint32_t)sl, (uint64_t)(g + 1) + *k->ro.ctr_base, k->ro.k0, k->ro.k1);
+        const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
+        const float ac = fminf(fmaxf(mean + __expf(ls) * z, -1.f), 1.f);
+        if (real && sl < A) {
+          if (last_of_launch) k->ro.act_clip[(size_t)env_id * A + sl] = ac;
+          else row_st(r + MID_ACT + sl, (T)ac);
+        }
+      } else if (real && last_of_launch && sl < A) {
+        k->ro.act_clip[(size_t)env_id * A + sl] = (float)act;   // as hs_rollout: the action the last step ran with
+      }
+    }
+  } else if constexpr (ROLL) {
     if (rollout) {   // the policy acts on the step's obs: step g + 1's action, drawn as ppo_act_kernel does
       KPtr<T> k = opaque(ka);
       const int g = k->ro.t_begin + tstep, N = k->nenv, A = k->ro.A;

@@ -168,6 +168,26 @@ struct RolloutArgs {
   uint32_t k0, k1;            // Philox key (the 64-bit seed)
   int deterministic;
 };
+// Fused policy evaluation (hs_evaluate): the rollout's loop -- env step, pi net on the step's obs, the
+// action handed to the pair's next step -- without the RolloutBuffer.  Of RolloutArgs it uses the policy,
+// t_begin / t_total, act_clip, ctr_base / k0 / k1 / deterministic, and ro.obs as ONE [N][D] staging row per
+// env (uncached memory, agent-scope accesses: rewritten every step, read back by the wave that wrote it);
+// every other RolloutArgs pointer is null.  Per finished episode it writes three result slots, and for
+// the envs [0, n_trace) one trace row per env step.  Memory does not grow with the number of steps
+// (the trace aside).  Pointers in the batch's precision are typed by the kernel (fp64 engine only).
+struct EvalArgs {
+  const uint32_t* episode0;   // [N] the batch's episode counters when the evaluation began
+  int max_episodes;           // E: slots e = episode - episode0[env] < E are written
+  int n_trace;                // envs [0, n_trace) are traced (0: none)
+  double* ep_return;          // [E][N] the env's own sum of rewards (info["total_reward"])
+  int* ep_length;             // [E][N] its step count
+  int* ep_end_step;           // [E][N] the global step g the episode ended in
+  void* tr_qpos;              // [t_total][n_trace][nq] state the step's reward was computed from
+  void* tr_qvel;              // [t_total][n_trace][nv]
+  float* tr_act;              // [t_total][n_trace][A] the clipped action step g ran with
+  void* tr_rew;               // [t_total][n_trace]
+  uint8_t* tr_done;           // [t_total][n_trace]
+};
 
 // p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape` (may be null), env
 // steps of one env pair run back to back on the chunk queue with the state handed over through
@@ -176,7 +196,7 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape = nullptr,
-                       const RolloutArgs* ro = nullptr);
+                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr);
 
 // waves of the resident step-kernel instance the current device holds at once (0 if unknown)
 template <typename T>

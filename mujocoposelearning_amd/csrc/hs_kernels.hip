@@ -80,7 +80,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
 // a wave may wait for the first chunk of a wave that has not started; the wait is bounded as ever.)
 // ROLL: the fused-rollout instance (fp64 Newton engine; launch_step picks it for hs_rollout), so the
 // policy forward's code and registers stay out of the per-step kernel
-template <typename T, int NV, bool PGS, bool ROLL = false>
+// EVAL (with ROLL): the fused-evaluation instance (hs_evaluate): the rollout's loop without the RolloutBuffer
+// rows, a kernel of its own so that the rollout instance keeps its code and registers
+template <typename T, int NV, bool PGS, bool ROLL = false, bool EVAL = false>
 __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via kernarg ptr */) {
   const KPtr<T> ka = (KPtr<T>)__builtin_amdgcn_kernarg_segment_ptr();
   // this launch's epoch (its hand-off tags are qtag(epoch, ...)): the epoch only changes after every
@@ -167,8 +169,8 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
     const int wait_tag = tape ? (t > 0 ? qtag(epoch, t - 1, 1) : 0) : (last ? qtag(epoch, 0, 0) : 0);
     const int set_tag = tape ? (t < K - 1 ? qtag(epoch, t, 1) : 0) : (last ? 0 : qtag(epoch, 0, 0));
     int hint;   // (STEP_* bits, wave-uniform)
-    step_pair<T, NV, PGS, Resident<T>, ROLL, true>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair, single && upper,
-                                                   wait_tag, set_tag, t, tape, &hint);
+    step_pair<T, NV, PGS, Resident<T>, ROLL, true, EVAL>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair,
+                                                         single && upper, wait_tag, set_tag, t, tape, &hint);
 #ifdef HS_TIMING
     // per item (indexed as step_pair's q0 stamps): its claim index within its chunk kind, and whether
     // it ran the reset pass
@@ -390,7 +392,7 @@ int resident_waves(bool pgs) {
 // a claim (step_kernel_queue), so every wave of the grid has to be running from the start.  It is
 // below resident_waves() where the queue instance's occupancy is below the direct kernel's (the fp32
 // Newton engine: 1 wave per SIMD against 2).
-template <typename T, bool PGS, bool ROLL>
+template <typename T, bool PGS, bool ROLL, bool EVAL = false>
 int queue_waves() {
   constexpr int MAXDEV = 64;
   static int cache[MAXDEV] = {};   // 0: not yet computed
@@ -400,7 +402,7 @@ int queue_waves() {
   int per_cu = 0, v = -1;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL>, WAVE, 0) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL>, WAVE, 0) == hipSuccess &&
       per_cu > 0)
     v = per_cu * prop.multiProcessorCount;
   cache[dev] = v;
@@ -411,13 +413,17 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape,
-                       const RolloutArgs* ro) {
+                       const RolloutArgs* ro, const EvalArgs* ev) {
   if (nenv <= 0) return hipSuccess;
   if (nv != 27) return hipErrorInvalidValue;
   KArgs<T> args{(MPtr<T>)dmodel, b, actions, reset_mask, noise_qpos, noise_qvel, p, nenv,
-                tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{}};
+                tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{},
+                ev ? *ev : EvalArgs{}};
   // fused rollouts: the fp64 Newton engine
   if (ro && (sizeof(T) != 8 || !ro->obs || p.solver == SOLVER_PGS)) return hipErrorInvalidValue;
+  // fused evaluation: a rollout launch (the policy, ro.obs = the staging rows) with result slots
+  if (ev && (!ro || !ev->episode0 || ev->max_episodes < 1 || ev->n_trace < 0 || ev->n_trace > nenv))
+    return hipErrorInvalidValue;
   if (args.p.nsteps < 1) args.p.nsteps = 1;
   // chunk-queue schedule when the env pairs outnumber the waves the GPU holds at once (the fp64
   // engine: 1 wave per SIMD), for multi-substep calls (HS_SCHED_DIRECT: never)
@@ -488,9 +494,12 @@ hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b
     rc = launch_tiers(std::true_type{});
   } else if (ro) {
     if constexpr (sizeof(T) == 8) {
-      const int held = queue_waves<T, false, true>();
+      const int held = ev ? queue_waves<T, false, true, true>() : queue_waves<T, false, true>();
       if (held <= 0) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true>), queue_grid(held), block, 0, stream, args);
+      if (ev)
+        hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true, true>), queue_grid(held), block, 0, stream, args);
+      else
+        hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true>), queue_grid(held), block, 0, stream, args);
     }
   } else {
     rc = launch_tiers(std::false_type{});
@@ -509,7 +518,7 @@ hipError_t launch_kinematics(const DevModel<T>* dmodel, int nv, const T* qpos, T
 #ifndef HS_ONLY_F64
 template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuffers<float>&, const float*,
                                        const uint8_t*, const float*, const float*, const StepParams&, int,
-                                       hipStream_t, const TapeOut<float>*, const RolloutArgs*);
+                                       hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
 template hipError_t launch_reward_eval<float>(const RewardEvalArgs<float>&, hipStream_t);
@@ -518,7 +527,7 @@ template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 #ifndef HS_ONLY_F32
 template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvBuffers<double>&, const float*,
                                         const uint8_t*, const double*, const double*, const StepParams&, int,
-                                        hipStream_t, const TapeOut<double>*, const RolloutArgs*);
+                                        hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
 template hipError_t launch_reward_eval<double>(const RewardEvalArgs<double>&, hipStream_t);

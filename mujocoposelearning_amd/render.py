@@ -167,6 +167,11 @@ class Renderer:
         pose = batch.kinematics(idx)
         self._scene = (pose, self._camera_pose(self._resolve(camera), batch, idx, pose))
 
+    def update_scene_pose(self, pose, batch, camera=None, env=0):
+        """The scene from a pose (``HsBatch.kinematics(env, qpos=...)``) instead of a data view: frames of
+        a recorded trajectory (evaluation.render_policy).  ``batch`` poses the tracking cameras' qpos0."""
+        self._scene = (pose, self._camera_pose(self._resolve(camera), batch, int(env), pose))
+
     # -- drawing ----------------------------------------------------------------------------
     def render(self):
         if self._scene is None:

@@ -15,7 +15,7 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KNAME = "step_kernel_queue<double, 27, false, true>"
+KNAME = "step_kernel_queue<double, 27, false, true, false>"   # <T, NV, PGS, ROLL, EVAL>: the fused rollout
 
 
 def _rows(src, sub):

@@ -14,7 +14,7 @@ STATS_STEPS = 3
 
 
 def is_step(name):
-    return "step_kernel_queue<double, 27, false, false>" in name
+    return "step_kernel_queue<double, 27, false, false, false>" in name   # <T, NV, PGS, ROLL, EVAL>: the per-step one
 
 
 def load(src, sub, timed):
