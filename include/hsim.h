@@ -49,6 +49,10 @@
  *                           surrogate, value MSE (stable_baselines3 2.3.2 ppo/ppo.py) and its backward
  *   hs_adam_clip         <- torch.nn.utils.clip_grad_norm_(max_grad_norm) + torch.optim.Adam.step of
  *                           SB3 PPO.train (ppo.py: max_grad_norm 0.5, Adam eps 1e-5)
+ *   hs_ppo_loss_ex(_grad_ex), hs_ppo_kl_stop, hs_adam_clip_ex <- the same update with SB3 PPO.train's
+ *                           target_kl early stop, clip_range_vf, per-iteration schedules and logged
+ *                           statistics (approx_kl, clip_fraction, entropy_loss, loss) decided and
+ *                           accumulated on the device, so a captured epoch needs no host check
  *   hs_dgrad_mask, hs_dgrad_act <- the input gradient of each layer fed by an activation (ReLU; ReLU or
  *                           Tanh), fused with that activation's backward (same loss.backward())
  *   hs_relu_grad_colsum, hs_act_grad_colsum, hs_colsum_pair <- the activation backward (threshold_backward /
@@ -514,6 +518,65 @@ uint64_t hs_adam_workspace(uint64_t total_numel);
 int hs_adam_clip(int nt, float* const* params, const float* const* grads, float* const* exp_avg,
                  float* const* exp_avg_sq, float* const* step, const int64_t* numel, float* workspace, float max_norm,
                  double lr, double beta1, double beta2, double eps, void* stream);
+/* SB3 PPO.train's controls on the device (ppo/ppo.py, stable_baselines3 2.3.2): every entry below reads
+ * the per-iteration hyperparameters from a float32 device block hparams[HS_PPO_HP_SIZE] (refreshed by the
+ * host before each train(), so captured graphs follow learning_rate / clip_range schedules), shares the
+ * int32 control words control[2] and accumulates into a float32 stats block of
+ * hs_ppo_stats_size(n_epochs) = HS_PPO_STAT_KL + 2 n_epochs floats that the host zeroes before train()
+ * and reads once after it. */
+enum { HS_PPO_HP_LR = 0,              /* Adam learning rate */
+       HS_PPO_HP_CLIP_RANGE = 1,      /* clip_range */
+       HS_PPO_HP_CLIP_RANGE_VF = 2,   /* clip_range_vf; < 0: no value clipping */
+       HS_PPO_HP_KL_STOP = 3,         /* 1.5 * target_kl; < 0: no early stop */
+       HS_PPO_HP_SIZE = 4 };
+enum { HS_PPO_CTL_STOP = 0,    /* stop word: set by the minibatch whose approx_kl exceeds HS_PPO_HP_KL_STOP */
+       HS_PPO_CTL_EPOCH = 1 }; /* index of the current epoch (set by the host between epochs) */
+enum { HS_PPO_STAT_POLICY_LOSS = 0, HS_PPO_STAT_VALUE_LOSS = 1, HS_PPO_STAT_CLIP_FRACTION = 2, HS_PPO_STAT_ENTROPY = 3,
+       HS_PPO_STAT_LOSS = 4,          /* sums over the minibatches evaluated (count: HS_PPO_STAT_COUNT) */
+       HS_PPO_STAT_LOSS_LAST = 5,     /* the last combined loss */
+       HS_PPO_STAT_COUNT = 6,
+       HS_PPO_STAT_KL_LAST = 7,       /* the last approx_kl a stop decision was taken from */
+       HS_PPO_STAT_EXPLAINED_VARIANCE = 8, HS_PPO_STAT_STD = 9,   /* free for the caller (per iteration) */
+       HS_PPO_STAT_KL = 10 };         /* [e][2]: sum of approx_kl and minibatch count of epoch e */
+uint64_t hs_ppo_stats_size(int n_epochs);
+/* hs_ppo_loss with clip = hparams[CLIP_RANGE] and, when hparams[CLIP_RANGE_VF] = c >= 0, SB3's clipped
+ * value loss mean((returns[idx] - (ov + clamp(values - ov, -c, c)))^2), ov = old_values[idx] (the rollout
+ * buffer's values [M]; read only then).  The same three launches also reduce, in the block order of the
+ * two losses, approx_kl = mean((r - 1) - d), d = log_prob - old_log_prob[idx], r = exp(d) (SB3's
+ * approx_kl_div as it writes it) and clip_fraction = mean(|r - 1| > clip); policy_loss and value_loss are
+ * bitwise hs_ppo_loss's without value clipping.  The final single-wave launch then, unless
+ * control[STOP] is already set (then stats and control are left untouched): adds policy_loss,
+ * value_loss, clip_fraction, the entropy sum_j (1/2 + log sqrt(2 pi) + log_std[j]) (A <= 32) and
+ * loss = policy_loss + vf_coef value_loss - ent_coef entropy to stats (LOSS_LAST = loss, COUNT += 1),
+ * adds approx_kl to stats[KL + 2 e] (and 1 to the count beside it), e = control[EPOCH] clamped to
+ * [0, n_epochs), and sets control[STOP] = 1 when hparams[KL_STOP] >= 0 and approx_kl > hparams[KL_STOP]
+ * (SB3: the tripping minibatch is recorded, it and every later one take no optimizer step).
+ * approx_kl_out != NULL defers that decision: the approx_kl is only written there, for hs_ppo_kl_stop
+ * to decide from the value all-reduced over ranks.  `workspace`: hs_ppo_loss_workspace_ex(B) floats.
+ * hs_ppo_loss_grad_ex is hs_ppo_loss_grad with clip from hparams plus the value-clip derivative
+ * (torch's clamp: the closed interval passes, 0 outside); bitwise hs_ppo_loss_grad without value
+ * clipping.  Asynchronous on `stream`. */
+uint64_t hs_ppo_loss_workspace_ex(int B);
+int hs_ppo_loss_ex(const float* log_prob, const float* values, const int64_t* idx, const float* advantages,
+                   const float* returns, const float* old_log_prob, const float* old_values, int B,
+                   int normalize_advantage, const float* hparams, const float* log_std, int A, float vf_coef,
+                   float ent_coef, float* stats, int n_epochs, int* control, float* approx_kl_out, float* policy_loss,
+                   float* value_loss, float* workspace, void* stream);
+int hs_ppo_loss_grad_ex(const float* log_prob, const float* values, int B, const float* hparams,
+                        const float* workspace, const float* g_pg, const float* g_vf, float* g_log_prob,
+                        float* g_values, void* stream);
+/* The deferred stop decision (one thread): unless control[STOP] is set, records the device scalar
+ * approx_kl (the global minibatch's, e.g. the extra element of the all-reduced gradient bucket) in
+ * stats[KL + 2 e] / KL_LAST and sets control[STOP] when it exceeds hparams[KL_STOP] >= 0. */
+int hs_ppo_kl_stop(const float* approx_kl, const float* hparams, float* stats, int n_epochs, int* control,
+                   void* stream);
+/* hs_adam_clip with lr = hparams[LR] read on the device and a device predicate: when *skip != 0 (the
+ * stop word) no tensor's params, exp_avg, exp_avg_sq or step changes.  With *skip == 0 and the same lr
+ * the results are bitwise hs_adam_clip's. */
+int hs_adam_clip_ex(int nt, float* const* params, const float* const* grads, float* const* exp_avg,
+                    float* const* exp_avg_sq, float* const* step, const int64_t* numel, float* workspace,
+                    float max_norm, const float* hparams, const int* skip, double beta1, double beta2, double eps,
+                    void* stream);
 /* out[c] = sum_r w[r] x[r][c] over a row-major [rows][cols] float32 device matrix (w = row_weight
  * [rows], or 1 when NULL -- the weighted form is a rank-1 weight gradient g'x), in a fixed
  * summation order (deterministic).  `workspace` must hold hs_colsum_workspace(rows, cols) floats

@@ -20,6 +20,12 @@ HS_AUXDIM = 40
 HS_OUT_AUX, HS_OUT_CTRL = 1, 2   # hs_env_config.outputs bits
 HS_SCHED_AUTO, HS_SCHED_DIRECT, HS_SCHED_SINGLE, HS_SCHED_FIXED_ORDER = 0, 1, 2, 3   # hs_env_config.schedule
 HS_ACT_RELU, HS_ACT_TANH = 0, 1   # hidden activation of hs_rollout_act / hs_mlp2_forward_act / hs_dgrad_act
+# hs_ppo_loss_ex / hs_adam_clip_ex: hyperparameter block, control words, stats block (include/hsim.h)
+HS_PPO_HP_LR, HS_PPO_HP_CLIP_RANGE, HS_PPO_HP_CLIP_RANGE_VF, HS_PPO_HP_KL_STOP, HS_PPO_HP_SIZE = 0, 1, 2, 3, 4
+HS_PPO_CTL_STOP, HS_PPO_CTL_EPOCH = 0, 1
+(HS_PPO_STAT_POLICY_LOSS, HS_PPO_STAT_VALUE_LOSS, HS_PPO_STAT_CLIP_FRACTION, HS_PPO_STAT_ENTROPY, HS_PPO_STAT_LOSS,
+ HS_PPO_STAT_LOSS_LAST, HS_PPO_STAT_COUNT, HS_PPO_STAT_KL_LAST, HS_PPO_STAT_EXPLAINED_VARIANCE, HS_PPO_STAT_STD,
+ HS_PPO_STAT_KL) = range(11)
 DBGDIM = 32768
 
 
@@ -132,6 +138,14 @@ def lib():
         "hs_adam_workspace": (u64, [u64]),
         "hs_adam_clip": (i, [i, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_double, C.c_double, C.c_double, C.c_double,
                              vp]),
+        "hs_ppo_stats_size": (u64, [i]),
+        "hs_ppo_loss_workspace_ex": (u64, [i]),
+        "hs_ppo_loss_ex": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, i, C.c_float, C.c_float, vp, i, vp, vp, vp, vp,
+                               vp, vp]),
+        "hs_ppo_loss_grad_ex": (i, [vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "hs_ppo_kl_stop": (i, [vp, vp, vp, i, vp, vp]),
+        "hs_adam_clip_ex": (i, [i, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, C.c_double, C.c_double, C.c_double,
+                                vp]),
         "hs_mlp2_forward": (i, [vp, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
         "hs_mlp2_forward_h": (i, [vp, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
         "hs_mlp2_forward_act": (i, [vp, i, i, i, i, i, vp, i, vp, vp, i, vp, vp, i, vp, i, vp, i, vp]),
@@ -162,6 +176,8 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",
             "hs_ppo_act", "hs_ppo_post", "hs_gauss_logp", "hs_gauss_logp_grad",
             "hs_ppo_loss_workspace", "hs_ppo_loss", "hs_ppo_loss_grad", "hs_adam_workspace", "hs_adam_clip",
+            "hs_ppo_stats_size", "hs_ppo_loss_workspace_ex", "hs_ppo_loss_ex", "hs_ppo_loss_grad_ex", "hs_ppo_kl_stop",
+            "hs_adam_clip_ex",
             "hs_mlp2_forward", "hs_mlp2_forward_h", "hs_mlp2_forward_act", "hs_colsum_partial_rows", "hs_relu_grad_colsum",
             "hs_act_grad_colsum", "hs_dgrad_mask_partial_rows",
             "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_dgrad_act", "hs_colsum_pair",

@@ -1028,6 +1028,86 @@ int hs_adam_clip(int nt, float* const* params, const float* const* grads, float*
              : -1;
 }
 
+static_assert(HS_PPO_HP_LR == hs::HP_LR && HS_PPO_HP_CLIP_RANGE == hs::HP_CLIP && HS_PPO_HP_CLIP_RANGE_VF == hs::HP_CLIP_VF &&
+                  HS_PPO_HP_KL_STOP == hs::HP_KL_STOP && HS_PPO_HP_SIZE == 4,
+              "hyperparameter block layout");
+static_assert(HS_PPO_CTL_STOP == hs::CTL_STOP && HS_PPO_CTL_EPOCH == hs::CTL_EPOCH, "control words");
+static_assert(HS_PPO_STAT_POLICY_LOSS == hs::ST_PG && HS_PPO_STAT_VALUE_LOSS == hs::ST_VF &&
+                  HS_PPO_STAT_CLIP_FRACTION == hs::ST_CLIPFRAC && HS_PPO_STAT_ENTROPY == hs::ST_ENT &&
+                  HS_PPO_STAT_LOSS == hs::ST_LOSS && HS_PPO_STAT_LOSS_LAST == hs::ST_LOSS_LAST &&
+                  HS_PPO_STAT_COUNT == hs::ST_COUNT && HS_PPO_STAT_KL_LAST == hs::ST_KL_LAST &&
+                  HS_PPO_STAT_EXPLAINED_VARIANCE == hs::ST_EXPL_VAR && HS_PPO_STAT_STD == hs::ST_STD &&
+                  HS_PPO_STAT_KL == hs::ST_KL,
+              "stats block layout");
+
+uint64_t hs_ppo_stats_size(int n_epochs) { return (uint64_t)HS_PPO_STAT_KL + 2 * (uint64_t)(n_epochs > 0 ? n_epochs : 0); }
+
+uint64_t hs_ppo_loss_workspace_ex(int B) { return B > 0 ? hs::ppo_loss_workspace_ex(B) : 0; }
+
+int hs_ppo_loss_ex(const float* log_prob, const float* values, const int64_t* idx, const float* advantages,
+                   const float* returns, const float* old_log_prob, const float* old_values, int B,
+                   int normalize_advantage, const float* hparams, const float* log_std, int A, float vf_coef,
+                   float ent_coef, float* stats, int n_epochs, int* control, float* approx_kl_out, float* policy_loss,
+                   float* value_loss, float* workspace, void* stream) {
+  if (B < 0) return fail("hs_ppo_loss_ex: negative size");
+  if (A < 0 || A > 32 || n_epochs < 1) return fail("hs_ppo_loss_ex: need 0 <= A <= 32 and n_epochs >= 1");
+  if (B == 0) return 0;
+  if (!log_prob || !values || !idx || !advantages || !returns || !old_log_prob || !old_values || !hparams ||
+      (A > 0 && !log_std) || !stats || !control || !policy_loss || !value_loss || !workspace)
+    return fail("hs_ppo_loss_ex: null buffer");
+  const hs::PpoLossEx x{hparams, log_std, A, vf_coef, ent_coef, stats, n_epochs, control, approx_kl_out};
+  return hip_ok(hs::launch_ppo_loss_fwd_ex(log_prob, values, idx, advantages, returns, old_log_prob, old_values, B,
+                                           normalize_advantage, x, policy_loss, value_loss, workspace,
+                                           (hipStream_t)stream),
+                "ppo loss kernels (ex)")
+             ? 0
+             : -1;
+}
+
+int hs_ppo_loss_grad_ex(const float* log_prob, const float* values, int B, const float* hparams,
+                        const float* workspace, const float* g_pg, const float* g_vf, float* g_log_prob,
+                        float* g_values, void* stream) {
+  if (B < 0) return fail("hs_ppo_loss_grad_ex: negative size");
+  if (B == 0) return 0;
+  if (!log_prob || !values || !hparams || !workspace || !g_pg || !g_vf || !g_log_prob || !g_values)
+    return fail("hs_ppo_loss_grad_ex: null buffer");
+  return hip_ok(hs::launch_ppo_loss_bwd_ex(log_prob, values, B, hparams, workspace, g_pg, g_vf, g_log_prob, g_values,
+                                           (hipStream_t)stream),
+                "ppo_loss_bwd_kernel (ex)")
+             ? 0
+             : -1;
+}
+
+int hs_ppo_kl_stop(const float* approx_kl, const float* hparams, float* stats, int n_epochs, int* control,
+                   void* stream) {
+  if (n_epochs < 1) return fail("hs_ppo_kl_stop: need n_epochs >= 1");
+  if (!approx_kl || !hparams || !stats || !control) return fail("hs_ppo_kl_stop: null buffer");
+  return hip_ok(hs::launch_ppo_kl_stop(approx_kl, hparams, stats, n_epochs, control, (hipStream_t)stream),
+                "kl_stop_kernel")
+             ? 0
+             : -1;
+}
+
+int hs_adam_clip_ex(int nt, float* const* params, const float* const* grads, float* const* exp_avg,
+                    float* const* exp_avg_sq, float* const* step, const int64_t* numel, float* workspace,
+                    float max_norm, const float* hparams, const int* skip, double beta1, double beta2, double eps,
+                    void* stream) {
+  if (nt < 1 || nt > 1024) return fail("hs_adam_clip_ex: need 1 <= nt <= 1024 tensors");
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !numel || !workspace || !hparams || !skip)
+    return fail("hs_adam_clip_ex: null argument");
+  std::vector<long long> n(nt);
+  for (int t = 0; t < nt; t++) {
+    if (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || !step[t] || numel[t] < 0)
+      return fail("hs_adam_clip_ex: null tensor or negative size");
+    n[t] = (long long)numel[t];
+  }
+  return hip_ok(hs::launch_adam_clip(nt, params, grads, exp_avg, exp_avg_sq, step, n.data(), workspace, max_norm, 0.0,
+                                     beta1, beta2, eps, (hipStream_t)stream, hparams, skip),
+                "adam kernels (ex)")
+             ? 0
+             : -1;
+}
+
 int hs_mlp2_forward_act(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
                         const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
                         const float* b3, int A, float* out, int ldo, void* stream) {

@@ -281,11 +281,39 @@ hipError_t launch_ppo_loss_fwd(const float* logp, const float* v, const int64_t*
                                float* vf, float* ws, hipStream_t stream);
 hipError_t launch_ppo_loss_bwd(const float* logp, const float* v, int B, float clip, const float* ws,
                                const float* g_pg, const float* g_vf, float* g_logp, float* g_v, hipStream_t stream);
-// clip_grad_norm_ + Adam over up to 1024 tensors (ppo.hip); part: adam_partials(total numel) floats
+// The same with SB3's train controls on the device (hs_ppo_loss_ex, include/hsim.h): the float32
+// hyperparameter block hp[HP_*], the control words ctl[CTL_*] and the stats block stats[ST_*]
+// (== HS_PPO_HP_* / HS_PPO_CTL_* / HS_PPO_STAT_* of the header, static_assert in hs_api.cpp)
+constexpr int HP_LR = 0, HP_CLIP = 1, HP_CLIP_VF = 2, HP_KL_STOP = 3;
+constexpr int CTL_STOP = 0, CTL_EPOCH = 1;
+constexpr int ST_PG = 0, ST_VF = 1, ST_CLIPFRAC = 2, ST_ENT = 3, ST_LOSS = 4, ST_LOSS_LAST = 5, ST_COUNT = 6,
+              ST_KL_LAST = 7, ST_EXPL_VAR = 8, ST_STD = 9, ST_KL = 10;
+struct PpoLossEx {
+  const float* hp;        // [4] device hyperparameters
+  const float* log_std;   // [A] (entropy of the state-independent Gaussian)
+  int A;
+  float vf_coef, ent_coef;
+  float* stats;           // [ST_KL + 2 n_epochs]
+  int n_epochs;
+  int* ctl;               // [2]
+  float* kl_out;          // NULL, or where the minibatch's approx_kl goes when the decision is deferred
+};
+size_t ppo_loss_workspace_ex(int B);
+hipError_t launch_ppo_loss_fwd_ex(const float* logp, const float* v, const int64_t* idx, const float* adv,
+                                  const float* ret, const float* old_logp, const float* old_v, int B, int normalize,
+                                  const PpoLossEx& x, float* pg, float* vf, float* ws, hipStream_t stream);
+hipError_t launch_ppo_loss_bwd_ex(const float* logp, const float* v, int B, const float* hp, const float* ws,
+                                  const float* g_pg, const float* g_vf, float* g_logp, float* g_v,
+                                  hipStream_t stream);
+hipError_t launch_ppo_kl_stop(const float* kl, const float* hp, float* stats, int n_epochs, int* ctl,
+                              hipStream_t stream);
+// clip_grad_norm_ + Adam over up to 1024 tensors (ppo.hip); part: adam_partials(total numel) floats.
+// hp / skip non-NULL: lr = hp[HP_LR] (device), and nothing is written when *skip != 0
 int adam_partials(long long total);
 hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
                             float* const* step, const long long* numel, float* part, float max_norm, double lr,
-                            double b1, double b2, double eps, hipStream_t stream);
+                            double b1, double b2, double eps, hipStream_t stream, const float* hp = nullptr,
+                            const int* skip = nullptr);
 // activation-backward (act = ACT_RELU or ACT_TANH) + bias-gradient first pass, and a paired single-pass column
 // sum (ppo.hip)
 size_t colsum_partial_rows(size_t rows, size_t cols);

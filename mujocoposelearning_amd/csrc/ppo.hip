@@ -33,6 +33,7 @@
 #include <cstdlib>
 
 #include "hs_act.h"
+#include "hs_kernels.h"
 #include "hs_philox.h"
 
 namespace hs {
@@ -180,6 +181,16 @@ __global__ __launch_bounds__(256) void gauss_logp_grad_kernel(const float* __res
 // writes the two scalars.  Workspace: 3 B + 4 blocks floats + 2 stats.
 constexpr int LOSS_TPB = 256;
 
+// The _ex forms (hs_ppo_loss_ex, include/hsim.h) read clip_range / clip_range_vf from the device
+// hyperparameter block `hp` (HP_*), gather the rollout values when value clipping is on
+//   v_c = old_v + clamp(v - old_v, -clip_vf, clip_vf),  vf = mean((ret - v_c)^2),
+//   dvf/dv_i = 2 (v_c - ret_i) / B inside the closed interval, 0 outside (torch's clamp)
+// and reduce, in the same block order as pg and vf, the sums of (r - 1) - d (SB3's approx_kl,
+// d = logp - old_logp) and of [|r - 1| > clip] (its clip_fraction): one more gathered array and
+// two more partials per block (workspace 4 B + 6 blocks + 2).  EX = false is hs_ppo_loss unchanged.
+template <bool EX> __host__ __device__ constexpr int loss_ng() { return EX ? 4 : 3; }   // gathered arrays
+template <bool EX> __host__ __device__ constexpr int loss_ps() { return EX ? 6 : 4; }   // partials per block
+
 __device__ inline float block_sum256(float v, float* red) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -189,17 +200,21 @@ __device__ inline float block_sum256(float v, float* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+template <bool EX>
 __global__ __launch_bounds__(LOSS_TPB) void loss_gather_kernel(const int64_t* __restrict__ idx,
                                                                const float* __restrict__ adv,
                                                                const float* __restrict__ ret,
-                                                               const float* __restrict__ old_logp, int B,
+                                                               const float* __restrict__ old_logp,
+                                                               const float* __restrict__ old_v,
+                                                               const float* __restrict__ hp, int B,
                                                                float* __restrict__ ws) {
   __shared__ float red[LOSS_TPB / 64];
+  constexpr int PS = loss_ps<EX>();
   const int i = blockIdx.x * LOSS_TPB + threadIdx.x;
   float* a_g = ws;
   float* old_g = ws + B;
   float* ret_g = ws + 2 * (size_t)B;
-  float* part = ws + 3 * (size_t)B;            // [blocks][4]: sum d, sum d^2, sum pg, sum vf
+  float* part = ws + loss_ng<EX>() * (size_t)B;   // [blocks][PS]: sum d, sum d^2, sum pg, sum vf (, sum kl, clipped)
   const float a0 = adv[idx[0]];
   float d = 0.f;
   if (i < B) {
@@ -208,31 +223,35 @@ __global__ __launch_bounds__(LOSS_TPB) void loss_gather_kernel(const int64_t* __
     a_g[i] = a;
     old_g[i] = old_logp[j];
     ret_g[i] = ret[j];
+    if constexpr (EX)
+      if (hp[HP_CLIP_VF] >= 0.f) ws[3 * (size_t)B + i] = old_v[j];
     d = a - a0;
   }
   const float s1 = block_sum256(d, red);
   const float s2 = block_sum256(d * d, red);
   if (threadIdx.x == 0) {
-    part[4 * blockIdx.x + 0] = s1;
-    part[4 * blockIdx.x + 1] = s2;
+    part[PS * blockIdx.x + 0] = s1;
+    part[PS * blockIdx.x + 1] = s2;
   }
 }
 
-// sum over blocks of part[4 k + c], by one full wave (lane-strided, then a fixed xor tree: the
+// sum over blocks of part[PS k + c], by one full wave (lane-strided, then a fixed xor tree: the
 // same order in every block and every run)
+template <int PS = 4>
 __device__ inline float wave_part_sum(const float* part, int nblk, int c) {
   const int l = threadIdx.x & 63;
   float t = 0.f;
-  for (int k = l; k < nblk; k += 64) t += part[4 * k + c];
+  for (int k = l; k < nblk; k += 64) t += part[PS * k + c];
   for (int o = 32; o >= 1; o >>= 1) t += __shfl_xor(t, o);
   return t;
 }
 
 // mean and 1 / (std + 1e-8) from the per-block shifted sums (called by a whole wave)
 // (norm == 0: SB3's normalize_advantage=False -- mean 0, scale 1)
+template <bool EX>
 __device__ inline void loss_stats(const float* ws, int B, int nblk, float a0, int norm, float& mean, float& inv) {
-  const float* part = ws + 3 * (size_t)B;
-  const float s1 = wave_part_sum(part, nblk, 0), s2 = wave_part_sum(part, nblk, 1);
+  const float* part = ws + loss_ng<EX>() * (size_t)B;
+  const float s1 = wave_part_sum<loss_ps<EX>()>(part, nblk, 0), s2 = wave_part_sum<loss_ps<EX>()>(part, nblk, 1);
   if (B > 1 && norm) {
     mean = a0 + s1 / (float)B;
     float var = (s2 - s1 * s1 / (float)B) / (float)(B - 1);
@@ -243,39 +262,63 @@ __device__ inline void loss_stats(const float* ws, int B, int nblk, float a0, in
   }
 }
 
+template <bool EX>
 __global__ __launch_bounds__(LOSS_TPB) void loss_terms_kernel(const float* __restrict__ logp,
-                                                              const float* __restrict__ v, int B, float clip,
-                                                              int norm, float* __restrict__ ws, int nblk) {
+                                                              const float* __restrict__ v, int B, float clip_arg,
+                                                              const float* __restrict__ hp, int norm,
+                                                              float* __restrict__ ws, int nblk) {
   __shared__ float red[LOSS_TPB / 64];
   __shared__ float st[2];
+  constexpr int PS = loss_ps<EX>();
   const float* a_g = ws;
   const float* old_g = ws + B;
   const float* ret_g = ws + 2 * (size_t)B;
-  float* part = ws + 3 * (size_t)B;
+  float* part = ws + loss_ng<EX>() * (size_t)B;
   if (threadIdx.x < 64) {
     float mu, iv;
-    loss_stats(ws, B, nblk, a_g[0], norm, mu, iv);
+    loss_stats<EX>(ws, B, nblk, a_g[0], norm, mu, iv);
     if (threadIdx.x == 0) { st[0] = mu; st[1] = iv; }
   }
   __syncthreads();
   const float mean = st[0], inv = st[1];
+  float clip = clip_arg;
+  if constexpr (EX) clip = hp[HP_CLIP];
   const int i = blockIdx.x * LOSS_TPB + threadIdx.x;
-  float pg = 0.f, vf = 0.f;
+  float pg = 0.f, vf = 0.f, kl = 0.f, cnt = 0.f;
   if (i < B) {
     const float an = (a_g[i] - mean) * inv;
-    const float r = expf(logp[i] - old_g[i]);
+    const float d = logp[i] - old_g[i];
+    const float r = expf(d);
     const float rc = fminf(fmaxf(r, 1.f - clip), 1.f + clip);
     pg = fminf(an * r, an * rc);
-    const float e = ret_g[i] - v[i];
+    float vp = v[i];
+    if constexpr (EX) {
+      kl = (r - 1.f) - d;
+      cnt = fabsf(r - 1.f) > clip ? 1.f : 0.f;
+      const float cv = hp[HP_CLIP_VF];
+      if (cv >= 0.f) {
+        const float ov = ws[3 * (size_t)B + i];
+        vp = ov + fminf(fmaxf(vp - ov, -cv), cv);
+      }
+    }
+    const float e = ret_g[i] - vp;
     vf = e * e;
   }
   pg = block_sum256(pg, red);
   vf = block_sum256(vf, red);
+  if constexpr (EX) {
+    kl = block_sum256(kl, red);
+    cnt = block_sum256(cnt, red);    // whole numbers <= 256 per block, < 2^24 in all: exact
+  }
   if (threadIdx.x == 0) {
-    part[4 * blockIdx.x + 2] = pg;
-    part[4 * blockIdx.x + 3] = vf;
+    part[PS * blockIdx.x + 2] = pg;
+    part[PS * blockIdx.x + 3] = vf;
+    if constexpr (EX) {
+      part[PS * blockIdx.x + 4] = kl;
+      part[PS * blockIdx.x + 5] = cnt;
+    }
     if (blockIdx.x == 0) {                    // stats for the backward
-      float* stats = part + 4 * nblk;
+      float* stats = part + PS * nblk;
       stats[0] = mean;
       stats[1] = inv;
     }
@@ -291,8 +334,60 @@ __global__ void loss_final_kernel(const float* __restrict__ ws, int B, int nblk,
   vf_out[0] = vf / (float)B;
 }
 
+// SB3's `if target_kl is not None and approx_kl_div > 1.5 * target_kl: break`, on the device: the
+// minibatch's approx_kl goes into the slot of the current epoch (ctl[CTL_EPOCH], bumped by the host
+// between epochs) and, above the threshold hp[HP_KL_STOP] (< 0: no target_kl), sets the stop word
+// ctl[CTL_STOP], which hs_adam_clip_ex and every later loss_final_ex read.  One thread.
+__device__ inline void kl_decide(float akl, const float* hp, float* stats, int n_epochs, int* ctl) {
+  int e = ctl[CTL_EPOCH];
+  e = e < 0 ? 0 : (e >= n_epochs ? n_epochs - 1 : e);
+  stats[ST_KL + 2 * e] += akl;
+  stats[ST_KL + 2 * e + 1] += 1.f;
+  stats[ST_KL_LAST] = akl;
+  const float thr = hp[HP_KL_STOP];
+  if (thr >= 0.f && akl > thr) ctl[CTL_STOP] = 1;
+}
+
+// one wave: the two loss scalars and, unless an earlier minibatch of this train() set the stop
+// word, this minibatch's SB3 train statistics added to the stats block (ST_*; the tripping
+// minibatch is recorded, SB3 appends before it checks).  kl_out != NULL: the approx_kl is only
+// written there (world > 1: the decision is hs_ppo_kl_stop's, from the all-reduced value).
+__global__ void loss_final_ex_kernel(const float* __restrict__ ws, int B, int nblk, PpoLossEx x,
+                                     float* __restrict__ pg_out, float* __restrict__ vf_out) {
+  const float* part = ws + 4 * (size_t)B;
+  const float pg = wave_part_sum<6>(part, nblk, 2), vf = wave_part_sum<6>(part, nblk, 3);
+  const float kl = wave_part_sum<6>(part, nblk, 4), cnt = wave_part_sum<6>(part, nblk, 5);
+  // DiagGaussian entropy sum_j (1/2 + log(sqrt(2 pi)) + log_std[j]), A <= 32
+  float ent = (int)threadIdx.x < x.A ? 1.41893853320467274f + x.log_std[threadIdx.x] : 0.f;
+  for (int o = 32; o >= 1; o >>= 1) ent += __shfl_xor(ent, o);
+  if (threadIdx.x != 0) return;
+  const float pgv = -pg / (float)B, vfv = vf / (float)B, akl = kl / (float)B;
+  pg_out[0] = pgv;
+  vf_out[0] = vfv;
+  if (x.kl_out) x.kl_out[0] = akl;
+  if (x.ctl[CTL_STOP] != 0) return;
+  const float loss = pgv + x.vf_coef * vfv - x.ent_coef * ent;
+  float* st = x.stats;
+  st[ST_PG] += pgv;
+  st[ST_VF] += vfv;
+  st[ST_CLIPFRAC] += cnt / (float)B;
+  st[ST_ENT] += ent;
+  st[ST_LOSS] += loss;
+  st[ST_LOSS_LAST] = loss;
+  st[ST_COUNT] += 1.f;
+  if (!x.kl_out) kl_decide(akl, x.hp, st, x.n_epochs, x.ctl);
+}
+
+__global__ void kl_stop_kernel(const float* __restrict__ kl, const float* __restrict__ hp, float* __restrict__ stats,
+                               int n_epochs, int* __restrict__ ctl) {
+  if (threadIdx.x != 0 || ctl[CTL_STOP] != 0) return;
+  kl_decide(kl[0], hp, stats, n_epochs, ctl);
+}
+
+template <bool EX>
 __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restrict__ logp,
-                                                           const float* __restrict__ v, int B, float clip,
+                                                           const float* __restrict__ v, int B, float clip_arg,
+                                                           const float* __restrict__ hp,
                                                            const float* __restrict__ ws, int nblk,
                                                            const float* __restrict__ g_pg,
                                                            const float* __restrict__ g_vf,
@@ -302,7 +397,9 @@ __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restri
   const float* a_g = ws;
   const float* old_g = ws + B;
   const float* ret_g = ws + 2 * (size_t)B;
-  const float* stats = ws + 3 * (size_t)B + 4 * nblk;
+  const float* stats = ws + loss_ng<EX>() * (size_t)B + loss_ps<EX>() * nblk;
+  float clip = clip_arg;
+  if constexpr (EX) clip = hp[HP_CLIP];
   const float an = (a_g[i] - stats[0]) * stats[1];
   const float r = expf(logp[i] - old_g[i]);
   const float lo = 1.f - clip, hi = 1.f + clip;
@@ -311,6 +408,16 @@ __global__ __launch_bounds__(256) void ppo_loss_bwd_kernel(const float* __restri
   const float d1 = an, d2 = (r >= lo && r <= hi) ? an : 0.f;
   const float dmin = s1 < s2 ? d1 : (s1 > s2 ? d2 : 0.5f * (d1 + d2));
   g_logp[i] = g_pg[0] * (-1.f / (float)B) * dmin * r;
+  if constexpr (EX) {
+    const float cv = hp[HP_CLIP_VF];
+    if (cv >= 0.f) {
+      const float ov = ws[3 * (size_t)B + i];
+      const float dv = v[i] - ov;
+      const float vp = ov + fminf(fmaxf(dv, -cv), cv);
+      g_v[i] = (dv >= -cv && dv <= cv) ? g_vf[0] * 2.f * (vp - ret_g[i]) / (float)B : 0.f;
+      return;
+    }
+  }
   g_v[i] = g_vf[0] * 2.f * (v[i] - ret_g[i]) / (float)B;
 }
 
@@ -361,10 +468,16 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_sqsum_kernel(AdamArgs a, float*
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// hp / skip (hs_adam_clip_ex; both NULL in hs_adam_clip): lr = hp[HP_LR] from the device block, and
+// *skip != 0 (the stop word of the KL early stop) leaves p, m, v and step as they are
 __global__ __launch_bounds__(ADAM_TPB) void adam_update_kernel(AdamArgs a, const float* __restrict__ part, int nblk,
                                                                float max_norm, float lr, float b1, float b2,
-                                                               float omb1, float omb2, float eps) {
+                                                               float omb1, float omb2, float eps,
+                                                               const float* __restrict__ hp,
+                                                               const int* __restrict__ skip) {
   __shared__ float coef_s;
+  if (skip && *skip != 0) return;   // the whole grid alike: nothing writes the word meanwhile
+  if (hp) lr = hp[HP_LR];
   if (threadIdx.x < 64) {
     float t = 0.f;
     for (int k = threadIdx.x; k < nblk; k += 64) t += part[k];
@@ -391,7 +504,8 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_update_kernel(AdamArgs a, const
   }
 }
 
-__global__ void adam_step_kernel(AdamArgs a) {
+__global__ void adam_step_kernel(AdamArgs a, const int* __restrict__ skip) {
+  if (skip && *skip != 0) return;
   const float step = a.step[0][0] + 1.f;
   __syncthreads();
   if ((int)threadIdx.x < a.nt) a.step[threadIdx.x][0] = step;
@@ -975,14 +1089,20 @@ size_t ppo_loss_workspace(int B) {
   return 3 * (size_t)B + 4 * nblk + 2;
 }
 
+size_t ppo_loss_workspace_ex(int B) {
+  const size_t nblk = B > 0 ? ((size_t)B + LOSS_TPB - 1) / LOSS_TPB : 0;
+  return 4 * (size_t)B + 6 * nblk + 2;
+}
+
 hipError_t launch_ppo_loss_fwd(const float* logp, const float* v, const int64_t* idx, const float* adv,
                                const float* ret, const float* old_logp, int B, float clip, int normalize, float* pg,
                                float* vf, float* ws, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
   const int nblk = (B + LOSS_TPB - 1) / LOSS_TPB;
-  hipLaunchKernelGGL(loss_gather_kernel, dim3(nblk), dim3(LOSS_TPB), 0, stream, idx, adv, ret, old_logp, B, ws);
-  hipLaunchKernelGGL(loss_terms_kernel, dim3(nblk), dim3(LOSS_TPB), 0, stream, logp, v, B, clip, normalize, ws,
-                     nblk);
+  hipLaunchKernelGGL(loss_gather_kernel<false>, dim3(nblk), dim3(LOSS_TPB), 0, stream, idx, adv, ret, old_logp,
+                     (const float*)nullptr, (const float*)nullptr, B, ws);
+  hipLaunchKernelGGL(loss_terms_kernel<false>, dim3(nblk), dim3(LOSS_TPB), 0, stream, logp, v, B, clip,
+                     (const float*)nullptr, normalize, ws, nblk);
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)ws, B, nblk, pg, vf);
   return hipGetLastError();
 }
@@ -991,8 +1111,39 @@ hipError_t launch_ppo_loss_bwd(const float* logp, const float* v, int B, float c
                                const float* g_pg, const float* g_vf, float* g_logp, float* g_v, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
   const int nblk = (B + LOSS_TPB - 1) / LOSS_TPB;
-  hipLaunchKernelGGL(ppo_loss_bwd_kernel, dim3(nblk), dim3(256), 0, stream, logp, v, B, clip, ws, nblk, g_pg, g_vf,
-                     g_logp, g_v);
+  hipLaunchKernelGGL(ppo_loss_bwd_kernel<false>, dim3(nblk), dim3(256), 0, stream, logp, v, B, clip,
+                     (const float*)nullptr, ws, nblk, g_pg, g_vf, g_logp, g_v);
+  return hipGetLastError();
+}
+
+// the same three launches with the hyperparameters read from x.hp, the SB3 diagnostics reduced
+// beside pg / vf and the stats / stop-word bookkeeping in the final single-wave kernel
+hipError_t launch_ppo_loss_fwd_ex(const float* logp, const float* v, const int64_t* idx, const float* adv,
+                                  const float* ret, const float* old_logp, const float* old_v, int B, int normalize,
+                                  const PpoLossEx& x, float* pg, float* vf, float* ws, hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  const int nblk = (B + LOSS_TPB - 1) / LOSS_TPB;
+  hipLaunchKernelGGL(loss_gather_kernel<true>, dim3(nblk), dim3(LOSS_TPB), 0, stream, idx, adv, ret, old_logp, old_v,
+                     x.hp, B, ws);
+  hipLaunchKernelGGL(loss_terms_kernel<true>, dim3(nblk), dim3(LOSS_TPB), 0, stream, logp, v, B, 0.f, x.hp, normalize,
+                     ws, nblk);
+  hipLaunchKernelGGL(loss_final_ex_kernel, dim3(1), dim3(64), 0, stream, (const float*)ws, B, nblk, x, pg, vf);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_loss_bwd_ex(const float* logp, const float* v, int B, const float* hp, const float* ws,
+                                  const float* g_pg, const float* g_vf, float* g_logp, float* g_v,
+                                  hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  const int nblk = (B + LOSS_TPB - 1) / LOSS_TPB;
+  hipLaunchKernelGGL(ppo_loss_bwd_kernel<true>, dim3(nblk), dim3(256), 0, stream, logp, v, B, 0.f, hp, ws, nblk, g_pg,
+                     g_vf, g_logp, g_v);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_kl_stop(const float* kl, const float* hp, float* stats, int n_epochs, int* ctl,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(kl_stop_kernel, dim3(1), dim3(64), 0, stream, kl, hp, stats, n_epochs, ctl);
   return hipGetLastError();
 }
 
@@ -1004,10 +1155,11 @@ int adam_partials(long long total) {
 
 // Any number of tensors (<= ADAM_MAXT * ADAM_MAXCHUNK): chunks of ADAM_MAXT share one partials
 // array, so every update block reduces the partials of ALL chunks to the same clip coefficient;
-// the step counters advance after every chunk's update has read them.
+// the step counters advance after every chunk's update has read them.  hp / skip non-NULL
+// (hs_adam_clip_ex): lr from the device block, and no chunk writes anything when *skip != 0.
 hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
                             float* const* step, const long long* numel, float* part, float max_norm, double lr,
-                            double b1, double b2, double eps, hipStream_t stream) {
+                            double b1, double b2, double eps, hipStream_t stream, const float* hp, const int* skip) {
   if (nt <= 0 || nt > ADAM_MAXT * ADAM_MAXCHUNK) return hipErrorInvalidValue;
   const int nchunk = (nt + ADAM_MAXT - 1) / ADAM_MAXT;
   AdamArgs a[ADAM_MAXCHUNK];
@@ -1036,8 +1188,8 @@ hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, floa
     if (nblk[c])
       hipLaunchKernelGGL(adam_update_kernel, dim3(nblk[c]), dim3(ADAM_TPB), 0, stream, a[c], (const float*)part,
                          off[nchunk], max_norm, (float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2),
-                         (float)eps);
-  for (int c = 0; c < nchunk; c++) hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(64), 0, stream, a[c]);
+                         (float)eps, hp, skip);
+  for (int c = 0; c < nchunk; c++) hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(64), 0, stream, a[c], skip);
   return hipGetLastError();
 }
 

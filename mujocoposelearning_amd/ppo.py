@@ -25,11 +25,13 @@ import torch
 import torch.nn as nn
 
 
+from . import _lib
 from . import batch as _batch_mod
 from ._lib import HS_ACT_RELU, HS_ACT_TANH
 from .ppo_ops import (FUSED_WIDTHS, Linear, _GaussLogpFn, _PPOLossFn, _SplitKLinearFn, _SplitKLinearReLUFn,  # noqa: F401
                       _SPLITK_ROWS, adam_clip_step, colsum, gae_device, activation_id, mlp2_forward,
-                      mlp_forward, mlp_head_forward, ppo_act, ppo_loss, ppo_post)
+                      mlp_forward, mlp_head_forward, ppo_act, ppo_kl_stop, ppo_loss, ppo_loss_ex, ppo_post,
+                      ppo_stats_size)
 
 FUSED_MLP = True      # rollout forward through the fused hs_mlp2_forward kernel where it applies
 FUSED_MLP_MAX_ROWS = None   # ... up to this many rows (None: any)
@@ -43,6 +45,14 @@ def _fused_width(w1, mid):
     if len(mid) != 1 or w1.shape[1] != 2 * H or H not in FUSED_WIDTHS or tuple(mid[0][0].shape) != (2, H, H):
         return None
     return H
+
+
+def _schedule_value(x, progress_remaining):
+    """SB3's schedules: a constant, or a callable of progress_remaining (1 at the start of learn(),
+    falling to 0 at total_timesteps); None stays None."""
+    if x is None:
+        return None
+    return float(x(progress_remaining)) if callable(x) else float(x)
 
 
 def _flat_packed(pk):
@@ -271,7 +281,7 @@ class PPO:
     def __init__(self, env, learning_rate=3e-4, n_steps=2048, batch_size=64, n_epochs=10, gamma=0.99,
                  gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  policy_kwargs=None, seed=0, world_size=None, rank=None, sync_grads=None, stagger_episodes=False,
-                 normalize_advantage=True):
+                 normalize_advantage=True, target_kl=None, clip_range_vf=None):
         import torch.distributed as dist
         if world_size is None:
             world_size = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -299,12 +309,21 @@ class PPO:
         torch.manual_seed(seed + 7919 * rank)   # per-rank exploration noise / minibatch order
         # fused (single-kernel) Adam on a device; the same update rule and state_dict as foreach Adam
         cuda = self.device.type == "cuda"
-        self.opt = torch.optim.Adam(self.policy.parameters(), lr=learning_rate, eps=1e-5,
+        # SB3 2.3.2's train controls: target_kl (None: no early stop), clip_range_vf (None: no value
+        # clipping); learning_rate, clip_range and clip_range_vf may be schedules f(progress_remaining),
+        # evaluated at the start of every train() (_update_hyperparameters)
+        self.target_kl, self.clip_range_vf = target_kl, clip_range_vf
+        self.n_updates = 0
+        self._total_timesteps = None     # set while learn() runs: progress_remaining = 1 - steps / total
+        self._lr_now = _schedule_value(learning_rate, 1.0)
+        self._clip_now = _schedule_value(clip_range, 1.0)
+        self._clip_vf_now = _schedule_value(clip_range_vf, 1.0)
+        self.opt = torch.optim.Adam(self.policy.parameters(), lr=self._lr_now, eps=1e-5,
                                     fused=True if cuda else None, capturable=cuda)
         # on a device the minibatch step replays as HIP graphs (see _build_graphs); the update is
         # launch-bound without them (~1.3 ms of kernels per 32768-sample step, ~1.7 ms eager)
         self.graphs = cuda
-        self._graphs = None
+        self._graphs = self._epoch_graph = None
         self.n_steps, self.batch_size, self.n_epochs = n_steps, batch_size, n_epochs
         self.gamma, self.gae_lambda, self.clip_range = gamma, gae_lambda, clip_range
         self.ent_coef, self.vf_coef, self.max_grad_norm = ent_coef, vf_coef, max_grad_norm
@@ -349,6 +368,46 @@ class PPO:
         self._noise_ctr = torch.zeros(1, dtype=torch.int64, device=dev)    # Philox step counter (device)
         self._rollout_graph = None
         self.logger = {}
+        # with world > 1 the stop decision is taken from the global minibatch's approx_kl, which rides
+        # as one extra element of the gradient bucket (only when target_kl is set: the bucket is the
+        # parameters alone otherwise, and the logged approx_kl is then this rank's)
+        self._kl_sync = self.sync_grads and target_kl is not None
+        if cuda:
+            # device-resident train controls (include/hsim.h HS_PPO_*): the hyperparameter block every
+            # update kernel reads (so captured graphs follow schedules), the stop word + epoch index,
+            # and the stats block read back once per train()
+            self._hp = torch.zeros(_lib.HS_PPO_HP_SIZE, dtype=f, device=dev)
+            self._hp_host = torch.zeros(_lib.HS_PPO_HP_SIZE, dtype=f).pin_memory()   # staging: an async copy
+            # control words and stats in one allocation, so one launch zeroes both before a train()
+            self._blk = torch.zeros(2 + ppo_stats_size(n_epochs), dtype=f, device=dev)
+            self._ctl = self._blk[:2].view(torch.int32)
+            self._stats = self._blk[2:]
+            self._kl_local = torch.zeros(1, dtype=f, device=dev)
+            self._upload_hyperparameters()
+
+    # -- SB3's per-iteration hyperparameters ------------------------------------------------------
+    def _update_hyperparameters(self):
+        """SB3's _update_current_progress_remaining + _update_learning_rate + the clip schedules of
+        PPO.train: evaluate learning_rate / clip_range / clip_range_vf at progress_remaining
+        (1 - num_timesteps / total_timesteps inside learn(), 1.0 for a bare train()) and hand them to
+        the optimizer (CPU) and, in one small copy, to the device block (GPU)."""
+        total = self._total_timesteps
+        progress = 1.0 if not total else 1.0 - float(self.num_timesteps) / float(total)
+        self._lr_now = _schedule_value(self.learning_rate, progress)
+        self._clip_now = _schedule_value(self.clip_range, progress)
+        self._clip_vf_now = _schedule_value(self.clip_range_vf, progress)
+        for grp in self.opt.param_groups:
+            grp["lr"] = self._lr_now
+        if self.device.type == "cuda":
+            self._upload_hyperparameters()
+
+    def _upload_hyperparameters(self):
+        cvf, tkl = self._clip_vf_now, self.target_kl
+        # the pinned staging buffer is rewritten only here, and every train() ends in a device -> host
+        # read of the stats block, so the previous copy has long completed
+        self._hp_host.copy_(torch.tensor([self._lr_now, self._clip_now, -1.0 if cvf is None else cvf,
+                                          -1.0 if tkl is None else 1.5 * tkl], dtype=torch.float32))
+        self._hp.copy_(self._hp_host, non_blocking=True)
 
     def collect_rollouts(self):
         if self.device.type == "cuda":
@@ -602,11 +661,14 @@ class PPO:
         else:
             dist.all_reduce(flat)        # ONE RCCL all-reduce per optimizer step (xGMI ring)
 
-    def _allreduce_grads(self):
+    def _allreduce_grads(self, kl=None):
+        """All-reduce the weighted gradient bucket; with ``kl`` (this rank's approx_kl of the minibatch,
+        when target_kl is set) it rides as one extra element, weighted like the gradients, and the
+        global minibatch's approx_kl is returned (a one-element view of the reduced bucket)."""
         if not self.sync_grads:
-            return
+            return kl
         grads = [p.grad for p in self.flat]
-        flat = torch.cat([g.reshape(-1) for g in grads])
+        flat = torch.cat([g.reshape(-1) for g in grads] + ([] if kl is None else [kl.detach().reshape(1).to(grads[0])]))
         flat.mul_(self.grad_weight)      # this rank's share of the samples (1/world for even shards)
         self._allreduce_flat(flat)
         o = 0
@@ -614,13 +676,21 @@ class PPO:
             n = g.numel()
             g.copy_(flat[o:o + n].view_as(g))
             o += n
+        return None if kl is None else flat[o:o + 1]
 
-    def _minibatch_loss(self, obs, act, old_logp, adv, ret, idx):
-        """SB3 PPO.train's per-minibatch loss (clipped surrogate + vf_coef MSE - ent_coef entropy)."""
+    def _minibatch_loss(self, obs, act, old_logp, adv, ret, idx, old_val=None):
+        """SB3 PPO.train's per-minibatch loss (clipped surrogate + vf_coef MSE - ent_coef entropy), the
+        value loss on old_v + clamp(v - old_v, +-clip_range_vf) when clip_range_vf is set (old_val: the
+        rollout values, the buffer's by default).  The minibatch's approx_kl and clip_fraction: on a
+        device they go straight into the stats block (hs_ppo_loss_ex), on the CPU into _mb_extra."""
         mean, v = self.policy(obs[idx])
         logp = self.policy._logp(mean, act[idx])
+        if old_val is None:
+            old_val = self.buf["val"].reshape(-1)
         if logp.is_cuda:                            # fused HIP loss (same formulas as below)
-            pg, vf = ppo_loss(logp, v, idx, adv, ret, old_logp, self.clip_range, self.normalize_advantage)
+            pg, vf = ppo_loss_ex(logp, v, idx, adv, ret, old_logp, old_val, self._hp, self.policy.log_std.detach(),
+                                 self.vf_coef, self.ent_coef, self._stats, self.n_epochs, self._ctl,
+                                 self._kl_local if self._kl_sync else None, self.normalize_advantage)
             loss = torch.add(pg, vf, alpha=self.vf_coef)
             if self.ent_coef:                       # SB3's default ent_coef 0: no term, no launches
                 loss = loss - self.ent_coef * self.policy.entropy()
@@ -629,41 +699,143 @@ class PPO:
         a = adv[idx]
         if self.normalize_advantage and a.numel() > 1:
             a = (a - a.mean()) / (a.std() + 1e-8)
-        ratio = torch.exp(logp - old_logp[idx])
-        pg = -torch.min(a * ratio, a * ratio.clamp(1 - self.clip_range, 1 + self.clip_range)).mean()
+        clip, clip_vf = self._clip_now, self._clip_vf_now
+        log_ratio = logp - old_logp[idx]
+        ratio = torch.exp(log_ratio)
+        pg = -torch.min(a * ratio, a * ratio.clamp(1 - clip, 1 + clip)).mean()
+        if clip_vf is not None:
+            ov = old_val[idx]
+            v = ov + torch.clamp(v - ov, -clip_vf, clip_vf)
         vf = torch.nn.functional.mse_loss(ret[idx], v)
+        with torch.no_grad():                       # SB3: approx_kl_div and clip_fraction of the minibatch
+            self._mb_extra = (((ratio - 1) - log_ratio).mean(), ((ratio - 1).abs() > clip).float().mean(), ent_mean)
         return pg + self.ent_coef * (-ent_mean) + self.vf_coef * vf, pg, vf
 
+    @staticmethod
+    def _explained_variance(val, ret):
+        """SB3 utils.explained_variance: 1 - Var(ret - val) / Var(ret) (population variances), nan when
+        Var(ret) == 0; a 0-dim tensor on the inputs' device."""
+        y, yp = ret.reshape(-1), val.reshape(-1)
+        var_y = y.var(unbiased=False)
+        return torch.where(var_y == 0, torch.full_like(var_y, float("nan")), 1 - (y - yp).var(unbiased=False) / var_y)
+
+    def _train_stats(self, st, epochs_entered):
+        """The logger entries of one train() from a stats block (a list laid out as HS_PPO_STAT_*)."""
+        L = _lib
+        n = max(st[L.HS_PPO_STAT_COUNT], 1.0)
+        e = max(epochs_entered - 1, 0)      # SB3 resets approx_kl_divs every epoch: the last one entered
+        kl_sum, kl_n = st[L.HS_PPO_STAT_KL + 2 * e], st[L.HS_PPO_STAT_KL + 2 * e + 1]
+        out = dict(policy_loss=st[L.HS_PPO_STAT_POLICY_LOSS] / n, value_loss=st[L.HS_PPO_STAT_VALUE_LOSS] / n,
+                   approx_kl=kl_sum / kl_n if kl_n else float("nan"),
+                   clip_fraction=st[L.HS_PPO_STAT_CLIP_FRACTION] / n, entropy_loss=-st[L.HS_PPO_STAT_ENTROPY] / n,
+                   explained_variance=st[L.HS_PPO_STAT_EXPLAINED_VARIANCE], loss=st[L.HS_PPO_STAT_LOSS_LAST],
+                   std=st[L.HS_PPO_STAT_STD], n_updates=self.n_updates, learning_rate=self._lr_now,
+                   clip_range=self._clip_now)
+        if self._clip_vf_now is not None:
+            out["clip_range_vf"] = self._clip_vf_now
+        self.last_kl = st[L.HS_PPO_STAT_KL_LAST]       # the approx_kl the last stop decision was taken from
+        self.logger.update(out)
+        return out
+
     def train(self, adv, ret):
+        """SB3 PPO.train: n_epochs passes over the rollout in minibatches; with target_kl, the first
+        minibatch whose approx_kl exceeds 1.5 target_kl takes no optimizer step and ends the update
+        (its statistics are recorded, n_updates counts its epoch)."""
         b = self.buf
         T, N = self.n_steps, self.env.num_envs
         M = T * N
-        if self.device.type == "cuda" and self.graphs and self._chunk is not None:
-            return self._train_graphed(adv, ret)
+        self._update_hyperparameters()
+        if self.device.type == "cuda":
+            # one stats block per train(): zeroed here (with the control words), filled by the loss
+            # kernels, read once at the end
+            self._blk.zero_()
+            if self.graphs and self._chunk is not None:
+                return self._train_graphed(adv, ret)
+            return self._train_device_eager(adv, ret)
         obs = b["obs"].reshape(M, -1)
         act = b["act"].reshape(M, -1)
-        old_logp = b["logp"].reshape(-1)
+        old_logp, old_val = b["logp"].reshape(-1), b["val"].reshape(-1)
         adv, ret = adv.reshape(-1), ret.reshape(-1)
-        stats = []
+        st = [0.0] * (_lib.HS_PPO_STAT_KL + 2 * self.n_epochs)
+        st[_lib.HS_PPO_STAT_EXPLAINED_VARIANCE] = float(self._explained_variance(old_val, ret))
+        stop, entered = False, 0
         for epoch in range(self.n_epochs):
             perm = torch.randperm(M, device=self.device)
+            entered += 1
+            self.n_updates += 1
             for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
                 self.grad_weight = self._mb_weight[j]
-                loss, pg, vf = self._minibatch_loss(obs, act, old_logp, adv, ret, perm[s:e])
+                loss, pg, vf = self._minibatch_loss(obs, act, old_logp, adv, ret, perm[s:e], old_val)
+                kl, cf, ent = self._mb_extra
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
-                self._allreduce_grads()
+                # world > 1: the decision value is the global minibatch's approx_kl (same on every rank)
+                red = self._allreduce_grads(kl if self._kl_sync else None)
+                kl = float(kl if red is None else red)
+                for k, x in ((_lib.HS_PPO_STAT_POLICY_LOSS, pg), (_lib.HS_PPO_STAT_VALUE_LOSS, vf),
+                             (_lib.HS_PPO_STAT_CLIP_FRACTION, cf), (_lib.HS_PPO_STAT_ENTROPY, ent),
+                             (_lib.HS_PPO_STAT_LOSS, loss)):
+                    st[k] += float(x.detach())
+                st[_lib.HS_PPO_STAT_LOSS_LAST] = float(loss.detach())
+                st[_lib.HS_PPO_STAT_COUNT] += 1.0
+                st[_lib.HS_PPO_STAT_KL + 2 * epoch] += kl
+                st[_lib.HS_PPO_STAT_KL + 2 * epoch + 1] += 1.0
+                st[_lib.HS_PPO_STAT_KL_LAST] = kl
+                if self.target_kl is not None and kl > 1.5 * self.target_kl:
+                    stop = True                      # SB3: break before the optimizer step
+                    break
                 self._clip_and_step()
-                stats.append((pg.detach(), vf.detach()))
-        pg = torch.stack([s[0] for s in stats]).mean().item()
-        vf = torch.stack([s[1] for s in stats]).mean().item()
-        return dict(policy_loss=pg, value_loss=vf)
+            if stop:
+                break
+        st[_lib.HS_PPO_STAT_STD] = float(self.policy.log_std.detach().exp().mean())
+        return self._train_stats(st, entered)
+
+    def _stopped(self):
+        """The device stop word, read by the host once after an epoch (only with target_kl set)."""
+        return self.target_kl is not None and bool(self._ctl[_lib.HS_PPO_CTL_STOP].item())
+
+    def _finish_device_train(self, entered, ret):
+        """The per-iteration statistics (queued behind the update's kernels, so the host's launches
+        hide under them; the rollout values and returns are untouched by the update) and the read."""
+        self._stats[_lib.HS_PPO_STAT_EXPLAINED_VARIANCE].copy_(self._explained_variance(self.buf["val"], ret))
+        self._stats[_lib.HS_PPO_STAT_STD].copy_(self.policy.log_std.detach().exp().mean())
+        return self._train_stats(self._stats.tolist(), entered)      # the one device -> host read
+
+    def _train_device_eager(self, adv, ret):
+        """train() on a device without graphs (capture refused, or ragged minibatches): the same
+        kernels and device predicates as the graphed update -- after the stop word is set the rest of
+        that epoch's minibatches run and are discarded -- with the stop word read once per epoch."""
+        b = self.buf
+        M = self.n_steps * self.env.num_envs
+        obs, act = b["obs"].reshape(M, -1), b["act"].reshape(M, -1)
+        old_logp, old_val = b["logp"].reshape(-1), b["val"].reshape(-1)
+        adv, ret = adv.reshape(-1), ret.reshape(-1)
+        entered = 0
+        for epoch in range(self.n_epochs):
+            perm = torch.randperm(M, device=self.device)
+            entered += 1
+            self.n_updates += 1
+            for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
+                self.grad_weight = self._mb_weight[j]
+                loss, pg, vf = self._minibatch_loss(obs, act, old_logp, adv, ret, perm[s:e], old_val)
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                kl = self._allreduce_grads(self._kl_local if self._kl_sync else None)
+                if self._kl_sync:
+                    ppo_kl_stop(kl, self._hp, self._stats, self.n_epochs, self._ctl)
+                self._clip_and_step()
+            if self._stopped():
+                break
+            self._ctl[_lib.HS_PPO_CTL_EPOCH].add_(1)
+        return self._finish_device_train(entered, ret)
 
     def _clip_and_step(self):
-        """clip_grad_norm_(max_grad_norm) + Adam step: hs_adam_clip on a device, torch on the CPU."""
+        """clip_grad_norm_(max_grad_norm) + Adam step: hs_adam_clip_ex on a device (lr from the device
+        block, skipped when the stop word is set), torch on the CPU."""
         params = self.flat
         if params[0].is_cuda:
-            self._adam_ws = adam_clip_step(self.opt, params, self.max_grad_norm, getattr(self, "_adam_ws", None))
+            self._adam_ws = adam_clip_step(self.opt, params, self.max_grad_norm, getattr(self, "_adam_ws", None),
+                                           hp=self._hp, skip=self._ctl)
         else:
             torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm)
             self.opt.step()
@@ -676,26 +848,31 @@ class PPO:
         bucket + clip_grad_norm + capturable fused Adam.  The per-step RCCL all-reduce of the
         bucket (world > 1) is the one eager call between the two replays.  The warm-up steps
         capture needs are undone (parameters and Adam state restored in place), so graphed
-        training takes exactly the eager path's optimizer steps."""
+        training takes exactly the eager path's optimizer steps.
+        Every per-iteration hyperparameter is read from the device block (_hp) and the target_kl stop
+        is a device predicate (the stop word of _ctl: set by the loss's final kernel -- with world > 1
+        by hs_ppo_kl_stop in G2, from the bucket's all-reduced extra element, before the Adam kernels
+        -- and read by hs_adam_clip_ex), so the graphs are captured once and follow the schedules."""
         b, M, bs = self.buf, self.n_steps * self.env.num_envs, self._chunk
         dev = self.device
         self._g_idx = torch.zeros(bs, dtype=torch.long, device=dev)
         self._g_adv = torch.zeros(M, dtype=torch.float32, device=dev)
         self._g_ret = torch.zeros(M, dtype=torch.float32, device=dev)
-        self._g_stats = torch.zeros(2, dtype=torch.float32, device=dev)
         src = (b["obs"].view(M, -1), b["act"].view(M, -1), b["logp"].view(-1), self._g_adv, self._g_ret)
+        old_val = b["val"].view(-1)
         params = list(self.policy.parameters())
 
-        sync = self.sync_grads
-        self._g_flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev) if sync else None
+        sync, kl_sync = self.sync_grads, self._kl_sync
+        n_par = sum(p.numel() for p in params)
+        self._g_flat = torch.zeros(n_par + (1 if kl_sync else 0), dtype=torch.float32, device=dev) if sync else None
         self._g_w = torch.full((1,), float(self._mb_weight[0]), dtype=torch.float32, device=dev)
 
         def g1_body():
-            loss, pg, vf = self._minibatch_loss(*src, self._g_idx)
+            loss, pg, vf = self._minibatch_loss(*src, self._g_idx, old_val)
             loss.backward()
-            self._g_stats.add_(torch.stack([pg.detach(), vf.detach()]))
             if sync:                     # the weighted gradient bucket the eager all-reduce sends
-                torch.cat([p.grad.reshape(-1) for p in params], out=self._g_flat)
+                torch.cat([p.grad.reshape(-1) for p in params] + ([self._kl_local] if kl_sync else []),
+                          out=self._g_flat)
                 self._g_flat.mul_(self._g_w)     # minibatch weight, refreshed before each replay
 
         def g2_body():
@@ -705,11 +882,14 @@ class PPO:
                     n = p.numel()
                     p.grad.copy_(self._g_flat[o:o + n].view_as(p.grad))
                     o += n
+                if kl_sync:              # the global minibatch's approx_kl: stop decision before Adam
+                    ppo_kl_stop(self._g_flat[n_par:], self._hp, self._stats, self.n_epochs, self._ctl)
             self._clip_and_step()
 
         saved_p = [p.detach().clone() for p in params]
         saved_s = {id(p): {k: v.clone() for k, v in self.opt.state[p].items()} for p in params if p in self.opt.state}
         self._g_idx.copy_(torch.arange(bs, device=dev))
+        self._ctl.zero_()                # the warm-up steps below must not meet a set stop word
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -728,20 +908,22 @@ class PPO:
             with torch.cuda.graph(g2, pool=pool, capture_error_mode="thread_local"):
                 g2_body()
             self._graphs = (g1, g2)
+            self._epoch_graph = None
             if not sync:
                 # world 1: the whole epoch -- every minibatch's gather, forward, loss, backward, clip and
                 # Adam, indices read from slices of one static permutation buffer -- as ONE graph, so
                 # small minibatches (README.md:23-53: batch 128, 128 steps per epoch) cost one replay
                 # per epoch instead of two per minibatch.  Each step starts from .grad = None, so its
-                # backward writes fresh gradients exactly as G1 does.
+                # backward writes fresh gradients exactly as G1 does.  After a minibatch trips the
+                # target_kl stop the rest of the epoch still runs forward and backward inside the graph
+                # and is discarded by the stop word (no statistics, no optimizer step).
                 self._g_perm = torch.zeros(M, dtype=torch.long, device=dev)
                 ge = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(ge, pool=pool, capture_error_mode="thread_local"):
                     for s0, e0 in zip(self._mb_bounds, self._mb_bounds[1:]):
                         self.opt.zero_grad(set_to_none=True)
-                        loss, pg, vf = self._minibatch_loss(*src, self._g_perm[s0:e0])
+                        loss, pg, vf = self._minibatch_loss(*src, self._g_perm[s0:e0], old_val)
                         loss.backward()
-                        self._g_stats.add_(torch.stack([pg.detach(), vf.detach()]))
                         self._clip_and_step()
                 self._epoch_graph = ge
         except RuntimeError as e:                  # capture refused: train eagerly from here on
@@ -761,37 +943,39 @@ class PPO:
                             v.copy_(old[k])
                         elif torch.is_tensor(v):
                             v.zero_()
+                self._blk.zero_()    # the warm-up's statistics and stop word: back to the start of train()
 
     def _train_graphed(self, adv, ret):
         if self._graphs is None:
             self._build_graphs()
             if self._graphs is None:
-                return self.train(adv, ret)       # capture failed: self.graphs is now False
+                return self._train_device_eager(adv, ret)       # capture failed: self.graphs is now False
         g1, g2 = self._graphs
         M = self.n_steps * self.env.num_envs
         self._g_adv.copy_(adv.reshape(-1))
         self._g_ret.copy_(ret.reshape(-1))
-        self._g_stats.zero_()
-        n = 0
+        entered = 0
         ge = getattr(self, "_epoch_graph", None)
         for epoch in range(self.n_epochs):
             perm = torch.randperm(M, device=self.device)
+            entered += 1
+            self.n_updates += 1
             if ge is not None:                    # world 1: one replay per epoch
                 self._g_perm.copy_(perm)
                 ge.replay()
-                n += len(self._mb_bounds) - 1
-                continue
-            for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
-                self._g_idx.copy_(perm[s:e])
-                if self.sync_grads:
-                    self._g_w.fill_(self._mb_weight[j])
-                g1.replay()
-                if self.sync_grads:
-                    self._allreduce_flat(self._g_flat)
-                g2.replay()
-                n += 1
-        pg, vf = (self._g_stats / n).tolist()
-        return dict(policy_loss=pg, value_loss=vf)
+            else:
+                for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
+                    self._g_idx.copy_(perm[s:e])
+                    if self.sync_grads:
+                        self._g_w.fill_(self._mb_weight[j])
+                    g1.replay()
+                    if self.sync_grads:
+                        self._allreduce_flat(self._g_flat)
+                    g2.replay()
+            if self._stopped():                   # target_kl only: one read of the stop word per epoch
+                break
+            self._ctl[_lib.HS_PPO_CTL_EPOCH].add_(1)
+        return self._finish_device_train(entered, ret)
 
     WARN_KINDS = _batch_mod.WARN_KINDS
 
@@ -819,6 +1003,13 @@ class PPO:
 
     def learn(self, total_timesteps, callback=None, log_interval=1):
         it = 0
+        self._total_timesteps = total_timesteps      # schedules: progress_remaining = 1 - steps / total
+        try:
+            return self._learn(total_timesteps, callback, it)
+        finally:
+            self._total_timesteps = None
+
+    def _learn(self, total_timesteps, callback, it):
         while self.num_timesteps < total_timesteps:
             t0 = time.perf_counter()
             adv, ret = self.collect_rollouts()
@@ -828,8 +1019,8 @@ class PPO:
             t2 = time.perf_counter()
             it += 1
             mean_ret = float(np.mean(self.ep_returns[-100:])) if self.ep_returns else float("nan")
-            self.logger = dict(iteration=it, timesteps=self.num_timesteps, rollout_s=t1 - t0, train_s=t2 - t1,
-                               ep_rew_mean=mean_ret, **st)
+            self.logger = dict(self.logger, iteration=it, timesteps=self.num_timesteps, rollout_s=t1 - t0,
+                               train_s=t2 - t1, ep_rew_mean=mean_ret, **st)
             if warn is not None:
                 self.logger["env_warnings"] = [int(x) for x in warn]
             if self._agree_stop(callback is not None and callback(self) is False):
@@ -849,9 +1040,12 @@ class PPO:
     def _data(self):
         act = self.policy_kwargs.get("activation_fn", nn.Tanh)
         return {"n_steps": self.n_steps, "batch_size": self.batch_size, "n_epochs": self.n_epochs,
-                "gamma": self.gamma, "gae_lambda": self.gae_lambda, "clip_range": self.clip_range,
+                "gamma": self.gamma, "gae_lambda": self.gae_lambda,
+                "clip_range": _schedule_value(self.clip_range, 1.0),     # a schedule: its value at the start
+                "clip_range_vf": _schedule_value(self.clip_range_vf, 1.0), "target_kl": self.target_kl,
                 "ent_coef": self.ent_coef, "vf_coef": self.vf_coef, "max_grad_norm": self.max_grad_norm,
-                "learning_rate": self.learning_rate, "num_timesteps": self.num_timesteps,
+                "learning_rate": _schedule_value(self.learning_rate, 1.0), "num_timesteps": self.num_timesteps,
+                "n_updates": self.n_updates,
                 "n_envs": self.n_envs_global,
                 "policy_kwargs": {"net_arch": self.net_arch,
                                   "activation_fn": act if isinstance(act, str) else act.__name__}}
@@ -867,4 +1061,11 @@ class PPO:
         data = load_sb3_zip(path, self.policy, self.opt, map_location=self.device)
         self._graphs = None          # optimizer state tensors were replaced: recapture
         self.num_timesteps = int(data.get("num_timesteps", 0))
+        self.n_updates = int(data.get("n_updates", 0))           # absent in older checkpoints
+        if "target_kl" in data:
+            self.target_kl = data["target_kl"]
+            self._kl_sync = self.sync_grads and self.target_kl is not None
+        if "clip_range_vf" in data and not callable(self.clip_range_vf):   # a schedule stays the caller's
+            self.clip_range_vf = data["clip_range_vf"]
+        self._update_hyperparameters()
         return self

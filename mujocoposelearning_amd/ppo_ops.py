@@ -6,7 +6,8 @@ restatement for CPU tensors (toy envs, tests).
 * rollout: ppo_act (Gaussian sample + log-prob + clip + buffer writes), ppo_post (bootstrap,
   dones, returns, next obs), gae_device (GAE reverse scan)
 * update: _GaussLogpFn (log-prob fwd/bwd), _PPOLossFn / ppo_loss (clipped surrogate + value MSE
-  fwd/bwd), _SplitKLinearFn / _SplitKLinearReLUFn / Linear / mlp_forward (split-K weight
+  fwd/bwd), _PPOLossExFn / ppo_loss_ex / ppo_kl_stop (the same with device-resident hyperparameters,
+  value clipping, SB3's train statistics and the target_kl stop word), _SplitKLinearFn / _SplitKLinearReLUFn / Linear / mlp_forward (split-K weight
   gradients, ReLU in the GEMM epilogue or an in-place Tanh), _MLPChainFn / mlp_head_forward (a whole
   net as one node: input gradient + activation backward + bias sum fused, hs_dgrad_act), colsum (deterministic column sums), adam_clip_step
   (clip_grad_norm_ + Adam on a torch Adam's own state)
@@ -133,12 +134,90 @@ def ppo_loss(logp, v, idx, adv, ret, old_logp, clip, normalize=True):
     return _PPOLossFn.apply(logp, v, idx, adv, ret, old_logp, clip, normalize)
 
 
-def adam_clip_step(opt, params, max_norm, workspace=None):
+class _PPOLossExFn(torch.autograd.Function):
+    """_PPOLossFn through hs_ppo_loss_ex / hs_ppo_loss_grad_ex: clip_range and clip_range_vf come from the
+    device hyperparameter block ``hp``, and the forward's last launch also adds SB3's train statistics
+    of the minibatch to ``stats`` and takes the target_kl stop decision (``ctl``), see include/hsim.h."""
+
+    @staticmethod
+    def forward(ctx, logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl,
+                kl_out, normalize):
+        from . import _lib
+        logp, v = logp.contiguous(), v.contiguous()
+        B = logp.shape[0]
+        dev = logp.device
+        L = _lib.lib()
+        pg = torch.empty((), dtype=torch.float32, device=dev)
+        vf = torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(L.hs_ppo_loss_workspace_ex(B)), dtype=torch.float32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.hs_ppo_loss_ex(logp.data_ptr(), v.data_ptr(), idx.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                    old_logp.data_ptr(), old_val.data_ptr(), B, 1 if normalize else 0, hp.data_ptr(),
+                                    log_std.data_ptr(), log_std.numel(), float(vf_coef), float(ent_coef),
+                                    stats.data_ptr(), int(n_epochs), ctl.data_ptr(),
+                                    None if kl_out is None else kl_out.data_ptr(), pg.data_ptr(), vf.data_ptr(),
+                                    ws.data_ptr(), st))
+        ctx.save_for_backward(logp, v, ws, hp)
+        return pg, vf
+
+    @staticmethod
+    def backward(ctx, g_pg, g_vf):
+        from . import _lib
+        logp, v, ws, hp = ctx.saved_tensors
+        B = logp.shape[0]
+        dev = logp.device
+        z = torch.zeros((), dtype=torch.float32, device=dev)
+        g_pg = z if g_pg is None else g_pg.to(torch.float32).contiguous()
+        g_vf = z if g_vf is None else g_vf.to(torch.float32).contiguous()
+        g_logp = torch.empty(B, dtype=torch.float32, device=dev)
+        g_v = torch.empty(B, dtype=torch.float32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib().hs_ppo_loss_grad_ex(logp.data_ptr(), v.data_ptr(), B, hp.data_ptr(), ws.data_ptr(),
+                                                  g_pg.data_ptr(), g_vf.data_ptr(), g_logp.data_ptr(), g_v.data_ptr(),
+                                                  st))
+        return (g_logp, g_v) + (None,) * 14
+
+
+def ppo_stats_size(n_epochs):
+    """Floats of the stats block of ``n_epochs`` epochs (hs_ppo_stats_size)."""
+    from . import _lib
+    return int(_lib.lib().hs_ppo_stats_size(int(n_epochs)))
+
+
+def ppo_loss_ex(logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl,
+                kl_out=None, normalize=True):
+    """(policy_loss, value_loss) of one minibatch on a device through hs_ppo_loss_ex: hyperparameters from
+    the float32 device block ``hp`` [4] (lr, clip_range, clip_range_vf or < 0, 1.5 target_kl or < 0), SB3's
+    train statistics added to ``stats`` [ppo_stats_size(n_epochs)] and the stop word / epoch index in the
+    int32 ``ctl`` [2]; ``kl_out`` (a float32 device scalar) defers the stop decision to ppo_kl_stop."""
+    for t in (adv, ret, old_logp, old_val):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
+    assert idx.dtype == torch.int64 and idx.is_contiguous()
+    assert hp.dtype == torch.float32 and hp.numel() == 4 and hp.is_contiguous()
+    assert ctl.dtype == torch.int32 and ctl.numel() == 2 and stats.dtype == torch.float32
+    assert stats.is_contiguous() and stats.numel() >= ppo_stats_size(n_epochs)
+    assert log_std.dtype == torch.float32 and log_std.is_contiguous() and log_std.numel() <= 32
+    assert kl_out is None or (kl_out.dtype == torch.float32 and kl_out.numel() == 1)
+    return _PPOLossExFn.apply(logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef, ent_coef, stats,
+                              n_epochs, ctl, kl_out, normalize)
+
+
+def ppo_kl_stop(kl, hp, stats, n_epochs, ctl):
+    """The deferred stop decision of ppo_loss_ex(kl_out=...) from the device scalar ``kl`` (hs_ppo_kl_stop)."""
+    from . import _lib
+    assert kl.dtype == torch.float32 and kl.numel() == 1
+    _lib.check(_lib.lib().hs_ppo_kl_stop(kl.data_ptr(), hp.data_ptr(), stats.data_ptr(), int(n_epochs), ctl.data_ptr(),
+                                         torch.cuda.current_stream(kl.device).cuda_stream))
+
+
+def adam_clip_step(opt, params, max_norm, workspace=None, hp=None, skip=None):
     """clip_grad_norm_(params, max_norm) + opt.step() for a single-group torch Adam on a device in
     three HIP launches (hs_adam_clip).  Reads and updates the optimizer's own state tensors
     (exp_avg, exp_avg_sq, capturable float32 step), so torch's state_dict / SB3 checkpoints see
     the same state; initialises it the way torch's Adam does on its first step.  Returns the
-    workspace (reuse it: a persistent buffer keeps graph captures valid)."""
+    workspace (reuse it: a persistent buffer keeps graph captures valid).
+    With ``hp`` and ``skip`` (hs_adam_clip_ex) the learning rate is hp[0] of the device hyperparameter
+    block instead of the param group's, and the step is a no-op when the int32 device word skip[0] != 0."""
     import ctypes as C
     from . import _lib
     grp = opt.param_groups[0]
@@ -159,6 +238,14 @@ def adam_clip_step(opt, params, max_norm, workspace=None):
     arr = lambda xs: (C.c_void_p * nt)(*[x.data_ptr() for x in xs])   # noqa: E731
     sts = [opt.state[p] for p in params]
     b1, b2 = grp["betas"]
+    if hp is not None:
+        assert hp.dtype == torch.float32 and skip.dtype == torch.int32
+        _lib.check(L.hs_adam_clip_ex(nt, arr(params), arr([p.grad for p in params]), arr([s["exp_avg"] for s in sts]),
+                                     arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]),
+                                     (C.c_int64 * nt)(*[p.numel() for p in params]), workspace.data_ptr(),
+                                     float(max_norm), hp.data_ptr(), skip.data_ptr(), float(b1), float(b2),
+                                     float(grp["eps"]), torch.cuda.current_stream(dev).cuda_stream))
+        return workspace
     _lib.check(L.hs_adam_clip(nt, arr(params), arr([p.grad for p in params]), arr([s["exp_avg"] for s in sts]),
                               arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]),
                               (C.c_int64 * nt)(*[p.numel() for p in params]), workspace.data_ptr(),

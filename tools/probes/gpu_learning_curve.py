@@ -1,7 +1,9 @@
 """Learning-curve sanity of the on-device PPO (SB3 is not importable, so the trainer
 is judged by the stand reward rising).  bench.py's train config: 4096 envs, n_steps 32,
 batch 32768, 4 epochs, lr 3e-4, MLP[256,256] ReLU (batch and epochs overridable).
-python tools/probes/gpu_learning_curve.py [iters] [stand|kneeling] [fp32|fp64] [seed] [batch] [epochs] [stagger] [lr]
+python tools/probes/gpu_learning_curve.py [iters] [stand|kneeling] [fp32|fp64] [seed] [batch] [epochs] [stagger] [lr] [target_kl]
+target_kl > 0: SB3's KL early stop; every printed row then carries that iteration's approx_kl, clip_fraction
+and the epochs entered before the stop (n_updates grows by one per epoch entered).
 stagger = 1: spread the envs' episode clocks over the episode after the first reset (env i starts
 i/N into it, as bench.py's window and the reference's 8 envs x 2048 steps per rollout do); without it
 every env resets together and a 32-step rollout sees one phase of the episode."""
@@ -21,10 +23,11 @@ from mujocoposelearning_amd.vec_env import HumanoidVecEnv  # noqa: E402
 XML = os.path.join(ROOT, "mujocoposelearning_amd", "assets", "humanoid.xml")
 
 
-def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epochs=4, stagger=0, lr=3e-4):
+def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epochs=4, stagger=0, lr=3e-4, target_kl=0.0):
     env = HumanoidVecEnv({"model_path": XML, "duration": 10.0, "reward_config": {"type": reward}, "frame_skip": 3},
                          n_envs=4096, model=HsModel(XML), seed=seed, precision=precision)
     ppo = PPO(env, n_steps=32, batch_size=batch, n_epochs=epochs, learning_rate=lr, seed=seed,
+              target_kl=target_kl if target_kl > 0 else None,
               policy_kwargs={"activation_fn": "ReLU", "net_arch": {"pi": [256, 256], "vf": [256, 256]}})
     if stagger:
         b, n, ep = env.batch, env.num_envs, 667
@@ -37,13 +40,15 @@ def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epoch
         adv, ret = ppo.collect_rollouts()
         r_step = float(ppo.buf["rew"].mean())
         h = float(ppo.buf["obs"][..., 0].mean())          # obs[0] = qpos[2], the torso height
+        n_before = ppo.n_updates
         st = ppo.train(adv, ret)
         if it % max(1, iters // 20) == 0 or it == 1:
             ep = float(np.mean(ppo.ep_returns[-200:])) if ppo.ep_returns else float("nan")
             rows.append((it, ppo.num_timesteps, r_step, h, ep, st["value_loss"], time.perf_counter() - t0))
             print(f"iter {it:4d} steps {ppo.num_timesteps / 1e6:6.1f}M  mean step reward {r_step:.4f}  "
                   f"mean height {h:.3f}  ep return (last 200) {ep:8.2f}  vf loss {st['value_loss']:.4f}  "
-                  f"log_std {float(ppo.policy.log_std.detach().mean()):.3f}  fused {ppo._fused_rollout_args() is not None}  "
+                  f"log_std {float(ppo.policy.log_std.detach().mean()):.3f}  approx_kl {st['approx_kl']:.4f}  "
+                  f"clip_fraction {st['clip_fraction']:.3f}  epochs {ppo.n_updates - n_before}/{epochs}  fused {ppo._fused_rollout_args() is not None}  "
                   f"{time.perf_counter() - t0:6.1f}s", flush=True)
     env.close()
     return rows
@@ -56,4 +61,5 @@ if __name__ == "__main__":
     main(int(sys.argv[1]) if len(sys.argv) > 1 else 400, sys.argv[2] if len(sys.argv) > 2 else "stand",
          sys.argv[3] if len(sys.argv) > 3 else "fp32", int(sys.argv[4]) if len(sys.argv) > 4 else 0,
          int(sys.argv[5]) if len(sys.argv) > 5 else 32768, int(sys.argv[6]) if len(sys.argv) > 6 else 4,
-         int(sys.argv[7]) if len(sys.argv) > 7 else 0, float(sys.argv[8]) if len(sys.argv) > 8 else 3e-4)
+         int(sys.argv[7]) if len(sys.argv) > 7 else 0, float(sys.argv[8]) if len(sys.argv) > 8 else 3e-4,
+         float(sys.argv[9]) if len(sys.argv) > 9 else 0.0)
