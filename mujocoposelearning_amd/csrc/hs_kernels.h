@@ -246,7 +246,7 @@ struct PackArgs {
 template <typename T>
 hipError_t launch_pack(const PackArgs<T>& a, hipStream_t stream);
 
-// PPO rollout bookkeeping around the policy GEMMs and the env step (ppo.hip)
+// PPO rollout bookkeeping around the policy GEMMs and the env step (ppo_rollout.hip)
 hipError_t launch_ppo_act(const float* mean, int mean_ld, const float* value, int value_ld, const float* log_std,
                           const float* episode_start, uint64_t seed, uint64_t counter, const uint64_t* counter_base,
                           int deterministic, float* act,
@@ -258,22 +258,22 @@ hipError_t launch_ppo_post(const float* reward, const uint8_t* terminated, const
                            size_t obs_floats, float* reward_out, uint8_t* done_out, double* ep_acc,
                            double* ep_return_out, float* episode_start, int N, hipStream_t stream);
 // fused 2-hidden-layer (H = 64, 128 or 256; act = ACT_RELU or ACT_TANH, hs_act.h) MLP forward of one packed
-// policy net (ppo.hip mlp2_fwd_kernel)
+// policy net (ppo_mlp.hip mlp2_fwd_kernel)
 hipError_t launch_mlp2_fwd(const float* X, int ldx, int D, int N, int H, int act, const float* W1, int ld1,
                            const float* b1, const float* W2, int ld2, const float* b2, const float* W3, int ld3,
                            const float* b3, int A, float* out, int ldo, hipStream_t stream);
-// column sums of a row-major [rows][cols] float32 matrix (ppo.hip); workspace of
+// column sums of a row-major [rows][cols] float32 matrix (ppo_reduce.hip); workspace of
 // colsum_workspace(rows, cols) floats (0: none needed)
 size_t colsum_workspace(size_t rows, size_t cols);
 hipError_t launch_colsum(const float* x, size_t rows, size_t cols, const float* row_weight, float* workspace,
                          float* out, hipStream_t stream);
-// diagonal-Gaussian log-prob of given actions and its backward (ppo.hip)
+// diagonal-Gaussian log-prob of given actions and its backward (ppo_rollout.hip)
 hipError_t launch_gauss_logp(const float* mean, int mean_ld, const float* act, const float* log_std, float* logp, int N,
                              int A, hipStream_t stream);
 hipError_t launch_gauss_logp_grad(const float* mean, int mean_ld, const float* act, const float* log_std,
                                   const float* g_logp, float* g_mean, float* gls_rows, int N, int A,
                                   hipStream_t stream);
-// SB3 PPO minibatch loss (clipped surrogate + value MSE) forward / backward (ppo.hip); workspace
+// SB3 PPO minibatch loss (clipped surrogate + value MSE) forward / backward (ppo_update.hip); workspace
 // of ppo_loss_workspace(B) floats, written by the forward and read by the backward
 size_t ppo_loss_workspace(int B);
 hipError_t launch_ppo_loss_fwd(const float* logp, const float* v, const int64_t* idx, const float* adv,
@@ -283,7 +283,7 @@ hipError_t launch_ppo_loss_bwd(const float* logp, const float* v, int B, float c
                                const float* g_pg, const float* g_vf, float* g_logp, float* g_v, hipStream_t stream);
 // The same with SB3's train controls on the device (hs_ppo_loss_ex, include/hsim.h): the float32
 // hyperparameter block hp[HP_*], the control words ctl[CTL_*] and the stats block stats[ST_*]
-// (== HS_PPO_HP_* / HS_PPO_CTL_* / HS_PPO_STAT_* of the header, static_assert in hs_api.cpp)
+// (== HS_PPO_HP_* / HS_PPO_CTL_* / HS_PPO_STAT_* of the header, static_assert in hs_api_ops.cpp)
 constexpr int HP_LR = 0, HP_CLIP = 1, HP_CLIP_VF = 2, HP_KL_STOP = 3;
 constexpr int CTL_STOP = 0, CTL_EPOCH = 1;
 constexpr int ST_PG = 0, ST_VF = 1, ST_CLIPFRAC = 2, ST_ENT = 3, ST_LOSS = 4, ST_LOSS_LAST = 5, ST_COUNT = 6,
@@ -307,7 +307,7 @@ hipError_t launch_ppo_loss_bwd_ex(const float* logp, const float* v, int B, cons
                                   hipStream_t stream);
 hipError_t launch_ppo_kl_stop(const float* kl, const float* hp, float* stats, int n_epochs, int* ctl,
                               hipStream_t stream);
-// clip_grad_norm_ + Adam over up to 1024 tensors (ppo.hip); part: adam_partials(total numel) floats.
+// clip_grad_norm_ + Adam over up to 1024 tensors (ppo_update.hip); part: adam_partials(total numel) floats.
 // hp / skip non-NULL: lr = hp[HP_LR] (device), and nothing is written when *skip != 0
 int adam_partials(long long total);
 hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, float* const* m, float* const* v,
@@ -315,9 +315,9 @@ hipError_t launch_adam_clip(int nt, float* const* p, const float* const* g, floa
                             double b1, double b2, double eps, hipStream_t stream, const float* hp = nullptr,
                             const int* skip = nullptr);
 // activation-backward (act = ACT_RELU or ACT_TANH) + bias-gradient first pass, and a paired single-pass column
-// sum (ppo.hip)
+// sum (ppo_reduce.hip)
 size_t colsum_partial_rows(size_t rows, size_t cols);
-// (G W) times act'(X) (X > 0 for ReLU, 1 - X^2 for Tanh) and its per-workgroup column sums (ppo.hip
+// (G W) times act'(X) (X > 0 for ReLU, 1 - X^2 for Tanh) and its per-workgroup column sums (ppo_mlp.hip
 // dgrad_mask_*_kernel): the input gradient of a Linear layer fed by an activation, fused with that
 // activation's backward; N = 256
 hipError_t launch_dgrad_mask(const float* G, int ldg, int K, const float* W, int ldw, const float* X, int ldx, int B,

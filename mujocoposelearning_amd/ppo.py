@@ -34,7 +34,6 @@ from .ppo_ops import (FUSED_WIDTHS, Linear, _GaussLogpFn, _PPOLossFn, _SplitKLin
                       ppo_stats_size)
 
 FUSED_MLP = True      # rollout forward through the fused hs_mlp2_forward kernel where it applies
-FUSED_MLP_MAX_ROWS = None   # ... up to this many rows (None: any)
 FUSED_ROLLOUT = True  # whole rollouts as hs_rollout launches (policy inside the env kernel) where they apply
 
 
@@ -194,15 +193,14 @@ class ActorCritic(nn.Module):
 
     def _fused_mlp_ok(self, obs):
         """The fused hs_mlp2_forward_act kernel applies: packed equal pi / vf nets of two hidden layers of
-        the same width, 64, 128 or 256 (ReLU or Tanh: _packed_act), <= 512 inputs and <= 32 actions, fp32 rows with unit stride on a device, and at
-        most FUSED_MLP_MAX_ROWS rows (above, the library GEMM chain is faster)."""
+        the same width, 64, 128 or 256 (ReLU or Tanh: _packed_act), <= 512 inputs and <= 32 actions, fp32 rows
+        with unit stride on a device."""
         pk = getattr(self, "_packed", None)
         if pk is None or not FUSED_MLP or not obs.is_cuda:
             return False
         w1, _, mid, w3, _ = pk
         return (_fused_width(w1, mid) is not None and obs.shape[1] <= 512 and w3.shape[2] <= 32
-                and obs.dtype == torch.float32 and obs.stride(1) == 1
-                and (FUSED_MLP_MAX_ROWS is None or obs.shape[0] <= FUSED_MLP_MAX_ROWS))
+                and obs.dtype == torch.float32 and obs.stride(1) == 1)
 
     @torch.no_grad()
     def net_forward(self, obs, which):
@@ -217,7 +215,7 @@ class ActorCritic(nn.Module):
         w1, b1, mid, w3, b3 = pk
         H = w1.shape[1] // 2
         if self._fused_mlp_ok(obs):
-            # one fused MFMA launch (ppo.hip mlp2_fwd_kernel) instead of three GEMMs, reading the
+            # one fused MFMA launch (ppo_mlp.hip mlp2_fwd_kernel) instead of three GEMMs, reading the
             # nn.Linear weights as they are ([out][in]: the reduction index contiguous)
             net, head = (self.pi_net, self.action_net) if which == 0 else (self.vf_net, self.value_net)
             l1, l2 = self._hidden(net)
@@ -433,12 +431,18 @@ class PPO:
                 self._rollout_graph.replay()
             else:
                 self._rollout_body()
-        self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
         boot = b["boot"].view(-1).nonzero().squeeze(1)
         if boot.numel():                                        # deferred TimeLimit bootstrap
             b["rew"].view(-1)[boot] += self.gamma * pol.value(b["tobs"].view(T * N, -1)[boot])
-        self.num_timesteps += T * self.n_envs_global
-        last_v = pol.value(self.obs)
+        return self._finish_rollout()
+
+    def _finish_rollout(self):
+        """The end of collect_rollouts on either path: finished-episode returns, the timestep count,
+        the value of the last obs and GAE."""
+        b = self.buf
+        self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
+        self.num_timesteps += self.n_steps * self.n_envs_global
+        last_v = self.policy.value(self.obs)
         return gae(b["rew"], b["val"], b["start"], last_v, self.episode_start, self.gamma, self.gae_lambda)
 
     def _fused_rollout_args(self):
@@ -589,10 +593,7 @@ class PPO:
             self.ep_acc.masked_fill_(done, 0.0)
             self.obs = obs.float().clone()
             self.episode_start = done.float()
-        self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
-        self.num_timesteps += self.n_steps * self.n_envs_global
-        last_v = pol.value(self.obs)
-        return gae(b["rew"], b["val"], b["start"], last_v, self.episode_start, self.gamma, self.gae_lambda)
+        return self._finish_rollout()
 
     # -- multi-rank lockstep ---------------------------------------------------------------------
     def _comm_device(self):
@@ -740,29 +741,49 @@ class PPO:
     def train(self, adv, ret):
         """SB3 PPO.train: n_epochs passes over the rollout in minibatches; with target_kl, the first
         minibatch whose approx_kl exceeds 1.5 target_kl takes no optimizer step and ends the update
-        (its statistics are recorded, n_updates counts its epoch)."""
-        b = self.buf
-        T, N = self.n_steps, self.env.num_envs
-        M = T * N
+        (its statistics are recorded, n_updates counts its epoch).  The epoch loop is this one; a path
+        (CPU, device eager, device graphed) supplies one epoch's minibatches, the stop test after it
+        and the finish that turns its statistics into the logger entries."""
+        M = self.n_steps * self.env.num_envs
+        cuda = self.device.type == "cuda"
         self._update_hyperparameters()
-        if self.device.type == "cuda":
+        if not cuda:
+            run_epoch, stopped, finish = self._train_path_cpu(adv, ret)
+        else:
             # one stats block per train(): zeroed here (with the control words), filled by the loss
             # kernels, read once at the end
             self._blk.zero_()
-            if self.graphs and self._chunk is not None:
-                return self._train_graphed(adv, ret)
-            return self._train_device_eager(adv, ret)
-        obs = b["obs"].reshape(M, -1)
-        act = b["act"].reshape(M, -1)
-        old_logp, old_val = b["logp"].reshape(-1), b["val"].reshape(-1)
-        adv, ret = adv.reshape(-1), ret.reshape(-1)
-        st = [0.0] * (_lib.HS_PPO_STAT_KL + 2 * self.n_epochs)
-        st[_lib.HS_PPO_STAT_EXPLAINED_VARIANCE] = float(self._explained_variance(old_val, ret))
-        stop, entered = False, 0
+            graphed = self.graphs and self._chunk is not None
+            run_epoch = self._train_path_graphed(adv, ret) if graphed else self._train_path_eager(adv, ret)
+            stopped, finish = self._stopped, lambda entered: self._finish_device_train(entered, ret)
+        entered = 0
         for epoch in range(self.n_epochs):
             perm = torch.randperm(M, device=self.device)
             entered += 1
             self.n_updates += 1
+            run_epoch(epoch, perm)
+            if stopped():
+                break
+            if cuda:
+                self._ctl[_lib.HS_PPO_CTL_EPOCH].add_(1)
+        return finish(entered)
+
+    def _rollout_views(self, adv, ret):
+        """(obs, act, old_logp, adv, ret, old_val) of the rollout, flattened over [T, N]."""
+        b, M = self.buf, self.n_steps * self.env.num_envs
+        return (b["obs"].reshape(M, -1), b["act"].reshape(M, -1), b["logp"].reshape(-1), adv.reshape(-1),
+                ret.reshape(-1), b["val"].reshape(-1))
+
+    def _train_path_cpu(self, adv, ret):
+        """train() on the CPU (toy envs, tests): the torch restatement, its statistics in a host list
+        laid out as the stats block, the stop decision taken on the host before the optimizer step."""
+        obs, act, old_logp, adv, ret, old_val = self._rollout_views(adv, ret)
+        st = [0.0] * (_lib.HS_PPO_STAT_KL + 2 * self.n_epochs)
+        st[_lib.HS_PPO_STAT_EXPLAINED_VARIANCE] = float(self._explained_variance(old_val, ret))
+        stop = False
+
+        def run_epoch(epoch, perm):
+            nonlocal stop
             for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
                 self.grad_weight = self._mb_weight[j]
                 loss, pg, vf = self._minibatch_loss(obs, act, old_logp, adv, ret, perm[s:e], old_val)
@@ -783,12 +804,13 @@ class PPO:
                 st[_lib.HS_PPO_STAT_KL_LAST] = kl
                 if self.target_kl is not None and kl > 1.5 * self.target_kl:
                     stop = True                      # SB3: break before the optimizer step
-                    break
+                    return
                 self._clip_and_step()
-            if stop:
-                break
-        st[_lib.HS_PPO_STAT_STD] = float(self.policy.log_std.detach().exp().mean())
-        return self._train_stats(st, entered)
+
+        def finish(entered):
+            st[_lib.HS_PPO_STAT_STD] = float(self.policy.log_std.detach().exp().mean())
+            return self._train_stats(st, entered)
+        return run_epoch, lambda: stop, finish
 
     def _stopped(self):
         """The device stop word, read by the host once after an epoch (only with target_kl set)."""
@@ -801,20 +823,13 @@ class PPO:
         self._stats[_lib.HS_PPO_STAT_STD].copy_(self.policy.log_std.detach().exp().mean())
         return self._train_stats(self._stats.tolist(), entered)      # the one device -> host read
 
-    def _train_device_eager(self, adv, ret):
+    def _train_path_eager(self, adv, ret):
         """train() on a device without graphs (capture refused, or ragged minibatches): the same
         kernels and device predicates as the graphed update -- after the stop word is set the rest of
         that epoch's minibatches run and are discarded -- with the stop word read once per epoch."""
-        b = self.buf
-        M = self.n_steps * self.env.num_envs
-        obs, act = b["obs"].reshape(M, -1), b["act"].reshape(M, -1)
-        old_logp, old_val = b["logp"].reshape(-1), b["val"].reshape(-1)
-        adv, ret = adv.reshape(-1), ret.reshape(-1)
-        entered = 0
-        for epoch in range(self.n_epochs):
-            perm = torch.randperm(M, device=self.device)
-            entered += 1
-            self.n_updates += 1
+        obs, act, old_logp, adv, ret, old_val = self._rollout_views(adv, ret)
+
+        def run_epoch(epoch, perm):
             for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
                 self.grad_weight = self._mb_weight[j]
                 loss, pg, vf = self._minibatch_loss(obs, act, old_logp, adv, ret, perm[s:e], old_val)
@@ -824,10 +839,7 @@ class PPO:
                 if self._kl_sync:
                     ppo_kl_stop(kl, self._hp, self._stats, self.n_epochs, self._ctl)
                 self._clip_and_step()
-            if self._stopped():
-                break
-            self._ctl[_lib.HS_PPO_CTL_EPOCH].add_(1)
-        return self._finish_device_train(entered, ret)
+        return run_epoch
 
     def _clip_and_step(self):
         """clip_grad_norm_(max_grad_norm) + Adam step: hs_adam_clip_ex on a device (lr from the device
@@ -945,37 +957,32 @@ class PPO:
                             v.zero_()
                 self._blk.zero_()    # the warm-up's statistics and stop word: back to the start of train()
 
-    def _train_graphed(self, adv, ret):
+    def _train_path_graphed(self, adv, ret):
+        """train() on a device as graph replays (captured on first use): one replay per epoch with
+        world 1, else G1 / all-reduce / G2 per minibatch."""
         if self._graphs is None:
             self._build_graphs()
             if self._graphs is None:
-                return self._train_device_eager(adv, ret)       # capture failed: self.graphs is now False
+                return self._train_path_eager(adv, ret)         # capture failed: self.graphs is now False
         g1, g2 = self._graphs
-        M = self.n_steps * self.env.num_envs
         self._g_adv.copy_(adv.reshape(-1))
         self._g_ret.copy_(ret.reshape(-1))
-        entered = 0
         ge = getattr(self, "_epoch_graph", None)
-        for epoch in range(self.n_epochs):
-            perm = torch.randperm(M, device=self.device)
-            entered += 1
-            self.n_updates += 1
+
+        def run_epoch(epoch, perm):
             if ge is not None:                    # world 1: one replay per epoch
                 self._g_perm.copy_(perm)
                 ge.replay()
-            else:
-                for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
-                    self._g_idx.copy_(perm[s:e])
-                    if self.sync_grads:
-                        self._g_w.fill_(self._mb_weight[j])
-                    g1.replay()
-                    if self.sync_grads:
-                        self._allreduce_flat(self._g_flat)
-                    g2.replay()
-            if self._stopped():                   # target_kl only: one read of the stop word per epoch
-                break
-            self._ctl[_lib.HS_PPO_CTL_EPOCH].add_(1)
-        return self._finish_device_train(entered, ret)
+                return
+            for j, (s, e) in enumerate(zip(self._mb_bounds, self._mb_bounds[1:])):
+                self._g_idx.copy_(perm[s:e])
+                if self.sync_grads:
+                    self._g_w.fill_(self._mb_weight[j])
+                g1.replay()
+                if self.sync_grads:
+                    self._allreduce_flat(self._g_flat)
+                g2.replay()
+        return run_epoch
 
     WARN_KINDS = _batch_mod.WARN_KINDS
 

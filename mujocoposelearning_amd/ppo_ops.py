@@ -1,12 +1,12 @@
 """Device operators of the on-device PPO (ppo.py): thin torch wrappers over the HIP kernels of
-csrc/ppo.hip and csrc/gae.hip (through the C ABI, include/hsim.h) plus the autograd functions that
+csrc/ppo_*.hip and csrc/gae.hip (through the C ABI, include/hsim.h) plus the autograd functions that
 use them in the update.  Every operator here runs on a GPU only; ppo.py keeps the torch
 restatement for CPU tensors (toy envs, tests).
 
 * rollout: ppo_act (Gaussian sample + log-prob + clip + buffer writes), ppo_post (bootstrap,
   dones, returns, next obs), gae_device (GAE reverse scan)
 * update: _GaussLogpFn (log-prob fwd/bwd), _PPOLossFn / ppo_loss (clipped surrogate + value MSE
-  fwd/bwd), _PPOLossExFn / ppo_loss_ex / ppo_kl_stop (the same with device-resident hyperparameters,
+  fwd/bwd), ppo_loss_ex / ppo_kl_stop (the same node with device-resident hyperparameters,
   value clipping, SB3's train statistics and the target_kl stop word), _SplitKLinearFn / _SplitKLinearReLUFn / Linear / mlp_forward (split-K weight
   gradients, ReLU in the GEMM epilogue or an in-place Tanh), _MLPChainFn / mlp_head_forward (a whole
   net as one node: input gradient + activation backward + bias sum fused, hs_dgrad_act), colsum (deterministic column sums), adam_clip_step
@@ -20,7 +20,6 @@ import torch.nn as nn
 from ._lib import HS_ACT_RELU, HS_ACT_TANH
 
 _SPLITK_ROWS = 2048      # rows per split-K slice of a weight gradient
-SPLIT_K = True           # module switch (A/B probes)
 
 
 class _SplitKLinearFn(torch.autograd.Function):
@@ -87,10 +86,15 @@ class _GaussLogpFn(torch.autograd.Function):
 class _PPOLossFn(torch.autograd.Function):
     """SB3 PPO.train's minibatch policy/value loss (advantage normalisation, clipped surrogate,
     value MSE) over indices idx into the rollout arrays: one hs_ppo_loss launch forward, one
-    hs_ppo_loss_grad launch backward (dL/dlog_prob, dL/dvalues)."""
+    hs_ppo_loss_grad launch backward (dL/dlog_prob, dL/dvalues).  With the device controls ``ex`` =
+    (old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl, kl_out) it goes through
+    hs_ppo_loss_ex / hs_ppo_loss_grad_ex instead: clip_range and clip_range_vf come from the device
+    hyperparameter block ``hp`` (``clip`` is unused), and the forward's last launch also adds SB3's
+    train statistics of the minibatch to ``stats`` and takes the target_kl stop decision (``ctl``),
+    see include/hsim.h."""
 
     @staticmethod
-    def forward(ctx, logp, v, idx, adv, ret, old_logp, clip, normalize=True):
+    def forward(ctx, logp, v, idx, adv, ret, old_logp, clip, normalize, ex):
         from . import _lib
         logp, v = logp.contiguous(), v.contiguous()
         B = logp.shape[0]
@@ -98,19 +102,28 @@ class _PPOLossFn(torch.autograd.Function):
         L = _lib.lib()
         pg = torch.empty((), dtype=torch.float32, device=dev)
         vf = torch.empty((), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.hs_ppo_loss_workspace(B)), dtype=torch.float32, device=dev)
+        n_ws = L.hs_ppo_loss_workspace(B) if ex is None else L.hs_ppo_loss_workspace_ex(B)
+        ws = torch.empty(int(n_ws), dtype=torch.float32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.hs_ppo_loss(logp.data_ptr(), v.data_ptr(), idx.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                 old_logp.data_ptr(), B, float(clip), 1 if normalize else 0, pg.data_ptr(), vf.data_ptr(),
-                                 ws.data_ptr(), st))
-        ctx.save_for_backward(logp, v, ws)
+        data = (logp.data_ptr(), v.data_ptr(), idx.data_ptr(), adv.data_ptr(), ret.data_ptr(), old_logp.data_ptr())
+        out = (pg.data_ptr(), vf.data_ptr(), ws.data_ptr(), st)
+        if ex is None:
+            _lib.check(L.hs_ppo_loss(*data, B, float(clip), 1 if normalize else 0, *out))
+            ctx.save_for_backward(logp, v, ws)
+        else:
+            old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl, kl_out = ex
+            _lib.check(L.hs_ppo_loss_ex(*data, old_val.data_ptr(), B, 1 if normalize else 0, hp.data_ptr(),
+                                        log_std.data_ptr(), log_std.numel(), float(vf_coef), float(ent_coef),
+                                        stats.data_ptr(), int(n_epochs), ctl.data_ptr(),
+                                        None if kl_out is None else kl_out.data_ptr(), *out))
+            ctx.save_for_backward(logp, v, ws, hp)
         ctx.clip = float(clip)
         return pg, vf
 
     @staticmethod
     def backward(ctx, g_pg, g_vf):
         from . import _lib
-        logp, v, ws = ctx.saved_tensors
+        logp, v, ws, *hp = ctx.saved_tensors
         B = logp.shape[0]
         dev = logp.device
         z = torch.zeros((), dtype=torch.float32, device=dev)
@@ -118,11 +131,14 @@ class _PPOLossFn(torch.autograd.Function):
         g_vf = z if g_vf is None else g_vf.to(torch.float32).contiguous()
         g_logp = torch.empty(B, dtype=torch.float32, device=dev)
         g_v = torch.empty(B, dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib().hs_ppo_loss_grad(logp.data_ptr(), v.data_ptr(), B, ctx.clip, ws.data_ptr(),
-                                               g_pg.data_ptr(), g_vf.data_ptr(), g_logp.data_ptr(), g_v.data_ptr(),
-                                               st))
-        return g_logp, g_v, None, None, None, None, None, None
+        grads = (ws.data_ptr(), g_pg.data_ptr(), g_vf.data_ptr(), g_logp.data_ptr(), g_v.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+        L = _lib.lib()
+        if hp:
+            _lib.check(L.hs_ppo_loss_grad_ex(logp.data_ptr(), v.data_ptr(), B, hp[0].data_ptr(), *grads))
+        else:
+            _lib.check(L.hs_ppo_loss_grad(logp.data_ptr(), v.data_ptr(), B, ctx.clip, *grads))
+        return (g_logp, g_v) + (None,) * 7
 
 
 def ppo_loss(logp, v, idx, adv, ret, old_logp, clip, normalize=True):
@@ -131,51 +147,7 @@ def ppo_loss(logp, v, idx, adv, ret, old_logp, clip, normalize=True):
     for t in (adv, ret, old_logp):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1
     assert idx.dtype == torch.int64 and idx.is_contiguous()
-    return _PPOLossFn.apply(logp, v, idx, adv, ret, old_logp, clip, normalize)
-
-
-class _PPOLossExFn(torch.autograd.Function):
-    """_PPOLossFn through hs_ppo_loss_ex / hs_ppo_loss_grad_ex: clip_range and clip_range_vf come from the
-    device hyperparameter block ``hp``, and the forward's last launch also adds SB3's train statistics
-    of the minibatch to ``stats`` and takes the target_kl stop decision (``ctl``), see include/hsim.h."""
-
-    @staticmethod
-    def forward(ctx, logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl,
-                kl_out, normalize):
-        from . import _lib
-        logp, v = logp.contiguous(), v.contiguous()
-        B = logp.shape[0]
-        dev = logp.device
-        L = _lib.lib()
-        pg = torch.empty((), dtype=torch.float32, device=dev)
-        vf = torch.empty((), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.hs_ppo_loss_workspace_ex(B)), dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.hs_ppo_loss_ex(logp.data_ptr(), v.data_ptr(), idx.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                    old_logp.data_ptr(), old_val.data_ptr(), B, 1 if normalize else 0, hp.data_ptr(),
-                                    log_std.data_ptr(), log_std.numel(), float(vf_coef), float(ent_coef),
-                                    stats.data_ptr(), int(n_epochs), ctl.data_ptr(),
-                                    None if kl_out is None else kl_out.data_ptr(), pg.data_ptr(), vf.data_ptr(),
-                                    ws.data_ptr(), st))
-        ctx.save_for_backward(logp, v, ws, hp)
-        return pg, vf
-
-    @staticmethod
-    def backward(ctx, g_pg, g_vf):
-        from . import _lib
-        logp, v, ws, hp = ctx.saved_tensors
-        B = logp.shape[0]
-        dev = logp.device
-        z = torch.zeros((), dtype=torch.float32, device=dev)
-        g_pg = z if g_pg is None else g_pg.to(torch.float32).contiguous()
-        g_vf = z if g_vf is None else g_vf.to(torch.float32).contiguous()
-        g_logp = torch.empty(B, dtype=torch.float32, device=dev)
-        g_v = torch.empty(B, dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib().hs_ppo_loss_grad_ex(logp.data_ptr(), v.data_ptr(), B, hp.data_ptr(), ws.data_ptr(),
-                                                  g_pg.data_ptr(), g_vf.data_ptr(), g_logp.data_ptr(), g_v.data_ptr(),
-                                                  st))
-        return (g_logp, g_v) + (None,) * 14
+    return _PPOLossFn.apply(logp, v, idx, adv, ret, old_logp, clip, normalize, None)
 
 
 def ppo_stats_size(n_epochs):
@@ -198,8 +170,8 @@ def ppo_loss_ex(logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef,
     assert stats.is_contiguous() and stats.numel() >= ppo_stats_size(n_epochs)
     assert log_std.dtype == torch.float32 and log_std.is_contiguous() and log_std.numel() <= 32
     assert kl_out is None or (kl_out.dtype == torch.float32 and kl_out.numel() == 1)
-    return _PPOLossExFn.apply(logp, v, idx, adv, ret, old_logp, old_val, hp, log_std, vf_coef, ent_coef, stats,
-                              n_epochs, ctl, kl_out, normalize)
+    return _PPOLossFn.apply(logp, v, idx, adv, ret, old_logp, 0.0, normalize,
+                            (old_val, hp, log_std, vf_coef, ent_coef, stats, n_epochs, ctl, kl_out))
 
 
 def ppo_kl_stop(kl, hp, stats, n_epochs, ctl):
@@ -238,19 +210,15 @@ def adam_clip_step(opt, params, max_norm, workspace=None, hp=None, skip=None):
     arr = lambda xs: (C.c_void_p * nt)(*[x.data_ptr() for x in xs])   # noqa: E731
     sts = [opt.state[p] for p in params]
     b1, b2 = grp["betas"]
+    tensors = (nt, arr(params), arr([p.grad for p in params]), arr([s["exp_avg"] for s in sts]),
+               arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]),
+               (C.c_int64 * nt)(*[p.numel() for p in params]), workspace.data_ptr(), float(max_norm))
+    tail = (float(b1), float(b2), float(grp["eps"]), torch.cuda.current_stream(dev).cuda_stream)
     if hp is not None:
         assert hp.dtype == torch.float32 and skip.dtype == torch.int32
-        _lib.check(L.hs_adam_clip_ex(nt, arr(params), arr([p.grad for p in params]), arr([s["exp_avg"] for s in sts]),
-                                     arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]),
-                                     (C.c_int64 * nt)(*[p.numel() for p in params]), workspace.data_ptr(),
-                                     float(max_norm), hp.data_ptr(), skip.data_ptr(), float(b1), float(b2),
-                                     float(grp["eps"]), torch.cuda.current_stream(dev).cuda_stream))
-        return workspace
-    _lib.check(L.hs_adam_clip(nt, arr(params), arr([p.grad for p in params]), arr([s["exp_avg"] for s in sts]),
-                              arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]),
-                              (C.c_int64 * nt)(*[p.numel() for p in params]), workspace.data_ptr(),
-                              float(max_norm), float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
-                              torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(L.hs_adam_clip_ex(*tensors, hp.data_ptr(), skip.data_ptr(), *tail))
+    else:
+        _lib.check(L.hs_adam_clip(*tensors, float(grp["lr"]), *tail))
     return workspace
 
 
@@ -321,7 +289,7 @@ def colsum_pair(x0, x1):
 
 def colsum(x, row_weight=None):
     """Column sums of a contiguous [rows, cols] float32 device matrix through hs_colsum
-    (ppo.hip): deterministic, and 3-5x faster than torch's dim-0 reduction at the PPO update's
+    (ppo_reduce.hip): deterministic, and 3-5x faster than torch's dim-0 reduction at the PPO update's
     shapes ([32768, 256] bias gradients, [16, 90112] split-K finishes)."""
     from . import _lib
     assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32 and x.is_cuda
@@ -433,7 +401,7 @@ def mlp_head_forward(seq, head, x):
 
 def _splitk_rows(x):
     n = x.shape[0] if x.dim() == 2 else 0
-    if SPLIT_K and x.is_cuda and torch.is_grad_enabled() and n >= 2 * _SPLITK_ROWS and n % _SPLITK_ROWS == 0:
+    if x.is_cuda and torch.is_grad_enabled() and n >= 2 * _SPLITK_ROWS and n % _SPLITK_ROWS == 0:
         return n // _SPLITK_ROWS
     return 0
 
@@ -473,7 +441,7 @@ FUSED_WIDTHS = (64, 128, 256)   # hidden widths of the fused forwards (hs_mlp2_f
 
 def mlp2_forward(x, w1, b1, w2, b2, w3, b3, act=HS_ACT_RELU):
     """Fused forward of one 2-hidden-layer MLP of width H = w1.shape[0] (64, 128 or 256) with hidden
-    activation ``act`` (HS_ACT_RELU or HS_ACT_TANH) through hs_mlp2_forward_act (ppo.hip: MFMA tiles,
+    activation ``act`` (HS_ACT_RELU or HS_ACT_TANH) through hs_mlp2_forward_act (ppo_mlp.hip: MFMA tiles,
     one launch): x [N, D] (row stride >= D); w1 [H, D],
     w2 [H, H], w3 [A, H] in nn.Linear's [out][in] layout (unit column stride), b1 / b2 [H], b3 [A]
     contiguous; returns out [N, A] float32."""
@@ -507,7 +475,7 @@ def gae_device(rewards, values, dones, last_values, last_dones, gamma, lam):
 
 def ppo_act(mean, value, log_std, episode_start, seed, counter, deterministic, act_out, act_clip_out, logp_out,
             val_out, start_out, stream=None, counter_base=None):
-    """hs_ppo_act on device tensors (ppo.hip): Gaussian sample + log-prob + clip + buffer writes.
+    """hs_ppo_act on device tensors (ppo_rollout.hip): Gaussian sample + log-prob + clip + buffer writes.
     The Philox counter is ``counter`` plus, if given, the int64 device scalar ``counter_base``
     (read by the kernel, so a captured graph draws fresh noise on every replay)."""
     from . import _lib
@@ -526,7 +494,7 @@ def ppo_act(mean, value, log_std, episode_start, seed, counter, deterministic, a
 
 def ppo_post(reward, terminated, truncated, terminal_value, gamma, obs, obs_out, reward_out, done_out, ep_acc,
              ep_return_out, episode_start, terminal_obs=None, boot_obs_out=None, boot_out=None, stream=None):
-    """hs_ppo_post on device tensors (ppo.hip): reward bootstrap, dones, returns, next obs copy.
+    """hs_ppo_post on device tensors (ppo_rollout.hip): reward bootstrap, dones, returns, next obs copy.
     terminal_value None = deferred bootstrap: boot flags -> boot_out, terminal-obs rows of the
     boot envs -> boot_obs_out (the caller adds gamma V(row) at the end of the rollout)."""
     from . import _lib

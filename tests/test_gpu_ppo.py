@@ -1,4 +1,4 @@
-"""HIP PPO rollout kernels (ppo.hip: hs_ppo_act / hs_ppo_post) against the torch restatement of
+"""HIP PPO rollout kernels (ppo_rollout.hip: hs_ppo_act / hs_ppo_post) against the torch restatement of
 SB3 2.3.2 collect_rollouts' per-step semantics (ppo.PPO._collect_rollouts_torch), and the device
 rollout's buffers against the policy they were sampled from.  SB3 itself is not importable here,
 so parity with SB3 is unpinned; these pin the kernels to the torch path's formulas."""
@@ -398,11 +398,15 @@ def test_graphed_rollout_matches_eager_rollout(prec, n, steps, monkeypatch):
         e.close()
 
 
-@pytest.mark.parametrize("B", [32768, 777, 1])
-def test_fused_ppo_loss_matches_torch(B):
+@pytest.mark.parametrize("B,normalize", [
+    pytest.param(32768, True, id="32768"), pytest.param(777, True, id="777"), pytest.param(1, True, id="1"),
+    pytest.param(777, False, id="777-raw"), pytest.param(1, False, id="1-raw")])
+def test_fused_ppo_loss_matches_torch(B, normalize):
     """hs_ppo_loss / hs_ppo_loss_grad == the torch restatement of SB3 PPO.train's minibatch loss
     (PPO._minibatch_loss's CPU branch) and its autograd gradients, with ratios inside and outside
-    the clip range."""
+    the clip range; normalize=False (SB3's normalize_advantage=False) against the formula on the raw
+    advantages, at B = 1 (where no normalisation applies either way) and B = 777 (four blocks, the
+    last one partial)."""
     from mujocoposelearning_amd.ppo import ppo_loss
     g = torch.Generator(device="cuda").manual_seed(B)
     M, clip = 50000, 0.2
@@ -416,10 +420,10 @@ def test_fused_ppo_loss_matches_torch(B):
     for fused in (True, False):
         lp, v = lp0.clone().requires_grad_(), v0.clone().requires_grad_()
         if fused:
-            pg, vf = ppo_loss(lp, v, idx, adv, ret, old, clip)
+            pg, vf = ppo_loss(lp, v, idx, adv, ret, old, clip, normalize)
         else:
             a = adv[idx]
-            if B > 1:
+            if B > 1 and normalize:
                 a = (a - a.mean()) / (a.std() + 1e-8)
             r = torch.exp(lp - old[idx])
             pg = -torch.min(a * r, a * r.clamp(1 - clip, 1 + clip)).mean()
@@ -490,7 +494,7 @@ def test_relu_grad_colsum_and_pair():
 @pytest.mark.parametrize("B,K", [(32768, 256), (10000, 256), (4096, 256), (100, 256), (37, 21), (32768, 21),
                                  (4096, 1), (5, 1)])
 def test_dgrad_mask_matches_torch(B, K):
-    """hs_dgrad_mask (ppo.hip dgrad_mask_*: the input gradient of a Linear fed by a ReLU, masked,
+    """hs_dgrad_mask (ppo_mlp.hip dgrad_mask_*: the input gradient of a Linear fed by a ReLU, masked,
     with per-row-block column sums) == (g @ w) * (x > 0) and its fp64 column sums, fp32 tolerance:
     the MFMA instance with one / two / four row blocks (4096 / 10000 / 32768 rows), a partial last
     tile (100, 10000), the
@@ -634,7 +638,7 @@ def test_ppo_deep_net_arch_trains_on_gpu():
 
 @pytest.mark.parametrize("N,D", [(4096, 352), (1000, 350), (33, 7), (257, 100), (20000, 352), (9001, 350)])
 def test_fused_mlp_forward_matches_gemm_chain(N, D):
-    """hs_mlp2_forward (ppo.hip mlp2_fwd_kernel: MFMA f32 tiles, one launch, the nn.Linear weights
+    """hs_mlp2_forward (ppo_mlp.hip mlp2_fwd_kernel: MFMA f32 tiles, one launch, the nn.Linear weights
     read in place) == the packed GEMM chain of ActorCritic.net_forward (torch fp32) for the pi mean
     and the vf value, within 1e-4 relative; odd row counts and input widths: the 16-row tile, a
     partial last k-group (350, 7, 100), element loads for rows that are not 16-byte aligned (350, 7)

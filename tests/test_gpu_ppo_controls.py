@@ -42,14 +42,16 @@ def _loss_inputs(B, zero_d=False):
     return adv, ret, old, idx, lp0, v0, old_val
 
 
-@pytest.mark.parametrize("vclip", [False, True], ids=["vclip-off", "vclip-on"])
+@pytest.mark.parametrize("vclip,normalize", [(False, True), (True, True), (False, False), (True, False)],
+                         ids=["vclip-off", "vclip-on", "vclip-off-raw", "vclip-on-raw"])
 @pytest.mark.parametrize("B", [1, 257, 16385])
-def test_loss_ex_matches_torch(B, vclip):
+def test_loss_ex_matches_torch(B, vclip, normalize):
     """B = 1 (one thread), 257 (a ragged second block), 16385 (65 blocks: one past the 64-lane stride of the
     partial sums).  Losses and gradients at test_fused_ppo_loss_matches_torch's tolerances against the fp32
     torch restatement, approx_kl at 1e-5 relative, the clip count against an fp64 reference up to the samples
     within 1e-6 of the clip boundary; without value clipping pg, vf and both gradients are bitwise
-    hs_ppo_loss's."""
+    hs_ppo_loss's.  normalize=False (the -raw cases, SB3's normalize_advantage=False): the same against the
+    formula on the raw advantages."""
     from mujocoposelearning_amd import _lib
     from mujocoposelearning_amd.ppo_ops import ppo_loss, ppo_loss_ex
     clip, cvf = 0.2, 0.3
@@ -59,12 +61,13 @@ def test_loss_ex_matches_torch(B, vclip):
     for kind in ("ex", "torch", "legacy"):
         lp, v = lp0.clone().requires_grad_(), v0.clone().requires_grad_()
         if kind == "ex":
-            pg, vf = ppo_loss_ex(lp, v, idx, adv, ret, old, old_val, hp, log_std, VF_COEF, ENT_COEF, stats, N_EPOCHS, ctl)
+            pg, vf = ppo_loss_ex(lp, v, idx, adv, ret, old, old_val, hp, log_std, VF_COEF, ENT_COEF, stats, N_EPOCHS, ctl,
+                                 normalize=normalize)
         elif kind == "legacy":
-            pg, vf = ppo_loss(lp, v, idx, adv, ret, old, clip)
+            pg, vf = ppo_loss(lp, v, idx, adv, ret, old, clip, normalize)
         else:
             a = adv[idx]
-            if B > 1:
+            if B > 1 and normalize:
                 a = (a - a.mean()) / (a.std() + 1e-8)
             d = lp - old[idx]
             r = torch.exp(d)

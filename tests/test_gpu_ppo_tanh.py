@@ -1,5 +1,5 @@
 """The PPO update's fused backward kernels with the Tanh activation (HS_ACT_TANH): hs_dgrad_act
-(ppo.hip dgrad_mask_*_kernel<.., ACT>: input gradient times 1 - x^2 with the bias sum's first pass),
+(ppo_mlp.hip dgrad_mask_*_kernel<.., ACT>: input gradient times 1 - x^2 with the bias sum's first pass),
 hs_act_grad_colsum (relu_colsum_kernel<ACT>) and the autograd nodes built on them (_MLPChainFn,
 _SplitKLinearReLUFn), against float64 formulas and plain torch autograd at the bars of their ReLU
 counterparts in tests/test_gpu_ppo.py."""

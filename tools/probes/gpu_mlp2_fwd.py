@@ -1,10 +1,10 @@
-"""Timing of the fused policy-MLP forward (ppo.hip mlp2_fwd_kernel) against the torch GEMM chain
+"""Timing of the fused policy-MLP forward (ppo_mlp.hip mlp2_fwd_kernel) against the torch GEMM chain
 (addmm + ReLU epilogues; with --activation Tanh, addmm + an in-place tanh) at the rollout's two shapes: the pi net per env step (4096 rows) and the
 vf net over a rollout buffer (32 x 4096 rows).  HIP events on the current stream; FLOP/s counts the
 three layers' 2 N (D H + H H + H A) multiply-adds.
     python tools/probes/gpu_mlp2_fwd.py [--activation ReLU|Tanh]
 (profiles/r5i/mlp2_probe_rb{1,2}.log were taken with a build that let HSIM_MLP_RB force the row
-blocks per wave; the launcher now picks them by row count, ppo.hip MLP_RB2_ROWS)"""
+blocks per wave; the launcher now picks them by row count, ppo_mlp.hip MLP_RB2_ROWS)"""
 import argparse
 import json
 import os
