@@ -1,7 +1,7 @@
 // Hidden-layer activation of the policy nets (product): ReLU or Tanh, the two an SB3 MlpPolicy is
 // built with (activation_fn = nn.ReLU in the reference's config, nn.Tanh by SB3's default).  Shared
 // by the fused MLP forward / backward kernels (ppo_mlp.hip, ppo_reduce.hip) and the fused rollout's in-kernel pi net
-// (hs_env_step.h policy_mean_body), so every path evaluates bitwise the same tanh.
+// (hs_policy.h policy_mean_body), so every path evaluates bitwise the same tanh.
 #pragma once
 #include <hip/hip_runtime.h>
 

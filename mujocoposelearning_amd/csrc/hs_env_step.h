@@ -1,14 +1,15 @@
-// The env layer around mj_step: bad-state checks and reset (custom_env.py:97-150), the reward
-// plug-ins (reward_functions.py:66-261), the 352-dim obs (custom_env.py:232-261), the fused
-// rollout's policy forward, the per-env commit, and step_pair -- one env step (custom_env.py:152-230)
-// of a wave's env pair, which every step kernel inlines once.
+// The env layer around mj_step: bad-state checks and reset (custom_env.py:97-150), the 352-dim obs
+// (custom_env.py:232-261), the per-env commit, and step_pair -- one env step (custom_env.py:152-230)
+// of a wave's env pair, which every step kernel inlines once -- with the phases it calls.  The reward
+// plug-ins are in hs_reward.h, the fused rollout's policy forward in hs_policy.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hs_act.h"
 #include "hs_philox.h"
 #include "hs_stepper.h"
+#include "hs_reward.h"
+#include "hs_policy.h"
 
 namespace hs {
 namespace {
@@ -82,144 +83,6 @@ __device__ __forceinline__ void physics_step(Stepper<T, NV, C>& st, KPtr<T> k, T
   xws = st.qacc;
 }
 
-// sum |cfrc_ext| of the last two bodies ("feet", reward_functions.py:121-122,176-177)
-template <typename T, typename C>
-__device__ __forceinline__ void foot_forces(MPtr<T> m, const Scratch<T, C>& s, T& lf, T& rf) {
-  const int nb = m->nbody;
-  lf = 0;
-  rf = 0;
-  for (int k = 0; k < 6; k++) { lf += fabs(s.u.n.cfrc[nb - 2][k]); rf += fabs(s.u.n.cfrc[nb - 1][k]); }
-}
-
-// The reward plug-ins' inputs, gathered per env.  The step kernel fills them from its scratch
-// (compute_reward below); hs_reward_eval (reward_eval_kernel) from caller-supplied fields.  Both run
-// the same reward_formula, so the device formulas are pinned directly by the reference's golden vectors.
-template <typename T>
-struct RewardIn {
-  T h, qw, qx, qy, qz;   // qpos[2], qpos[3:7]
-  T vx;                  // qvel[0]
-  T time;
-  T com0, com1;          // subtree_com[0][0:2]
-  T comv;                // sum(subtree_linvel[0]^2), numpy order (sequential: 3 < 8 terms)
-  T lf, rf;              // sum |cfrc_ext[-2]|, sum |cfrc_ext[-1]| (numpy order: sequential over 6)
-  T energy;              // sum((qfrc_actuator[-nj:] * qvel[6:])^2), numpy's pairwise order (np_sum_half)
-  T ctrl_sq;             // sum(ctrl^2), numpy's pairwise order
-};
-
-// reward_functions.py:66-261 + utils.py:3-21, each expression in the reference's own association
-// and without FMA contraction, so the only difference to numpy is the device libm (exp / atan2 / asin).
-// The reference's Python min(a, b) is `b if b < a else a` (a NaN first operand is returned as is).
-template <typename T, typename KP>
-__device__ __forceinline__ T reward_formula(int reward_id, KP kn, const RewardIn<T>& in) {
-#pragma clang fp contract(off)
-  const T w = in.qw, x = in.qx, y = in.qy, z = in.qz;
-  const T roll = atan2(T(2) * (w * x + y * z), T(1) - T(2) * (x * x + y * y));
-  const T pitch = asin(T(2) * (w * y - z * x));   // not clamped: |sinp| > 1 -> NaN, as np.arcsin
-  const T h = in.h;
-  auto pymin = [](T a, T b) { return b < a ? b : a; };
-  if (reward_id == REWARD_STAND || reward_id == REWARD_WALK) {
-    const T hd = h - T(1.282);
-    const T height_reward = exp(T(-2.0) * (hd * hd));
-    const T orientation_reward = exp(T(-3.0) * (roll * roll + pitch * pitch));
-    const T posture = T(0.5) * height_reward + T(0.5) * orientation_reward;
-    const T torque = exp(T(-0.05) * in.ctrl_sq);
-    if (reward_id == REWARD_STAND) {                       // :156-211
-      if (h < T(0.8)) return T(0);
-      const T vd = in.vx - T(1.0);
-      const T vr = exp(T(-2.0) * (vd * vd));
-      const T total = in.lf + in.rf + T(1e-8);
-      const T foot = T(1.0) - pymin(in.lf, in.rf) / total;
-      return T(0.4) * vr + T(0.3) * posture + T(0.2) * foot + T(0.1) * torque;
-    }
-    if (h < T(0.8)) return T(0.1) * h / T(0.8);           // :213-261
-    const T vd = in.vx - T(10.0);
-    const T vr = exp(T(-0.5) * (vd * vd));
-    return vr + posture * torque;
-  }
-  if (reward_id == REWARD_KNEELING) {                      // :66-154
-    // kn: target_height, min_height, max_roll_pitch, com_radius, energy_w, posture_w, com_w, foot_w, alive_w
-    if (h < T(kn[1])) return h * h;
-    const T mrp = T(kn[2]);
-    const T orientation_error = (roll * roll + pitch * pitch) / (mrp * mrp);
-    const T posture_reward = exp(T(-5.0) * orientation_error);
-    const T hd = h - T(kn[0]);
-    const T height_reward = exp(T(-5.0) * (hd * hd));
-    const T posture = T(0.7) * posture_reward + T(0.3) * height_reward;
-    const T dist = sqrt(in.com0 * in.com0 + in.com1 * in.com1);
-    const T com = T(0.7) * exp(T(-10.0) * (dist / T(kn[3]))) + T(0.3) * exp(T(-0.1) * in.comv);
-    const T total = in.lf + in.rf + T(1e-8);
-    const T foot = pymin(in.lf, in.rf) / total;
-    const T energy = exp(T(-0.01) * in.energy);
-    const T alive = T(1.0) - exp(T(-0.5) * in.time);
-    return T(kn[5]) * posture + T(kn[6]) * com + T(kn[7]) * foot + T(kn[4]) * energy + T(kn[8]) * alive;
-  }
-  return T(0);
-}
-
-// the step kernel's reward: inputs from the env's scratch.  cfrc_ext and subtree_linvel are never
-// computed by mj_step without sensors (lazy), so the reference's reward reads zeros for them; with
-// full_state, the real wrenches / velocity of post_constraint.
-template <typename T, typename C>
-__device__ __forceinline__ T compute_reward(MPtr<T> m, const Scratch<T, C>& s, KPtr<T> k, T time,
-                                            T energy_sum, T ctrl_sq) {
-  RewardIn<T> in;
-  in.h = s.qpos[2];
-  in.qw = s.qpos[3];
-  in.qx = s.qpos[4];
-  in.qy = s.qpos[5];
-  in.qz = s.qpos[6];
-  in.vx = s.qvel[0];
-  in.time = time;
-  in.com0 = s.com[0];
-  in.com1 = s.com[1];
-  in.comv = T(0);
-  in.lf = T(0);
-  in.rf = T(0);
-  if (k->p.full_state) {
-#pragma clang fp contract(off)
-    for (int q = 0; q < 3; q++) in.comv += s.u.n.linv[0][q] * s.u.n.linv[0][q];
-    foot_forces(m, s, in.lf, in.rf);
-  }
-  in.energy = energy_sum;
-  in.ctrl_sq = ctrl_sq;
-  return reward_formula(k->p.reward_id, k->p.kneel, in);
-}
-
-// np.sum's order (numpy pairwise_sum, n <= 128) over the values x_i held by sub-lanes off + i,
-// i < n, of each 32-lane half: n < 8 -> ((0 + x0) + x1) + ...; else eight accumulators r_j = x_j +
-// x_{j+8} + ... over the whole blocks of 8, combined ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)),
-// then the rest added in order.  The block stage and the tree are DPP (row_ror:8, permlane16 swap,
-// the quad / half-mirror steps of hsum); the tail is a few lane reads.  off + n <= 32; the result is
-// in every lane of the half.  (hsum's butterfly order differs from numpy's by an ulp of the sum,
-// which the exp() of a reward term can amplify to several ulp of the reward.)
-template <typename T>
-__device__ __forceinline__ T np_sum_half(T v, int off, int n, int lane) {
-#pragma clang fp contract(off)
-  const int base = (lane & HL) + off;
-  auto at = [&](int i) { return __shfl(v, base + i, WAVE); };
-  T res;
-  int i;
-  if (n < 8) {
-    res = T(0);
-    i = 0;
-  } else {
-    T x = off == 0 ? v : __shfl(v, base + (lane & (HL - 1)), WAVE);   // x_j on sub-lane j
-    const int nb = n - n % 8;
-    T r = x;
-    const T x8 = dpp<0x128>(x);                           // row_ror:8 -> x_{j+8} on sub-lanes 0..7
-    if (nb >= 16) r += x8;
-    if (nb >= 24) { const T t = x; r += up_row(t); }       // x_{j+16}
-    if (nb >= 32) r += up_row(x8);                         // x_{j+24}
-    r += dpp<0xB1>(r);                                     // r0 + r1, r2 + r3, ...
-    r += dpp<0x4E>(r);                                     // (r0 + r1) + (r2 + r3), ...
-    r += dpp<0x141>(r);                                    // ... + ((r4 + r5) + (r6 + r7)) on sub-lane 0
-    res = bcast<0>(r);
-    i = nb;
-  }
-  for (; i < n; i++) res += at(i);
-  return res;
-}
-
 // custom_env.py:232-261 layout; qfrc_actuator comes from registers (sub-lane i holds dof i)
 // UC: the row lies in uncached memory and is rewritten every env step (the fused evaluation's staging
 // row): agent-scope stores, as the hand-off rows (row_st)
@@ -244,117 +107,6 @@ __device__ __forceinline__ void write_obs(MPtr<T> m, const Scratch<T, C>& s, int
   const int o5 = o4 + nv, nf = 6 * (m->nbody - 1);
   if (obs_dim >= o5 + nf)    // full_state: + cfrc_ext[1:] (custom_env.py:247,255, commented out there)
     for (int k = sl; k < nf; k += HL) put(o5 + k, (O)s.u.n.cfrc[1 + k / 6][k % 6]);
-}
-
-// Fused rollout: the SB3 MlpPolicy's pi net (mlp_extractor.policy_net + action_net, fp32 as SB3's
-// policy) on the wave's two envs at once (the lower half-wave's env and the upper's; a ghost half
-// mirrors its partner).  Two hidden layers of H = 64 R (R = 1, 2, 4: RolloutArgs::H = 64, 128, 256) with
-// the activation ACT (RolloutArgs::hact: ReLU or Tanh, hs_act.h -- the function of mlp2_fwd_kernel):
-// lane L (of 64) owns outputs R L .. R L + R - 1 for BOTH envs, so each input costs one 4 R-byte weight
-// load per lane (coalesced: the wave reads each weight row once) and two LDS broadcasts (the two envs'
-// inputs).  Every output sums its inputs in ascending index, whatever R.  The head: sub-lane sl < A of
-// each half owns action sl of its half's env.  The obs rows and hidden activations are staged in each
-// half's scratch union (free after the env step; x[512] / h[256] hold every width).  Returns the action
-// mean of (this half's env, sub-lane sl), 0 for sl >= A.
-// unroll of the hidden layers' loads (groups of 4 rows) and of the head's: measured 1 / 2 / 4 / 8 in
-// profiles/ab/ab_r4u_policy_unroll.log (4 and 8 tie), a rolling 16-row ring in ab_r4ae_policy_ring.log
-// -- at H = 256 only; the narrower nets (latency-bound: a 256- or 512-byte row per wave) keep them
-constexpr int kPolUnroll = 4, kPolHeadUnroll = 16;
-// R consecutive floats as one load of 4 R bytes (p is 4 R-byte aligned)
-template <int R>
-__device__ __forceinline__ void pol_load(const float* p, float (&u)[R]) {
-  static_assert(R == 1 || R == 2 || R == 4, "hidden width 64, 128 or 256");
-  if constexpr (R == 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
-  } else if constexpr (R == 2) {
-    const float2 v = *reinterpret_cast<const float2*>(p);
-    u[0] = v.x; u[1] = v.y;
-  } else {
-    u[0] = p[0];
-  }
-}
-// UC: the obs row is the fused evaluation's staging row (uncached memory, rewritten every env step): read
-// at agent scope, as the hand-off rows (row_ld)
-template <int R, int ACT, bool UC = false, typename T, typename C>
-__device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  constexpr int H = 64 * R;
-  const bool up = lane >= HL;
-  const int sl = lane & (HL - 1);
-  float* xa = smem[0].u.pol.x;   // lower half's env
-  float* xb = smem[1].u.pol.x;   // upper half's env
-  float* ha = smem[0].u.pol.h;
-  float* hb = smem[1].u.pol.h;
-  const int D = k->ro.D, A = k->ro.A, ld1 = k->ro.ld1;
-  float* xo = up ? xb : xa;
-  if constexpr (UC) {
-    for (int i = sl; i < D; i += HL) xo[i] = row_ld(obs + i);
-  } else {
-    for (int i = sl; i < D; i += HL) xo[i] = obs[i];
-  }
-  WSYNC();
-  auto layer = [&](const float* w, int ld, const float* b, const float* ina, const float* inb, int n, float* outa,
-                   float* outb) {
-    float a[R], c[R];
-    pol_load<R>(b + R * lane, a);
-#pragma unroll
-    for (int j = 0; j < R; j++) c[j] = a[j];
-    const float* wl = w + R * lane;
-#pragma unroll kPolUnroll
-    for (int i = 0; i < n; i += 4) {
-      const float4 va = *reinterpret_cast<const float4*>(ina + i);
-      const float4 vb = *reinterpret_cast<const float4*>(inb + i);
-      const float xs[4] = {va.x, va.y, va.z, va.w}, ys[4] = {vb.x, vb.y, vb.z, vb.w};
-#pragma unroll
-      for (int ii = 0; ii < 4; ii++) {
-        float u[R];
-        pol_load<R>(wl + (size_t)(i + ii) * ld, u);
-#pragma unroll
-        for (int j = 0; j < R; j++) a[j] += xs[ii] * u[j];
-#pragma unroll
-        for (int j = 0; j < R; j++) c[j] += ys[ii] * u[j];
-      }
-    }
-    WSYNC();   // every lane has read the inputs (the outputs may alias them)
-#pragma unroll
-    for (int j = 0; j < R; j++) {
-      outa[R * lane + j] = hs_act<ACT>(a[j]);
-      outb[R * lane + j] = hs_act<ACT>(c[j]);
-    }
-    WSYNC();
-  };
-  layer(k->ro.w1, ld1, k->ro.b1, xa, xb, D, ha, hb);        // obs -> h1
-  layer(k->ro.w2, H, k->ro.b2, ha, hb, H, xa, xb);          // h1 -> h2 (into the obs slots)
-  float mean = 0.f;
-  if (sl < A) {
-    mean = k->ro.b3[sl];
-    const float* w3 = k->ro.w3 + sl;
-#pragma unroll kPolHeadUnroll
-    for (int i = 0; i < H; i++) mean += xo[i] * w3[(size_t)i * A];
-  }
-  return mean;
-}
-// The narrow instances are calls, not inlined: inlined beside the 256 ones they cost the rollout kernel
-// registers (4 AGPRs more, profiles/rollout_widths.md), and a call per env step is noise next to the step.
-// The two 256-wide bodies (ReLU and Tanh) are inlined: together they leave every figure of the kernel
-// where it was, and as a call the Tanh one ran the rollout 5 % slower (profiles/tanh_policy.md).
-template <int R, int ACT, bool UC = false, typename T, typename C>
-__device__ __noinline__ float policy_mean_call(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  return policy_mean_body<R, ACT, UC>(k, obs, smem, lane);
-}
-// one wave-uniform dispatch on the hidden width and the activation (hs_rollout_act admits 64, 128 and 256,
-// ReLU and Tanh only)
-template <bool UC = false, typename T, typename C>
-__device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  const int H = k->ro.H;
-  if (k->ro.hact == ACT_TANH) {
-    if (H == 256) return policy_mean_body<4, ACT_TANH, UC>(k, obs, smem, lane);
-    if (H == 128) return policy_mean_call<2, ACT_TANH, UC>(k, obs, smem, lane);
-    return policy_mean_call<1, ACT_TANH, UC>(k, obs, smem, lane);
-  }
-  if (H == 256) return policy_mean_body<4, ACT_RELU, UC>(k, obs, smem, lane);
-  if (H == 128) return policy_mean_call<2, ACT_RELU, UC>(k, obs, smem, lane);
-  return policy_mean_call<1, ACT_RELU, UC>(k, obs, smem, lane);
 }
 
 template <typename T, int NV, typename C>
@@ -440,11 +192,27 @@ __device__ __forceinline__ bool resets_next(KPtr<T> k, MPtr<T> m, T time, int st
   return k->p.autoreset && ((double)(time + (T)k->p.nsub * m->timestep) >= k->p.duration ||
                             step_count + 1 >= k->p.max_steps);
 }
-// One env step (or reset / raw physics call) of the env pair (index, index + 1) of one wave.
-// `list` (wide tier): indices map to env ids through it; resident tier: indices are env ids.
-// In the resident tier an env whose contacts / rows overflowed the resident capacity in any
-// substep is NOT committed: it is appended to the wide tier's work list instead, and the wide
-// launch that follows re-runs its whole step from the same (untouched) inputs.
+
+// ---- step_pair's phases, in the order it runs them.  Each is inlined into its one caller; `sl` is the
+// lane's sub-lane of its half, `env` / `env_id` the env its half steps.
+
+// load from batch: the env's state as the previous launch committed it
+template <bool EVAL, typename T, typename C>
+__device__ __forceinline__ void load_batch_state(KPtr<T> ka, Scratch<T, C>& s, int sl, int nq, int nv, int env_id,
+                                                 bool rollout, T& time, T& xws, int& step_count, uint32_t& episode,
+                                                 T& total, double& epacc) {
+  time = ka->b.time[env_id];
+  xws = (sl < nv) ? ka->b.qacc_ws[(size_t)env_id * nv + sl] : T(0);
+  if (sl < nq) s.qpos[sl] = ka->b.qpos[(size_t)env_id * nq + sl];
+  if (sl + HL < nq) s.qpos[sl + HL] = ka->b.qpos[(size_t)env_id * nq + sl + HL];
+  if (sl < nv) s.qvel[sl] = ka->b.qvel[(size_t)env_id * nv + sl];
+  step_count = ka->b.step_count[env_id];
+  episode = ka->b.episode[env_id];
+  total = ka->b.total_reward[env_id];
+  if constexpr (!EVAL)
+    if (rollout) epacc = ka->ro.ep_acc[env_id];
+}
+
 // Queued schedule (launch_step sets p.queue when the pairs outnumber the resident waves): the
 // pair's substeps [s0, s1) only.  A chunk that ends before the last substep hands the state over
 // through b.mid and sets the pair's flag := this launch's tag; the last-substep chunk waits for the
@@ -454,6 +222,351 @@ __device__ __forceinline__ bool resets_next(KPtr<T> k, MPtr<T> m, T time, int st
 // write-back on either side.  Every chunk recomputes the whole mj_step pipeline from (qpos, qvel,
 // qacc_warmstart, time), so the hand-off is exact: results are bitwise those of one wave running all
 // substeps.
+
+// load from hand-off row: wait for the pair's previous chunk (or tape step) to hand the state over, then
+// read the row.  false: the tape launch aborted, the caller leaves (results discarded: the host replays).
+template <bool EVAL, typename T, typename C>
+__device__ __forceinline__ bool load_handoff_state(KPtr<T> ka, Scratch<T, C>& s, int lane, int nq, int nv, int nu,
+                                                   int env_id, int pair, int wait_tag, int tstep, bool rollout,
+                                                   T& time, T& xws, int& step_count, uint32_t& episode, T& total,
+                                                   int (&warn)[NWARN], T& act_row, double& epacc) {
+  const int sl = lane & (HL - 1);
+  int* flag = ka->b.qsync + QS_FLAG + pair;
+  int seen = 0, abort = 0;
+  if (lane == 0) {   // bounded (~0.5 s): a broken hand-off must not hang the GPU
+    int w = 0;
+    if (pair + 1 != ka->p.dbg_lose_pair1)   // test hook: treat this unit's hand-off as lost
+      while ((seen = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != wait_tag &&
+             ++w < (1 << 22)) {
+        // a tape launch that aborted (overflow) never hands this pair over: leave at once
+        if (tstep > 0 && (abort = __hip_atomic_load(ka->b.qsync + QS_ABORT, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT)) != 0)
+          break;
+        __builtin_amdgcn_s_sleep(2);
+      }
+  }
+  if (__builtin_amdgcn_readfirstlane(abort) != 0) return false;
+  const bool lost = __builtin_amdgcn_readfirstlane(seen) != wait_tag;
+  WSYNC();   // (compiler order: the row loads stay behind the poll)
+  const T* r = ka->b.mid + (size_t)env_id * MIDDIM;
+  time = row_ld(r + MID_TIME);
+  xws = (sl < nv) ? row_ld(r + MID_WS + sl) : T(0);
+  if (sl < nq) s.qpos[sl] = row_ld(r + MID_Q + sl);
+  if (sl + HL < nq) s.qpos[sl + HL] = row_ld(r + MID_Q + sl + HL);
+  if (sl < nv) s.qvel[sl] = row_ld(r + MID_V + sl);
+#pragma unroll
+  for (int w = 0; w < NWARN; w++) warn[w] = (int)row_ld(r + MID_W + w);
+  step_count = (int)row_ld(r + MID_SC);
+  episode = (uint32_t)row_ld(r + MID_EP);
+  total = row_ld(r + MID_TOT);
+  if (rollout) {
+    if (sl < nu) act_row = row_ld(r + MID_ACT + sl);
+    if constexpr (!EVAL) epacc = (double)row_ld(r + MID_EPACC);
+  }
+  // never seen in practice; if it were, the state is poisoned so that the substep's mj_checkPos
+  // resets the env (mj_resetData, ctrl 0 for that substep) -- counted in its own slot,
+  // HS_WARN_HANDOFF, not as a bad state (the -1 cancels the HS_WARN_BADQPOS count the poisoned
+  // qpos draws); the trainer raises on it: loud, never silent
+  if (lost) {
+    warn[WARN_HANDOFF]++;
+    warn[WARN_BADQPOS]--;
+    if (sl == 2) s.qpos[2] = T(NAN);
+  }
+  return true;
+}
+
+// store hand-off row: the state and the warning counters accumulated so far, for the pair's next chunk
+// (or next tape step).  The caller publishes it (publish, below).
+template <typename T, typename C>
+__device__ __forceinline__ void store_handoff_state(KPtr<T> k, const Scratch<T, C>& s, int sl, int nq, int nv, int env,
+                                                    T time, T xws, int step_count, uint32_t episode, T total,
+                                                    const int* warn) {
+  T* r = k->b.mid + (size_t)env * MIDDIM;
+  if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
+  if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
+  if (sl < nv) { row_st(r + MID_V + sl, s.qvel[sl]); row_st(r + MID_WS + sl, xws); }
+  if (sl == 0) {
+    row_st(r + MID_TIME, time);
+#pragma unroll
+    for (int w = 0; w < NWARN; w++) row_st(r + MID_W + w, (T)warn[w]);
+    row_st(r + MID_SC, (T)step_count);
+    row_st(r + MID_EP, (T)episode);
+    row_st(r + MID_TOT, total);
+  }
+}
+
+// a word of b.qsync (a pair's flag, the abort word) := value, once every store this wave issued (its
+// hand-off rows) is in memory
+__device__ __forceinline__ void publish(int* word, int value, int lane) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0) __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// this env step's output rows: the tape's slice tstep, or the batch's own buffers (null: an
+// intermediate step of a tape launch without per-step outputs writes none)
+template <typename T>
+__device__ __forceinline__ T* step_obs_row(KPtr<T> k, int env, int obs_dim, int tstep, bool tape_final) {
+  if (k->tape.obs) return k->tape.obs + ((size_t)tstep * k->nenv + env) * obs_dim;
+  return tape_final ? k->b.obs + (size_t)env * obs_dim : nullptr;
+}
+// fused rollout: the rollout buffer's obs row of step g + 1 (the obs this step returns)
+template <typename T>
+__device__ __forceinline__ float* ro_next_obs(KPtr<T> k, int env, int tstep) {
+  const int g = k->ro.t_begin + tstep;
+  return g + 1 < k->ro.t_total ? k->ro.obs + ((size_t)(g + 1) * k->nenv + env) * k->ro.D
+                               : k->ro.obs_last + (size_t)env * k->ro.D;
+}
+
+// fused rollout: SB3 collect_rollouts' bookkeeping of this step (ppo_post_kernel): reward and
+// done rows, the episode return, TimeLimit.truncated envs' terminal obs for the bootstrap,
+// and the returned obs (an env that auto-resets returns its reset obs, written after the reset pass)
+template <typename T, int NV, typename C>
+__device__ __forceinline__ void rollout_rows(KPtr<T> k, const Stepper<T, NV, C>& st, int sl, int env, int tstep,
+                                             int obs_dim, T r, bool term, bool trunc, double& epacc) {
+  const float rf = (float)r;
+  const double acc = epacc + (double)rf;
+  const bool rdone = term || trunc;
+  const size_t gi = (size_t)(k->ro.t_begin + tstep) * k->nenv + env;
+  if (sl == 0) {
+    k->ro.rew[gi] = rf;
+    k->ro.done[gi] = rdone;
+    k->ro.epret[gi] = acc;
+    k->ro.boot[gi] = trunc && !term;
+  }
+  epacc = rdone ? 0.0 : acc;
+  if (trunc && !term) write_obs(st.m, st.s, sl, st.qfa, k->ro.tobs + gi * obs_dim, obs_dim);
+  if (!rdone) write_obs(st.m, st.s, sl, st.qfa, ro_next_obs(k, env, tstep), obs_dim);
+}
+
+// fused evaluation: no RolloutBuffer rows.  A finished episode's result slots (one address per
+// episode, written once), a traced env's row of this step (written once), and the step's obs
+// into the env's staging row for the policy forward (next_action)
+template <typename T, int NV, typename C>
+__device__ __forceinline__ void eval_rows(KPtr<T> k, const Stepper<T, NV, C>& st, int sl, int nq, int nv, int nu,
+                                          int env, int tstep, int obs_dim, T r, bool rdone, T act, int step_count,
+                                          uint32_t episode, T total) {
+  const Scratch<T, C>& s = st.s;
+  const int g = k->ro.t_begin + tstep;
+  if (rdone && sl == 0) {
+    const uint32_t e = episode - k->ev.episode0[env];
+    if (e < (uint32_t)k->ev.max_episodes) {
+      const size_t o = (size_t)e * k->nenv + env;
+      k->ev.ep_return[o] = (double)total;
+      k->ev.ep_length[o] = step_count;
+      k->ev.ep_end_step[o] = g;
+    }
+  }
+  if (env < k->ev.n_trace) {   // the state the reward was computed from (terminal on a done step)
+    const size_t row = (size_t)g * k->ev.n_trace + env;
+    T* tq = (T*)k->ev.tr_qpos + row * nq;
+    if (sl < nq) tq[sl] = s.qpos[sl];
+    if (sl + HL < nq) tq[sl + HL] = s.qpos[sl + HL];
+    if (sl < nv) ((T*)k->ev.tr_qvel)[row * nv + sl] = s.qvel[sl];
+    if (sl < nu) k->ev.tr_act[row * nu + sl] = (float)act;
+    if (sl == 0) {
+      ((T*)k->ev.tr_rew)[row] = r;
+      k->ev.tr_done[row] = rdone;
+    }
+  }
+  if (!rdone) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
+}
+
+// env-step outcome, after the last substep (custom_env.py:163-230): the obs row, and for an env step the
+// reward, the done flags, a finished episode's info and terminal obs, the fused rollout's or evaluation's
+// rows, and whether this half resets now (do_reset) or, HINTS, some half will in its next env step
+template <bool HINTS, bool EVAL, typename T, int NV, typename C>
+__device__ __forceinline__ void env_outcome(KPtr<T> k, Stepper<T, NV, C>& st, int lane, int nq, int nv, int nu,
+                                            int env, int tstep, bool tape_final, bool rollout, bool active, T act,
+                                            T time, uint32_t episode, int& step_count, T& total, double& epacc,
+                                            bool& rdone, bool& do_reset, bool& will_reset_next) {
+  const Scratch<T, C>& s = st.s;
+  const int sl = lane & (HL - 1);
+  const int obs_dim = k->p.obs_dim;
+  HS_STAMP(st.clk, 22);
+  T* orow = step_obs_row(k, env, obs_dim, tstep, tape_final);
+  if (active && orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
+  HS_STAMP(st.clk, 23);
+  if (k->p.mode != MODE_ENV_STEP) return;
+  step_count += 1;
+  bool trunc = step_count >= k->p.max_steps;
+  // np.sum(np.square(qfrc_actuator[-nj:] * qvel[6:])) and np.sum(np.square(ctrl)) in numpy's order
+  // (each sum only for the reward that reads it: kneeling the energy, stand / walk the torque;
+  // the launch's reward id is wave-uniform)
+  const int rid = opaque(k)->p.reward_id;
+  const T e = sl < nv ? st.qfa * s.qvel[sl] : T(0);
+  const T esum = rid == REWARD_KNEELING ? np_sum_half(e * e, 6, nv - 6, lane) : T(0);
+  const T cu = sl < st.m->nu ? s.ctrl[sl] : T(0);
+  const T csum = (rid == REWARD_STAND || rid == REWARD_WALK) ? np_sum_half(cu * cu, 0, st.m->nu, lane) : T(0);
+  HS_STAMP(st.clk, 24);
+  T r = trunc ? T(0) : compute_reward(st.m, s, k, time, esum, csum);
+  HS_STAMP(st.clk, 25);
+  total += r;
+  bool term = (double)time >= k->p.duration;
+  if (sl == 0 && active && (k->tape.reward || tape_final)) {
+    const size_t o = k->tape.reward ? (size_t)tstep * k->nenv : 0;
+    (k->tape.reward ? k->tape.reward : k->b.reward)[o + env] = r;
+    (k->tape.terminated ? k->tape.terminated : k->b.terminated)[o + env] = term;
+    (k->tape.truncated ? k->tape.truncated : k->b.truncated)[o + env] = trunc;
+  }
+  // the final step's info of a finished episode (SubprocVecEnv returns its step_count /
+  // total_reward before resetting, custom_env.py:216-224), with or without auto-reset
+  if ((term || trunc) && active && sl == 0) {
+    if (k->b.term_step_count) k->b.term_step_count[env] = step_count;
+    if (k->b.term_total_reward) k->b.term_total_reward[env] = total;
+  }
+  if (rollout && active) {
+    rdone = term || trunc;
+    if constexpr (EVAL) eval_rows(k, st, sl, nq, nv, nu, env, tstep, obs_dim, r, rdone, act, step_count, episode, total);
+    else rollout_rows(k, st, sl, env, tstep, obs_dim, r, term, trunc, epacc);
+  }
+  if ((term || trunc) && k->p.autoreset && active) {
+    write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
+    do_reset = true;
+  }
+  // (an env that resets below restarts at time = dt, step 0: not flagged)
+  if constexpr (HINTS)
+    will_reset_next = __ballot(active && !do_reset && resets_next(k, st.m, time, step_count)) != 0;
+}
+
+// resident tier: an overflowing env is deferred to the wide tier instead of committed
+template <typename T, typename C>
+__device__ __forceinline__ bool defer_to_wide(KPtr<T> k, const int* warn, int sl, int env) {
+  if constexpr (C::WIDE) {
+    return false;
+  } else {
+    if (!k->b.redo || warn[WARN_OVERFLOW] == 0) return false;
+    if (sl == 0) {
+      const int slot = atomicAdd(&k->b.redo[0], 1);
+      k->b.redo[2 + slot] = env;
+      atomicAdd(k->b.redo_total, 1ull);
+    }
+    return true;
+  }
+}
+
+// commit, defer or hand off: where the state of an env that has finished its env step (or its reset
+// pass) goes, as (step_count, total) of the calling site.  true: deferred to the wide tier, nothing written.
+// Tape launch (set_tag on a whole-step item): the state goes on to the pair's next env step only
+// through its hand-off row (uncached), together with the warning counters accumulated so far.
+// Only the tape's LAST step commits to the batch buffers: consecutive steps of one env may run on
+// different XCDs, whose L2s are not coherent with each other, so two steps writing the same
+// batch address would leave whichever dirty line is written back last.  For the same reason the
+// batch's obs / reward / done rows are written by the last step only when the tape has no
+// per-step outputs, and the host keeps each env to at most one finished episode per tape launch
+// (hs_step_tape), so its terminal obs / info rows are written once.
+template <typename T, int NV, typename C>
+__device__ __forceinline__ bool commit_or_handoff(KPtr<T> k, const Stepper<T, NV, C>& st, int sl, int nq, int nv,
+                                                  int env, T time, T xws, int step_count, uint32_t episode, T total,
+                                                  const int* warn, bool tape_final, bool tape_handoff) {
+  if (defer_to_wide<T, C>(k, warn, sl, env)) return true;
+  if (tape_final) commit(st.m, k, st, env, time, xws, step_count, episode, total, warn, k->p.full_state != 0);
+  if (tape_handoff) store_handoff_state(k, st.s, sl, nq, nv, env, time, xws, step_count, episode, total, warn);
+  return false;
+}
+
+// reset draw: custom_env.py:97-130: mj_resetData; qpos = init (z=1.282, upright); += U(+-0.01) noise
+// with z noise x0.1 and no quaternion noise; qvel = U(+-0.01); one mj_step with ctrl = 0 (the caller's
+// next substep).
+template <typename T, typename C>
+__device__ __forceinline__ void reset_draw(KPtr<T> k, MPtr<T> m, Scratch<T, C>& s, int sl, int nq, int nv, int nu,
+                                           int env, uint32_t& episode, T& time, T& xws) {
+  T sc = (T)k->p.noise_scale;
+  const uint64_t seed = k->p.seed;
+  const T* nz_q = k->nz_q;
+  const T* nz_v = k->nz_v;
+  uint32_t ep = episode + 1;
+  for (int q = sl; q < nq; q += HL) {
+    T v = m->qpos0[q];
+    T nzq = nz_q ? nz_q[(size_t)env * nq + q] : uniform_pm<T>(seed, env, ep, q, sc);
+    if (m->jnt_type[0] == JNT_FREE) {
+      if (q == 2) { v = (T)k->p.init_height; nzq *= T(0.1); }
+      if (q >= 3 && q < 7) { v = q == 3 ? T(1) : T(0); nzq = 0; }
+    }
+    s.qpos[q] = v + nzq;
+  }
+  if (sl < nv) s.qvel[sl] = nz_v ? nz_v[(size_t)env * nv + sl] : uniform_pm<T>(seed, env, ep, 64 + sl, sc);
+  if (sl < nu) s.ctrl[sl] = 0;
+  xws = 0;
+  time = 0;
+  episode = ep;
+  WSYNC();
+}
+
+// next action (fused rollout and evaluation): the policy acts on the step's obs: step g + 1's action, the
+// mean or the draw of counter g + 1 + *ctr_base as ppo_act_kernel makes it, clipped, into the hand-off row
+// (or act_clip after the launch's last step).  The rollout also writes step g + 1's RolloutBuffer rows and
+// carries the episode return.
+// EVAL: the obs is in the env's staging row.  The row is uncached memory, written by env_outcome or after
+// the reset pass with agent-scope stores by this wave (both halves' rows; a ghost half reads its partner's)
+// and read back at agent scope after the wait below: no L1 / L2 line of an earlier step of this env, on
+// whatever XCD it ran, can be returned.
+template <bool EVAL, typename T, typename C>
+__device__ __forceinline__ void next_action(KPtr<T> k, Scratch<T, C>* smem, int lane, int env_id, int tstep, bool real,
+                                            T act, double epacc, bool rdone) {
+  const int sl = lane & (HL - 1);
+  const int g = k->ro.t_begin + tstep, A = k->ro.A;
+  const bool last_of_launch = tstep == k->p.nsteps - 1;
+  T* r = k->b.mid + (size_t)env_id * MIDDIM;
+  if (g + 1 < k->ro.t_total) {
+    [[maybe_unused]] const size_t gi = (size_t)(g + 1) * k->nenv + env_id;   // the rollout's rows of step g + 1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
+    float mean;
+    if constexpr (EVAL) mean = policy_mean<true>(k, k->ro.obs + (size_t)env_id * k->ro.D, smem, lane);
+    else mean = policy_mean(k, k->ro.obs + gi * k->ro.D, smem, lane);
+    const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
+    float z = 0.f;
+    if (!k->ro.deterministic && sl < A)
+      z = policy_noise((uint32_t)env_id, (uint32_t)sl, (uint64_t)(g + 1) + *k->ro.ctr_base, k->ro.k0, k->ro.k1);
+    const float a = mean + __expf(ls) * z;
+    const float ac = fminf(fmaxf(a, -1.f), 1.f);
+    if (real && sl < A) {
+      if constexpr (!EVAL) k->ro.act[gi * A + sl] = a;
+      if (last_of_launch) k->ro.act_clip[(size_t)env_id * A + sl] = ac;
+      else row_st(r + MID_ACT + sl, (T)ac);
+    }
+    if constexpr (!EVAL) {
+      const float lp = half_sum(sl < A ? -0.5f * z * z - ls - 0.91893853320467274f : 0.f);
+      if (real && sl == 0) {
+        k->ro.logp[gi] = lp;
+        k->ro.start[gi] = rdone ? 1.f : 0.f;
+      }
+    }
+  }
+  // the rollout's last step: act_clip ends as the action that step ran with (as the per-step path)
+  // (its own test, not the else of the one above: as an else the rollout instance took 256 AGPRs and
+  // 16 B/lane of scratch, against 254 and none, profiles/step_pair_split.md)
+  if (real && last_of_launch && g + 1 >= k->ro.t_total && sl < A) k->ro.act_clip[(size_t)env_id * A + sl] = (float)act;
+  if constexpr (!EVAL) {
+    if (real && sl == 0) {
+      if (last_of_launch) {
+        k->ro.ep_acc[env_id] = epacc;
+        k->ro.episode_start[env_id] = rdone ? 1.f : 0.f;
+      } else {
+        row_st(r + MID_EPACC, (T)epacc);
+      }
+    }
+  }
+}
+
+// signal: a tape launch never runs the wide tier, so an env deferred on ANY of its steps -- the last one
+// included, which hands nothing over -- stops the launch: the host restores the saved state and
+// replays the tape step by step (hs_api.cpp guarded_tape).  Otherwise the pair's next env step may
+// start: rows in memory, then the flag.
+template <typename T>
+__device__ __forceinline__ void signal_next_step(KPtr<T> k, int lane, int pair, int set_tag, bool tape_handoff,
+                                                 bool deferred) {
+  const bool any_deferred = __ballot(deferred) != 0;
+  if (any_deferred) publish(k->b.qsync + QS_ABORT, 1, lane);
+  else if (tape_handoff) publish(k->b.qsync + QS_FLAG + pair, set_tag, lane);
+}
+
+// One env step (or reset / raw physics call) of the env pair (index, index + 1) of one wave.
+// `list` (wide tier): indices map to env ids through it; resident tier: indices are env ids.
+// In the resident tier an env whose contacts / rows overflowed the resident capacity in any
+// substep is NOT committed: it is appended to the wide tier's work list instead, and the wide
+// launch that follows re-runs its whole step from the same (untouched) inputs.
+// Queued schedule: the pair's substeps [s0, s1) only, the state arriving (wait_tag) and leaving
+// (set_tag) through the pair's hand-off row (load_handoff_state above).
 // ghost: this half-wave mirrors env idx (the single-env schedule's upper half) and commits nothing.
 // HINTS (the chunk queue): *hint = STEP_* bits of this call.
 // EVAL (with ROLL): the fused evaluation (hs_evaluate, EvalArgs) -- the rollout's loop without the
@@ -466,7 +579,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
                                           int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false,
                                           int* hint = nullptr) {
   if constexpr (HINTS) *hint = 0;
-  constexpr bool WIDE = C::WIDE;
+  [[maybe_unused]] constexpr bool WIDE = C::WIDE;   // (HS_FLUSH)
   const int lane = opaque_v(threadIdx.x);   // (no lane-derived value hoisted out of the chunk-queue loop)
   const bool up = lane >= HL;
   const int sl = lane & (HL - 1);
@@ -493,61 +606,14 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
   int step_count;
   uint32_t episode;
   T total, act;
+  if (wait_tag != 0) {   // queued: the pair's previous chunk (or tape step) hands the state over
+    if (!load_handoff_state<EVAL>(ka, s, lane, nq, nv, nu, env_id, pair, wait_tag, tstep, rollout, time, xws,
+                                  step_count, episode, total, warn, act_row, epacc))
+      return;
+  } else {
+    load_batch_state<EVAL>(ka, s, sl, nq, nv, env_id, rollout, time, xws, step_count, episode, total, epacc);
+  }
   {
-    if (wait_tag != 0) {   // queued: wait for the pair's previous chunk (or tape step) to hand the state over
-      int* flag = ka->b.qsync + QS_FLAG + pair;
-      int seen = 0, abort = 0;
-      if (lane == 0) {   // bounded (~0.5 s): a broken hand-off must not hang the GPU
-        int w = 0;
-        if (pair + 1 != ka->p.dbg_lose_pair1)   // test hook: treat this unit's hand-off as lost
-          while ((seen = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != wait_tag &&
-                 ++w < (1 << 22)) {
-            // a tape launch that aborted (overflow) never hands this pair over: leave at once
-            if (tstep > 0 && (abort = __hip_atomic_load(ka->b.qsync + QS_ABORT, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT)) != 0)
-              break;
-            __builtin_amdgcn_s_sleep(2);
-          }
-      }
-      if (__builtin_amdgcn_readfirstlane(abort) != 0) return;   // results discarded: the host replays
-      const bool lost = __builtin_amdgcn_readfirstlane(seen) != wait_tag;
-      WSYNC();   // (compiler order: the row loads stay behind the poll)
-      const T* r = ka->b.mid + (size_t)env_id * MIDDIM;
-      time = row_ld(r + MID_TIME);
-      xws = (sl < nv) ? row_ld(r + MID_WS + sl) : T(0);
-      if (sl < nq) s.qpos[sl] = row_ld(r + MID_Q + sl);
-      if (sl + HL < nq) s.qpos[sl + HL] = row_ld(r + MID_Q + sl + HL);
-      if (sl < nv) s.qvel[sl] = row_ld(r + MID_V + sl);
-#pragma unroll
-      for (int w = 0; w < NWARN; w++) warn[w] = (int)row_ld(r + MID_W + w);
-      step_count = (int)row_ld(r + MID_SC);
-      episode = (uint32_t)row_ld(r + MID_EP);
-      total = row_ld(r + MID_TOT);
-      if (rollout) {
-        if (sl < nu) act_row = row_ld(r + MID_ACT + sl);
-        if constexpr (!EVAL) epacc = (double)row_ld(r + MID_EPACC);
-      }
-      // never seen in practice; if it were, the state is poisoned so that the substep's mj_checkPos
-      // resets the env (mj_resetData, ctrl 0 for that substep) -- counted in its own slot,
-      // HS_WARN_HANDOFF, not as a bad state (the -1 cancels the HS_WARN_BADQPOS count the poisoned
-      // qpos draws); the trainer raises on it: loud, never silent
-      if (lost) {
-        warn[WARN_HANDOFF]++;
-        warn[WARN_BADQPOS]--;
-        if (sl == 2) s.qpos[2] = T(NAN);
-      }
-    } else {
-      time = ka->b.time[env_id];
-      xws = (sl < nv) ? ka->b.qacc_ws[(size_t)env_id * nv + sl] : T(0);
-      if (sl < nq) s.qpos[sl] = ka->b.qpos[(size_t)env_id * nq + sl];
-      if (sl + HL < nq) s.qpos[sl + HL] = ka->b.qpos[(size_t)env_id * nq + sl + HL];
-      if (sl < nv) s.qvel[sl] = ka->b.qvel[(size_t)env_id * nv + sl];
-      step_count = ka->b.step_count[env_id];
-      episode = ka->b.episode[env_id];
-      total = ka->b.total_reward[env_id];
-      if constexpr (!EVAL)
-        if (rollout) epacc = ka->ro.ep_acc[env_id];
-    }
     // data.ctrl is an input only to a raw physics call that keeps the current ctrl; env steps set
     // it from the action, resets zero it
     const float* actions = ka->actions;
@@ -563,57 +629,11 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
   st.qfa = 0;
   st.qacc = 0;
   st.niter = 0;
-  // resident tier: an overflowing env is deferred to the wide tier instead of committed
-  auto defer = [&](KPtr<T> k) -> bool {
-    if constexpr (WIDE) {
-      return false;
-    } else {
-      if (!k->b.redo || warn[WARN_OVERFLOW] == 0) return false;
-      if (sl == 0) {
-        const int slot = atomicAdd(&k->b.redo[0], 1);
-        k->b.redo[2 + slot] = env_id;
-        atomicAdd(k->b.redo_total, 1ull);
-      }
-      return true;
-    }
-  };
-  // Tape launch (set_tag on a whole-step item): the state goes on to the pair's next env step only
-  // through its hand-off row (uncached), together with the warning counters accumulated so far.
-  // Only the tape's LAST step commits to the batch buffers: consecutive steps of one env may run on
-  // different XCDs, whose L2s are not coherent with each other, so two steps writing the same
-  // batch address would leave whichever dirty line is written back last.  For the same reason the
-  // batch's obs / reward / done rows are written by the last step only when the tape has no
-  // per-step outputs, and the host keeps each env to at most one finished episode per tape launch
-  // (hs_step_tape), so its terminal obs / info rows are written once.
+  // tape launch: a whole-step item hands over to the pair's next env step, and only the tape's last
+  // step commits to the batch (commit_or_handoff)
   const bool tape_handoff = set_tag != 0 && s1 == ka->p.nsub;
   const bool tape_final = !(ka->p.nsteps > 1 && tstep < ka->p.nsteps - 1);
   bool deferred = false;
-  auto handoff = [&](KPtr<T> k, int env, T time_, T xws_, int sc, uint32_t ep, T tot) {
-    T* r = k->b.mid + (size_t)env * MIDDIM;
-    if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
-    if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
-    if (sl < nv) { row_st(r + MID_V + sl, s.qvel[sl]); row_st(r + MID_WS + sl, xws_); }
-    if (sl == 0) {
-      row_st(r + MID_TIME, time_);
-#pragma unroll
-      for (int w = 0; w < NWARN; w++) row_st(r + MID_W + w, (T)warn[w]);
-      row_st(r + MID_SC, (T)sc);
-      row_st(r + MID_EP, (T)ep);
-      row_st(r + MID_TOT, tot);
-    }
-  };
-  // this env step's output rows: the tape's slice tstep, or the batch's own buffers (null: an
-  // intermediate step of a tape launch without per-step outputs writes none)
-  auto obs_row = [&](KPtr<T> k, int env, int obs_dim) -> T* {
-    if (k->tape.obs) return k->tape.obs + ((size_t)tstep * k->nenv + env) * obs_dim;
-    return tape_final ? k->b.obs + (size_t)env * obs_dim : nullptr;
-  };
-  // fused rollout: the rollout buffer's obs row of step g + 1 (the obs this step returns)
-  auto ro_next_obs = [&](KPtr<T> k, int env) -> float* {
-    const int g = k->ro.t_begin + tstep;
-    return g + 1 < k->ro.t_total ? k->ro.obs + ((size_t)(g + 1) * k->nenv + env) * k->ro.D
-                                 : k->ro.obs_last + (size_t)env * k->ro.D;
-  };
 
   // Both halves always run the same instruction stream; a half that is inactive (ghost env,
   // masked reset) or not resetting while its partner resets computes on scratch but commits
@@ -638,169 +658,39 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
     const int env = opaque_v(env_id);   // per-env addresses recomputed at each use, not kept live
     if (sub == s1 && s1 < nsub) {         // queued chunk ends before the last substep: hand over
       KPtr<T> k = opaque(ka);
-      if (active) {
-        T* r = k->b.mid + (size_t)env * MIDDIM;
-        if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
-        if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
-        if (sl < nv) { row_st(r + MID_V + sl, s.qvel[sl]); row_st(r + MID_WS + sl, xws); }
-        if (sl == 0) {
-          row_st(r + MID_TIME, time);
-#pragma unroll
-          for (int w = 0; w < NWARN; w++) row_st(r + MID_W + w, (T)warn[w]);
-          row_st(r + MID_SC, (T)step_count);
-          row_st(r + MID_EP, (T)episode);
-          row_st(r + MID_TOT, total);
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the row is in memory before the flag is
-      if (lane == 0) __hip_atomic_store(k->b.qsync + QS_FLAG + pair, set_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (active) store_handoff_state(k, s, sl, nq, nv, env, time, xws, step_count, episode, total, warn);
+      publish(k->b.qsync + QS_FLAG + pair, set_tag, lane);   // the row is in memory before the flag is
       HS_FLUSH();
       break;
     }
-    if (sub == nsub && !in_reset) {
+    if (sub == nsub && !in_reset) {       // after the last substep: the env step's outcome
       if (nsub > 0) {
         KPtr<T> k = opaque(ka);
-        const int obs_dim = k->p.obs_dim;
-        HS_STAMP(st.clk, 22);
-        T* orow = obs_row(k, env, obs_dim);
-        if (active && orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
-        HS_STAMP(st.clk, 23);
-        if (k->p.mode == MODE_ENV_STEP) {
-          step_count += 1;
-          bool trunc = step_count >= k->p.max_steps;
-          // np.sum(np.square(qfrc_actuator[-nj:] * qvel[6:])) and np.sum(np.square(ctrl)) in numpy's order
-          // (each sum only for the reward that reads it: kneeling the energy, stand / walk the torque;
-          // the launch's reward id is wave-uniform)
-          const int rid = opaque(k)->p.reward_id;
-          const T e = sl < nv ? st.qfa * s.qvel[sl] : T(0);
-          const T esum = rid == REWARD_KNEELING ? np_sum_half(e * e, 6, nv - 6, lane) : T(0);
-          const T cu = sl < st.m->nu ? s.ctrl[sl] : T(0);
-          const T csum = (rid == REWARD_STAND || rid == REWARD_WALK) ? np_sum_half(cu * cu, 0, st.m->nu, lane) : T(0);
-          HS_STAMP(st.clk, 24);
-          T r = trunc ? T(0) : compute_reward(st.m, s, k, time, esum, csum);
-          HS_STAMP(st.clk, 25);
-          total += r;
-          bool term = (double)time >= k->p.duration;
-          if (sl == 0 && active && (k->tape.reward || tape_final)) {
-            const size_t o = k->tape.reward ? (size_t)tstep * k->nenv : 0;
-            (k->tape.reward ? k->tape.reward : k->b.reward)[o + env] = r;
-            (k->tape.terminated ? k->tape.terminated : k->b.terminated)[o + env] = term;
-            (k->tape.truncated ? k->tape.truncated : k->b.truncated)[o + env] = trunc;
-          }
-          // the final step's info of a finished episode (SubprocVecEnv returns its step_count /
-          // total_reward before resetting, custom_env.py:216-224), with or without auto-reset
-          if ((term || trunc) && active && sl == 0) {
-            if (k->b.term_step_count) k->b.term_step_count[env] = step_count;
-            if (k->b.term_total_reward) k->b.term_total_reward[env] = total;
-          }
-          // fused rollout: SB3 collect_rollouts' bookkeeping of this step (ppo_post_kernel): reward and
-          // done rows, the episode return, TimeLimit.truncated envs' terminal obs for the bootstrap,
-          // and the returned obs (an env that auto-resets returns its reset obs, written below)
-          if constexpr (EVAL) {
-            // fused evaluation: no RolloutBuffer rows.  A finished episode's result slots (one address per
-            // episode, written once), a traced env's row of this step (written once), and the step's obs
-            // into the env's staging row for the policy forward below
-            if (rollout && active) {
-              rdone = term || trunc;
-              const int g = k->ro.t_begin + tstep;
-              if (rdone && sl == 0) {
-                const uint32_t e = episode - k->ev.episode0[env];
-                if (e < (uint32_t)k->ev.max_episodes) {
-                  const size_t o = (size_t)e * k->nenv + env;
-                  k->ev.ep_return[o] = (double)total;
-                  k->ev.ep_length[o] = step_count;
-                  k->ev.ep_end_step[o] = g;
-                }
-              }
-              if (env < k->ev.n_trace) {   // the state the reward was computed from (terminal on a done step)
-                const size_t row = (size_t)g * k->ev.n_trace + env;
-                T* tq = (T*)k->ev.tr_qpos + row * nq;
-                if (sl < nq) tq[sl] = s.qpos[sl];
-                if (sl + HL < nq) tq[sl + HL] = s.qpos[sl + HL];
-                if (sl < nv) ((T*)k->ev.tr_qvel)[row * nv + sl] = s.qvel[sl];
-                if (sl < nu) k->ev.tr_act[row * nu + sl] = (float)act;
-                if (sl == 0) {
-                  ((T*)k->ev.tr_rew)[row] = r;
-                  k->ev.tr_done[row] = rdone;
-                }
-              }
-              if (!rdone) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
-            }
-          } else if (rollout && active) {
-            const float rf = (float)r;
-            const double acc = epacc + (double)rf;
-            rdone = term || trunc;
-            const size_t gi = (size_t)(k->ro.t_begin + tstep) * k->nenv + env;
-            if (sl == 0) {
-              k->ro.rew[gi] = rf;
-              k->ro.done[gi] = rdone;
-              k->ro.epret[gi] = acc;
-              k->ro.boot[gi] = trunc && !term;
-            }
-            epacc = rdone ? 0.0 : acc;
-            if (trunc && !term) write_obs(st.m, s, sl, st.qfa, k->ro.tobs + gi * obs_dim, obs_dim);
-            if (!rdone) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);
-          }
-          if ((term || trunc) && k->p.autoreset && active) {
-            write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
-            do_reset = true;
-          }
-          // (an env that resets below restarts at time = dt, step 0: not flagged)
-          if constexpr (HINTS)
-            will_reset_next = __ballot(active && !do_reset && resets_next(k, st.m, time, step_count)) != 0;
-        }
+        env_outcome<HINTS, EVAL>(k, st, lane, nq, nv, nu, env, tstep, tape_final, rollout, active, act, time, episode,
+                                 step_count, total, epacc, rdone, do_reset, will_reset_next);
         if (active && !do_reset) {
-          if (!defer(k)) {
-            if (tape_final) commit(st.m, k, st, env, time, xws, step_count, episode, total, warn, k->p.full_state != 0);
-            if (tape_handoff) handoff(k, env, time, xws, step_count, episode, total);
-          } else {
+          if (commit_or_handoff(k, st, sl, nq, nv, env, time, xws, step_count, episode, total, warn, tape_final,
+                                tape_handoff))
             deferred = true;
-          }
           active = false;   // committed (or deferred); a reset pass below is scratch work for this half
         }
       }
       if (__ballot(do_reset) == 0) { HS_FLUSH(); break; }
-      // custom_env.py:97-130: mj_resetData; qpos = init (z=1.282, upright); += U(+-0.01) noise
-      // with z noise x0.1 and no quaternion noise; qvel = U(+-0.01); one mj_step with ctrl = 0.
-      KPtr<T> k = opaque(ka);
       in_reset = true;
       st.dbg = nullptr;
-      T sc = (T)k->p.noise_scale;
-      const uint64_t seed = k->p.seed;
-      const T* nz_q = k->nz_q;
-      const T* nz_v = k->nz_v;
-      uint32_t ep = episode + 1;
-      for (int q = sl; q < nq; q += HL) {
-        T v = m->qpos0[q];
-        T nzq = nz_q ? nz_q[(size_t)env * nq + q] : uniform_pm<T>(seed, env, ep, q, sc);
-        if (m->jnt_type[0] == JNT_FREE) {
-          if (q == 2) { v = (T)k->p.init_height; nzq *= T(0.1); }
-          if (q >= 3 && q < 7) { v = q == 3 ? T(1) : T(0); nzq = 0; }
-        }
-        s.qpos[q] = v + nzq;
-      }
-      if (sl < nv) s.qvel[sl] = nz_v ? nz_v[(size_t)env * nv + sl] : uniform_pm<T>(seed, env, ep, 64 + sl, sc);
-      if (sl < nu) s.ctrl[sl] = 0;
-      xws = 0;
-      time = 0;
-      episode = ep;
-      WSYNC();
-    } else if (sub > nsub) {
+      reset_draw(opaque(ka), m, s, sl, nq, nv, nu, env, episode, time, xws);
+    } else if (sub > nsub) {              // after the reset's substep: the reset obs, the new episode's state
       if (do_reset && active) {
         KPtr<T> k = opaque(ka);
         if (k->b.dbg && env == 0) dump_debug(st, k->b.dbg);
         const int obs_dim = k->p.obs_dim;
-        T* orow = obs_row(k, env, obs_dim);
+        T* orow = step_obs_row(k, env, obs_dim, tstep, tape_final);
         if (orow) write_obs(st.m, s, sl, st.qfa, orow, obs_dim);
         if constexpr (EVAL) {
           if (rollout) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
-        } else if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env), obs_dim);   // the reset obs
-        if (!defer(k)) {
-          if (tape_final) commit(st.m, k, st, env, time, xws, 0, episode, T(0), warn, k->p.full_state != 0);
-          if (tape_handoff) handoff(k, env, time, xws, 0, episode, T(0));
-        } else {
+        } else if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env, tstep), obs_dim);   // the reset obs
+        if (commit_or_handoff(k, st, sl, nq, nv, env, time, xws, 0, episode, T(0), warn, tape_final, tape_handoff))
           deferred = true;
-        }
       }
       HS_FLUSH();
       break;
@@ -815,91 +705,10 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
 #endif
     if (st.dbg && active && !in_reset) dump_debug(st, st.dbg);
   }
-  if constexpr (EVAL) {
-    // The policy acts on the step's obs in the env's staging row: step g + 1's action, the mean or the
-    // hs_ppo_act draw of counter g + 1 + *ctr_base, clipped, into the hand-off row (or act_clip after the
-    // launch's last step).  The row is uncached memory, written above with agent-scope stores by this
-    // wave (both halves' rows; a ghost half reads its partner's) and read back at agent scope after the
-    // wait below: no L1 / L2 line of an earlier step of this env, on whatever XCD it ran, can be returned.
-    if (rollout) {
-      KPtr<T> k = opaque(ka);
-      const int g = k->ro.t_begin + tstep, A = k->ro.A;
-      const bool last_of_launch = tstep == k->p.nsteps - 1;
-      T* r = k->b.mid + (size_t)env_id * MIDDIM;
-      if (g + 1 < k->ro.t_total) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
-        const float mean = policy_mean<true>(k, k->ro.obs + (size_t)env_id * k->ro.D, smem, lane);
-        float z = 0.f;
-        if (!k->ro.deterministic && sl < A)
-          z = policy_noise((uint32_t)env_id, (uint32_t)sl, (uint64_t)(g + 1) + *k->ro.ctr_base, k->ro.k0, k->ro.k1);
-        const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
-        const float ac = fminf(fmaxf(mean + __expf(ls) * z, -1.f), 1.f);
-        if (real && sl < A) {
-          if (last_of_launch) k->ro.act_clip[(size_t)env_id * A + sl] = ac;
-          else row_st(r + MID_ACT + sl, (T)ac);
-        }
-      } else if (real && last_of_launch && sl < A) {
-        k->ro.act_clip[(size_t)env_id * A + sl] = (float)act;   // as hs_rollout: the action the last step ran with
-      }
-    }
-  } else if constexpr (ROLL) {
-    if (rollout) {   // the policy acts on the step's obs: step g + 1's action, drawn as ppo_act_kernel does
-      KPtr<T> k = opaque(ka);
-      const int g = k->ro.t_begin + tstep, N = k->nenv, A = k->ro.A;
-      const bool last_of_launch = tstep == k->p.nsteps - 1;
-      T* r = k->b.mid + (size_t)env_id * MIDDIM;
-      if (g + 1 < k->ro.t_total) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
-        const float mean = policy_mean(k, k->ro.obs + ((size_t)(g + 1) * N + env_id) * k->ro.D, smem, lane);
-        const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
-        float z = 0.f;
-        if (!k->ro.deterministic && sl < A)
-          z = policy_noise((uint32_t)env_id, (uint32_t)sl, (uint64_t)(g + 1) + *k->ro.ctr_base, k->ro.k0, k->ro.k1);
-        const float a = mean + __expf(ls) * z;
-        const float lp = half_sum(sl < A ? -0.5f * z * z - ls - 0.91893853320467274f : 0.f);
-        if (real) {
-          const size_t gi = (size_t)(g + 1) * N + env_id;
-          if (sl < A) {
-            const float ac = fminf(fmaxf(a, -1.f), 1.f);
-            k->ro.act[gi * A + sl] = a;
-            if (last_of_launch) k->ro.act_clip[(size_t)env_id * A + sl] = ac;
-            else row_st(r + MID_ACT + sl, (T)ac);
-          }
-          if (sl == 0) {
-            k->ro.logp[gi] = lp;
-            k->ro.start[gi] = rdone ? 1.f : 0.f;
-          }
-        }
-      }
-      // the rollout's last step: act_clip ends as the action that step ran with (as the per-step path)
-      if (real && last_of_launch && g + 1 >= k->ro.t_total && sl < A) k->ro.act_clip[(size_t)env_id * A + sl] = (float)act;
-      if (real && sl == 0) {
-        if (last_of_launch) {
-          k->ro.ep_acc[env_id] = epacc;
-          k->ro.episode_start[env_id] = rdone ? 1.f : 0.f;
-        } else {
-          row_st(r + MID_EPACC, (T)epacc);
-        }
-      }
-    }
+  if constexpr (ROLL) {
+    if (rollout) next_action<EVAL>(opaque(ka), smem, lane, env_id, tstep, real, act, epacc, rdone);
   }
-  // A tape launch never runs the wide tier, so an env deferred on ANY of its steps -- the last one
-  // included, which hands nothing over -- stops the launch: the host restores the saved state and
-  // replays the tape step by step (hs_api.cpp guarded_tape).  Otherwise the pair's next env step may
-  // start: rows in memory, then the flag.
-  if (tape_handoff || tape_launch) {
-    KPtr<T> k = opaque(ka);
-    const bool any_deferred = __ballot(deferred) != 0;
-    if (tape_handoff || any_deferred) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) {
-        if (any_deferred)
-          __hip_atomic_store(k->b.qsync + QS_ABORT, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-          __hip_atomic_store(k->b.qsync + QS_FLAG + pair, set_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
+  if (tape_handoff || tape_launch) signal_next_step(opaque(ka), lane, pair, set_tag, tape_handoff, deferred);
   if constexpr (HINTS) *hint = (will_reset_next ? STEP_WILL_RESET : 0) | (in_reset ? STEP_DID_RESET : 0);
 }
 

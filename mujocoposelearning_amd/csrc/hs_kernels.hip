@@ -28,7 +28,9 @@
 //   hs_contacts.h     narrow phase, impedance, J x / J' f, contact aggregates
 //   hs_phase_clock.h  per-phase stamps of the HS_TIMING build
 //   hs_stepper.h      Stepper: one mj_step, phase by phase
-//   hs_env_step.h     reset, reward, obs, policy forward, commit, step_pair
+//   hs_reward.h       the reward plug-ins' inputs and formulas, numpy's summation order
+//   hs_policy.h       the fused rollout's / evaluation's policy forward (pi net on a wave's two envs)
+//   hs_env_step.h     reset, obs, commit, step_pair and its phases (load, outcome, hand-off, next action)
 //   this file         the __global__ kernels, the host launchers, the explicit instantiations
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // Counter-based Gaussian noise of the PPO rollout (product): Philox4x32-10 (Salmon et al., SC'11)
 // keyed by the 64-bit seed, and a Box-Muller transform of two of its words.  Shared by the per-step
-// sampler (ppo_rollout.hip ppo_act_kernel) and the fused rollout (hs_env_step.h step_pair), so both draw bitwise the
+// sampler (ppo_rollout.hip ppo_act_kernel) and the fused rollout (hs_env_step.h next_action), so both draw bitwise the
 // same z for the same (env, action index, rollout step).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -475,7 +475,7 @@ class PPO:
         """collect_rollouts as hs_rollout_act launches: this method samples step 0's action on the first obs
         (the per-step sampler, as _rollout_body), then each launch runs up to hs_rollout_max_steps env
         steps with the policy forward, sampling and buffer bookkeeping inside the env kernel
-        (hs_env_step.h step_pair), each env pair's step t + 1 starting when its own step t is done.
+        (hs_env_step.h step_pair: rollout_rows, next_action; hs_policy.h), each env pair's step t + 1 starting when its own step t is done.
         The noise is hs_ppo_act's Philox stream, so the draws are those of the per-step path; the
         policy means agree with the GEMM chain to fp32 rounding (tests/test_gpu_ppo.py).  A launch
         that hits a resident-tier contact overflow is undone by the library, and the rest of the

@@ -2,7 +2,7 @@
 
 ``REWARD_FUNCTIONS[name](env_data, params) -> float`` with identical keys
 (``default``, ``kneeling``, ``stand``, ``walk``; reward_functions.py:264-269) and semantics.
-Each built-in also has a DEVICE implementation inside the step kernel (``hs_env_step.h``
+Each built-in also has a DEVICE implementation inside the step kernel (``hs_reward.h``
 ``compute_reward``); envs use the device path for built-ins and fall back to calling the
 Python function on a read-only ``data`` view for user-registered callables (slow, correct).
 """

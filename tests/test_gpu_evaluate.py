@@ -1,5 +1,5 @@
 """Fused policy evaluation (hs_evaluate, evaluation.evaluate_policy_device): whole episodes in launches
-of the fp64 chunk-queue kernel's evaluation instance (hs_env_step.h step_pair, EVAL) -- env step, pi net on
+of the fp64 chunk-queue kernel's evaluation instance (hs_env_step.h step_pair, EVAL: eval_rows, next_action; hs_policy.h) -- env step, pi net on
 the env's wave from the env's one staging row, clipped action to the pair's next step -- with per-episode
 results and an optional trace instead of the RolloutBuffer.
 

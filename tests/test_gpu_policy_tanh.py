@@ -1,7 +1,7 @@
 """Tanh policy nets (SB3's MlpPolicy default, and PPO's here) on the fused rollout-time kernels:
 the shared device tanh (csrc/hs_act.h hs_tanh) through hs_mlp2_forward_act with identity weights,
 mlp2_fwd_kernel<.., ACT_TANH> against the packed GEMM chain, hs_rollout_act's in-kernel policy
-(hs_env_step.h policy_mean_body<R, ACT_TANH>) with the checks of tests/test_gpu_rollout.py, ReLU
+(hs_policy.h policy_mean_body<R, ACT_TANH>) with the checks of tests/test_gpu_rollout.py, ReLU
 through the new entry point bitwise as through the old, the refusals, and the default-constructed
 trainer.  Every case asserts that it runs the fused path, not the fallback."""
 import ctypes as C

@@ -1,6 +1,6 @@
 """The fused rollout-time kernels at hidden widths 64 and 128 (the reference's config.py trains
 [64, 64]): hs_mlp2_forward_h (ppo_mlp.hip mlp2_fwd_kernel<.., H>) against the packed GEMM chain, and
-hs_rollout's in-kernel policy forward (hs_env_step.h policy_mean_r<H / 64>) with the checks of
+hs_rollout's in-kernel policy forward (hs_policy.h policy_mean_body<H / 64, ACT>) with the checks of
 tests/test_gpu_rollout.py -- env replay bitwise, the per-step sampler on the chain's mean, episode
 returns bitwise.  Every case asserts that it runs the fused path, not the fallback."""
 import ctypes as C

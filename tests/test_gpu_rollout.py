@@ -1,7 +1,7 @@
 """Fused PPO rollouts (hs_rollout, PPO._rollout_fused): SB3 collect_rollouts' per-step loop --
 policy forward, Gaussian sample, clip, env step, buffer bookkeeping -- as one launch of the fp64
 engine's chunk-queue kernel per chunk of steps, the pi net evaluated on each env's wave
-(hs_env_step.h policy_mean / step_pair).
+(hs_policy.h policy_mean, hs_env_step.h step_pair).
 
 Checked against the pieces the per-step path is built from:
 * the env: stepping a copy of the batch with the rollout's own clipped actions, one hs_step per
