@@ -343,6 +343,28 @@ typedef struct hs_eval_bufs {
  * hs_step at a time.  < 0: error (hs_last_error).  Synchronizes; hs_last_tape_ms covers the launch. */
 int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
                 int t_total, void* stream);
+/* VecNormalize's observation moments for the fused policy (SB3 2.3.2 common/vec_env/vec_normalize.py):
+ * device arrays mean [obs_dim] and inv_std [obs_dim] (float32; 1 / sqrt(var + epsilon), as hs_rms_merge
+ * writes them) and clip_obs.  The struct must be zero-initialised before its fields are filled in. */
+typedef struct hs_obs_norm_args {
+  const float* mean;
+  const float* inv_std;
+  float clip;
+  int obs_dim;      /* must equal the batch's obs_dim */
+} hs_obs_norm_args;
+/* hs_rollout_act on a VecNormalize-wrapped env <- VecNormalize.step_wait's normalize_obs in front of
+ * PPO.collect_rollouts' policy forward: the policy inside the kernel reads clamp((obs - mean) inv_std, +-clip)
+ * of every obs value (the same fp32 expression as hs_obs_norm, bitwise), computed as the obs row is
+ * loaded.  The rollout buffer rows (obs, obs_last, terminal_obs) are written RAW, as by hs_rollout_act: the
+ * caller normalises them afterwards in one hs_obs_norm pass with the same moments, which stay fixed for the
+ * whole rollout.  Every other argument, the return values and the overflow undo are hs_rollout_act's. */
+int hs_rollout_norm(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb,
+                    const hs_obs_norm_args* norm, int t_begin, int n_steps, int t_total, void* stream);
+/* hs_evaluate for a policy trained on normalised obs <- evaluate_policy(model, VecNormalize(env,
+ * training=False)): the policy reads the normalised obs as above, the moments are not updated, the
+ * staging rows stay raw and the episode returns are the env's raw ones. */
+int hs_evaluate_norm(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, const hs_obs_norm_args* norm,
+                     int t_begin, int n_steps, int t_total, void* stream);
 /* Auto-reset noise source of hs_step: [N][nq] / [N][nv] device arrays of the batch precision with
  * the raw U(-noise_scale, noise_scale) draws of the NEXT reset of each env (the kernel applies the
  * x0.1 height factor and zeroes the quaternion part, custom_env.py:109-114); NULL, NULL = the
@@ -434,6 +456,42 @@ int hs_reward(hs_batch* b, int reward_id, const double* kneel_params, void* out,
 int hs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values,
            const float* last_dones, float* advantages, float* returns, int T, int N, float gamma, float gae_lambda,
            void* stream);
+/* VecNormalize.normalize_obs over rows <- np.clip((obs - obs_rms.mean) / np.sqrt(obs_rms.var + epsilon),
+ * -clip_obs, clip_obs) (vec_normalize.py), and optionally in the same pass the batch moments that
+ * obs_rms.update(obs) takes of the RAW rows.  X [rows][ldx] float32 (first obs_dim columns), mean / inv_std
+ * [obs_dim] float32; out [rows][ldo] may be X itself (in place).  out = clamp((x - mean) * inv_std, +-clip),
+ * float32, subtraction and product each rounded to nearest (no FMA): bitwise what the fused policy of
+ * hs_rollout_norm reads.  moments != NULL: moments[0] = rows, moments[1 + c] = the mean and
+ * moments[1 + obs_dim + c] = the sum of squared deviations (M2 = var * rows) of column c, float64, taken about
+ * the first row as a shift and reduced in a fixed two-stage order (no atomics: two runs are bitwise equal);
+ * `workspace` then holds hs_obs_norm_workspace(rows, obs_dim) bytes.  obs_dim <= 512.  16-byte accesses when
+ * obs_dim, ldx, ldo are multiples of 4 and every pointer is 16-byte aligned.  Asynchronous on `stream`. */
+uint64_t hs_obs_norm_workspace(uint64_t rows, int obs_dim);
+int hs_obs_norm(const float* X, uint64_t ldx, uint64_t rows, int obs_dim, const float* mean, const float* inv_std,
+                float clip, float* out, uint64_t ldo, double* moments, void* workspace, void* stream);
+/* RunningMeanStd.update_from_moments (common/running_mean_std.py) on the device, float64: state = (count,
+ * mean [dim], var [dim]) absorbs n_sets batch moment sets (count, mean [dim], M2 [dim]) -- hs_obs_norm's
+ * layout -- at sets + k * set_stride, in ascending k, each by Chan's merge in SB3's operation order; a set
+ * with count 0 is skipped.  Then, when given, mean_f32 [dim] = mean and inv_std_f32 [dim] =
+ * 1 / sqrt(var + epsilon) rounded to float32: the arrays hs_obs_norm and hs_rollout_norm read.  n_sets = 0
+ * only refreshes those arrays.  One small launch, asynchronous on `stream`: no host synchronisation. */
+int hs_rms_merge(double* state, int dim, const double* sets, int n_sets, uint64_t set_stride, double epsilon,
+                 float* mean_f32, float* inv_std_f32, void* stream);
+/* VecNormalize's reward path over a finished rollout, phase A <- self.returns = self.returns * gamma + rewards
+ * of step_wait, step by step: rewards [T][N] float32 (raw), dones [T][N] uint8; returns_carry [N] float64
+ * holds self.returns between rollouts (in / out; zeroed where done, after the step's moments).  Writes
+ * moments [T][3] float64 = (N, mean, M2) of the step's returns over the N envs -- what ret_rms.update(
+ * self.returns) takes -- in a fixed reduction order.  `workspace`: T * N doubles.  Asynchronous. */
+int hs_return_moments(const float* rewards, const uint8_t* dones, int T, int N, double gamma, double* returns_carry,
+                      double* workspace, double* moments, void* stream);
+/* Phase B <- ret_rms.update + normalize_reward of step_wait: for t = 0 .. T - 1 the step's batch -- the
+ * union, in ascending k, of the n_sets sets at moments + k * set_stride + 3 t (one set per rank: the
+ * all-gathered hs_return_moments blocks; n_sets = 1 for one process) -- is merged into state = (count, mean,
+ * var) of ret_rms (float64), and rewards[t][:] = clip(rewards[t][:] / sqrt(var + epsilon), +-clip) with the
+ * variance after that merge (quotient in float64, rounded to float32).  In place; `workspace`: T doubles.
+ * Asynchronous on `stream`. */
+int hs_reward_scale(float* rewards, int T, int N, double* state, const double* moments, int n_sets,
+                    uint64_t set_stride, double epsilon, double clip, double* workspace, void* stream);
 /* One PPO rollout step's policy sampling and buffer writes over N envs (A <= 32 actions):
  * mean [N][mean_ld] (first A columns), value [N] at stride value_ld, log_std [A], episode_start
  * [N] (all float32 device memory).  actions = mean + exp(log_std) * z with z ~ N(0, 1) from the

@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("evaluate_policy", "evaluate_policy_device", "EvalCallback", "EvalResult", "render_policy"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name in ("VecNormalize", "RunningMeanStd"):
+        from . import vec_normalize
+        return getattr(vec_normalize, name)
     if name == "HsBatch":
         from .batch import HsBatch
         return HsBatch

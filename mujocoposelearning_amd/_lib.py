@@ -67,6 +67,10 @@ class hs_eval_bufs(C.Structure):
                [("seed", C.c_uint64), ("deterministic", C.c_int)]
 
 
+class hs_obs_norm_args(C.Structure):
+    _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float), ("obs_dim", C.c_int)]
+
+
 class hs_batch_info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_envs", "precision", "nq", "nv", "nu", "nbody", "obs_dim", "elem_size",
                                        "resident_con", "resident_efc", "wide_con", "wide_efc", "resident_waves",
@@ -113,6 +117,13 @@ def lib():
         "hs_rollout_act": (i, [vp, vp, i, vp, i, i, i, vp]),
         "hs_rollout_max_steps": (i, [vp]),
         "hs_evaluate": (i, [vp, vp, i, vp, i, i, i, vp]),
+        "hs_rollout_norm": (i, [vp, vp, i, vp, vp, i, i, i, vp]),
+        "hs_evaluate_norm": (i, [vp, vp, i, vp, vp, i, i, i, vp]),
+        "hs_obs_norm_workspace": (u64, [u64, i]),
+        "hs_obs_norm": (i, [vp, u64, u64, i, vp, vp, C.c_float, vp, u64, vp, vp, vp]),
+        "hs_rms_merge": (i, [vp, i, vp, i, u64, d, vp, vp, vp]),
+        "hs_return_moments": (i, [vp, vp, i, i, d, vp, vp, vp, vp]),
+        "hs_reward_scale": (i, [vp, i, i, vp, vp, i, u64, d, d, vp, vp]),
         "hs_set_autoreset_noise": (i, [vp, vp, vp]),
         "hs_physics_step": (i, [vp, vp, i, vp]),
         "hs_state_io": (i, [vp, i, vp, vp, vp, vp, vp]),
@@ -181,7 +192,9 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create
             "hs_mlp2_forward", "hs_mlp2_forward_h", "hs_mlp2_forward_act", "hs_colsum_partial_rows", "hs_relu_grad_colsum",
             "hs_act_grad_colsum", "hs_dgrad_mask_partial_rows",
             "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_dgrad_act", "hs_colsum_pair",
-            "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version")
+            "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version",
+            "hs_rollout_norm", "hs_evaluate_norm", "hs_obs_norm_workspace", "hs_obs_norm", "hs_rms_merge",
+            "hs_return_moments", "hs_reward_scale")
 
 
 class HsimError(RuntimeError):

@@ -192,7 +192,7 @@ hs::StepParams params_of(const hs_batch* b, int mode, int nsub) {
 
 int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const void* nq, const void* nvz, int nsub,
            void* stream, int nsteps = 1, const hs_tape_out* tape = nullptr, const hs::RolloutArgs* ro = nullptr,
-           const hs::EvalArgs* ev = nullptr) {
+           const hs::EvalArgs* ev = nullptr, const hs::NormArgs* nm = nullptr) {
   if (!b) return fail("null batch");
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
@@ -204,7 +204,7 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
     hs::TapeOut<double> to{tape ? (double*)tape->obs : nullptr, tape ? (double*)tape->reward : nullptr,
                            tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
     e = hs::launch_step<double>((const hs::DevModel<double>*)b->dmodel, nv, env_buffers<double>(b), act, mask,
-                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro, ev);
+                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro, ev, nm);
   } else {
     hs::TapeOut<float> to{tape ? (float*)tape->obs : nullptr, tape ? (float*)tape->reward : nullptr,
                           tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
@@ -720,13 +720,56 @@ hs::RolloutArgs policy_args(const hs_policy* pol, int hidden, int act) {
   ro.ld1 = pol->ld1; ro.D = pol->obs_dim; ro.A = pol->act_dim; ro.H = hidden; ro.hact = act;
   return ro;
 }
+
+// hs_rollout_norm / hs_evaluate_norm: the moments the policy normalises its obs with
+int norm_args_check(const hs_batch* b, const hs_obs_norm_args* on, const std::string& who, hs::NormArgs* out) {
+  if (!on) return fail(who + ": null hs_obs_norm_args");
+  if (!on->mean || !on->inv_std) return fail(who + ": null mean / inv_std");
+  if (on->obs_dim != b->obs_dim)
+    return fail(who + ": hs_obs_norm_args.obs_dim " + std::to_string(on->obs_dim) + " is not the batch's obs_dim " +
+                std::to_string(b->obs_dim));
+  if (!(on->clip > 0.f)) return fail(who + ": need clip > 0");
+  out->mean = on->mean; out->inv_std = on->inv_std; out->clip = on->clip;
+  return 0;
+}
+
+int rollout_impl(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
+                 int t_total, void* stream, const hs_obs_norm_args* on, bool norm);
+int evaluate_impl(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
+                  int t_total, void* stream, const hs_obs_norm_args* on, bool norm);
 }  // namespace
 
 int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
                    int t_total, void* stream) {
+  return rollout_impl(b, pol, act, rb, t_begin, n_steps, t_total, stream, nullptr, false);
+}
+
+int hs_rollout_norm(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb,
+                    const hs_obs_norm_args* norm, int t_begin, int n_steps, int t_total, void* stream) {
+  return rollout_impl(b, pol, act, rb, t_begin, n_steps, t_total, stream, norm, true);
+}
+
+int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
+                int t_total, void* stream) {
+  return evaluate_impl(b, pol, act, eb, t_begin, n_steps, t_total, stream, nullptr, false);
+}
+
+int hs_evaluate_norm(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, const hs_obs_norm_args* norm,
+                     int t_begin, int n_steps, int t_total, void* stream) {
+  return evaluate_impl(b, pol, act, eb, t_begin, n_steps, t_total, stream, norm, true);
+}
+
+namespace {
+int rollout_impl(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_bufs* rb, int t_begin, int n_steps,
+                 int t_total, void* stream, const hs_obs_norm_args* on, bool norm) {
   if (!b || !pol || !rb) return fail("null argument");
   int hidden = 0;
-  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, "hs_rollout", &hidden)) return rc;
+  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, norm ? "hs_rollout_norm" : "hs_rollout",
+                                  &hidden))
+    return rc;
+  hs::NormArgs nm{};
+  if (norm)
+    if (int rc = norm_args_check(b, on, "hs_rollout_norm", &nm)) return rc;
   for (const void* q : {(const void*)pol->w1, (const void*)pol->b1, (const void*)pol->w2, (const void*)pol->b2,
                         (const void*)pol->w3, (const void*)pol->b3, (const void*)pol->log_std, (const void*)rb->obs,
                         (const void*)rb->obs_last, (const void*)rb->actions, (const void*)rb->log_probs,
@@ -754,17 +797,22 @@ int hs_rollout_act(hs_batch* b, const hs_policy* pol, int act, const hs_rollout_
   hipStream_t st = (hipStream_t)stream;
   int rc = guarded_tape(b, regs, st, [&] {
     return launch(b, hs::MODE_ENV_STEP, rb->actions_clipped, nullptr, nullptr, nullptr, b->cfg.frame_skip, stream,
-                  n_steps, nullptr, &ro);
+                  n_steps, nullptr, &ro, nullptr, norm ? &nm : nullptr);
   });
   if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
   return rc;
 }
 
-int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
-                int t_total, void* stream) {
+int evaluate_impl(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* eb, int t_begin, int n_steps,
+                  int t_total, void* stream, const hs_obs_norm_args* on, bool norm) {
   if (!b || !pol || !eb) return fail("null argument");
   int hidden = 0;
-  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, "hs_evaluate", &hidden)) return rc;
+  if (int rc = fused_policy_check(b, pol, act, t_begin, n_steps, t_total, norm ? "hs_evaluate_norm" : "hs_evaluate",
+                                  &hidden))
+    return rc;
+  hs::NormArgs nm{};
+  if (norm)
+    if (int rc = norm_args_check(b, on, "hs_evaluate_norm", &nm)) return rc;
   for (const void* q : {(const void*)pol->w1, (const void*)pol->b1, (const void*)pol->w2, (const void*)pol->b2,
                         (const void*)pol->w3, (const void*)pol->b3, (const void*)pol->log_std,
                         (const void*)eb->actions_clipped, (const void*)eb->episode0, (const void*)eb->ep_return,
@@ -803,11 +851,12 @@ int hs_evaluate(hs_batch* b, const hs_policy* pol, int act, const hs_eval_bufs* 
   regs.push_back({eb->actions_clipped, N * (size_t)pol->act_dim * sizeof(float)});
   int rc = guarded_tape(b, regs, (hipStream_t)stream, [&] {
     return launch(b, hs::MODE_ENV_STEP, eb->actions_clipped, nullptr, nullptr, nullptr, b->cfg.frame_skip, stream,
-                  n_steps, nullptr, &ro, &ev);
+                  n_steps, nullptr, &ro, &ev, norm ? &nm : nullptr);
   });
   if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
   return rc;
 }
+}  // namespace
 
 int hs_debug_lose_handoff(hs_batch* b, int env) {
   if (!b) return fail("null batch");

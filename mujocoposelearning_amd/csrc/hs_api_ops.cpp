@@ -275,6 +275,56 @@ int hs_colsum(const float* x, uint64_t rows, uint64_t cols, const float* row_wei
   return hip_rc(hs::launch_colsum(x, rows, cols, row_weight, workspace, out, (hipStream_t)stream), "colsum_kernel");
 }
 
+uint64_t hs_obs_norm_workspace(uint64_t rows, int obs_dim) {
+  return obs_dim > 0 ? hs::obs_norm_workspace((size_t)rows, obs_dim) : 0;
+}
+
+int hs_obs_norm(const float* X, uint64_t ldx, uint64_t rows, int obs_dim, const float* mean, const float* inv_std,
+                float clip, float* out, uint64_t ldo, double* moments, void* workspace, void* stream) {
+  if (obs_dim < 1 || obs_dim > 512) return fail("hs_obs_norm: need 1 <= obs_dim <= 512");
+  if (ldx < (uint64_t)obs_dim || ldo < (uint64_t)obs_dim) return fail("hs_obs_norm: need ldx >= obs_dim and ldo >= obs_dim");
+  if (!(clip > 0.f)) return fail("hs_obs_norm: need clip > 0");
+  if (rows == 0) return 0;
+  if (!X || !mean || !inv_std || !out) return fail("hs_obs_norm: null buffer");
+  if (moments && !workspace) return fail("hs_obs_norm: moments need the workspace of hs_obs_norm_workspace bytes");
+  return hip_rc(hs::launch_obs_norm(X, (size_t)ldx, (size_t)rows, obs_dim, mean, inv_std, clip, out, (size_t)ldo,
+                                    moments, workspace, (hipStream_t)stream),
+                "obs_norm_kernel");
+}
+
+int hs_rms_merge(double* state, int dim, const double* sets, int n_sets, uint64_t set_stride, double epsilon,
+                 float* mean_f32, float* inv_std_f32, void* stream) {
+  if (dim < 1 || n_sets < 0) return fail("hs_rms_merge: need dim >= 1 and n_sets >= 0");
+  if (n_sets > 0 && set_stride < (uint64_t)(1 + 2 * dim)) return fail("hs_rms_merge: need set_stride >= 1 + 2 dim");
+  if (!state || (n_sets > 0 && !sets)) return fail("hs_rms_merge: null buffer");
+  return hip_rc(hs::launch_rms_merge(state, dim, sets, n_sets, (size_t)set_stride, epsilon, mean_f32, inv_std_f32,
+                                     (hipStream_t)stream),
+                "rms_merge_kernel");
+}
+
+int hs_return_moments(const float* rewards, const uint8_t* dones, int T, int N, double gamma, double* returns_carry,
+                      double* workspace, double* moments, void* stream) {
+  if (T < 0 || N < 0) return fail("hs_return_moments: negative size");
+  if (T == 0 || N == 0) return 0;
+  if (!rewards || !dones || !returns_carry || !workspace || !moments) return fail("hs_return_moments: null buffer");
+  return hip_rc(hs::launch_return_moments(rewards, dones, T, N, gamma, returns_carry, workspace, moments,
+                                          (hipStream_t)stream),
+                "return moments kernels");
+}
+
+int hs_reward_scale(float* rewards, int T, int N, double* state, const double* moments, int n_sets,
+                    uint64_t set_stride, double epsilon, double clip, double* workspace, void* stream) {
+  if (T < 0 || N < 0) return fail("hs_reward_scale: negative size");
+  if (n_sets < 1 || set_stride < (uint64_t)3 * (uint64_t)(T > 0 ? T : 0))
+    return fail("hs_reward_scale: need n_sets >= 1 and set_stride >= 3 T");
+  if (!(clip > 0.0)) return fail("hs_reward_scale: need clip > 0");
+  if (T == 0 || N == 0) return 0;
+  if (!rewards || !state || !moments || !workspace) return fail("hs_reward_scale: null buffer");
+  return hip_rc(hs::launch_reward_scale(rewards, T, N, state, moments, n_sets, (size_t)set_stride, epsilon, clip,
+                                        workspace, (hipStream_t)stream),
+                "reward scale kernels");
+}
+
 int hs_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values,
            const float* last_dones, float* advantages, float* returns, int T, int N, float gamma, float gae_lambda,
            void* stream) {

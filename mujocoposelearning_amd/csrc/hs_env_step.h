@@ -500,7 +500,8 @@ __device__ __forceinline__ void reset_draw(KPtr<T> k, MPtr<T> m, Scratch<T, C>& 
 // the reset pass with agent-scope stores by this wave (both halves' rows; a ghost half reads its partner's)
 // and read back at agent scope after the wait below: no L1 / L2 line of an earlier step of this env, on
 // whatever XCD it ran, can be returned.
-template <bool EVAL, typename T, typename C>
+// NORM: the policy reads the obs normalised with the launch's moments (hs_policy.h).
+template <bool EVAL, bool NORM = false, typename T, typename C>
 __device__ __forceinline__ void next_action(KPtr<T> k, Scratch<T, C>* smem, int lane, int env_id, int tstep, bool real,
                                             T act, double epacc, bool rdone) {
   const int sl = lane & (HL - 1);
@@ -511,8 +512,8 @@ __device__ __forceinline__ void next_action(KPtr<T> k, Scratch<T, C>* smem, int 
     [[maybe_unused]] const size_t gi = (size_t)(g + 1) * k->nenv + env_id;   // the rollout's rows of step g + 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's obs row is written before it is read
     float mean;
-    if constexpr (EVAL) mean = policy_mean<true>(k, k->ro.obs + (size_t)env_id * k->ro.D, smem, lane);
-    else mean = policy_mean(k, k->ro.obs + gi * k->ro.D, smem, lane);
+    if constexpr (EVAL) mean = policy_mean<true, NORM>(k, k->ro.obs + (size_t)env_id * k->ro.D, smem, lane);
+    else mean = policy_mean<false, NORM>(k, k->ro.obs + gi * k->ro.D, smem, lane);
     const float ls = sl < A ? k->ro.log_std[sl] : 0.f;
     float z = 0.f;
     if (!k->ro.deterministic && sl < A)
@@ -573,7 +574,9 @@ __device__ __forceinline__ void signal_next_step(KPtr<T> k, int lane, int pair, 
 // RolloutBuffer: the step's obs goes to the env's one staging row (ro.obs, [N][D], uncached), the policy
 // reads it back, the clipped action goes to the pair's next step; a finished episode writes its three
 // result slots, a traced env one trace row.
-template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false, bool EVAL = false>
+// NORM (with ROLL): the instances of hs_rollout_norm / hs_evaluate_norm, whose policy normalises its obs.
+template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false, bool EVAL = false,
+          bool NORM = false>
 __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCache<T, C>* pcache, int idx,
                                           int nidx, const int* list, int s0, int s1, int pair, bool ghost = false,
                                           int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false,
@@ -706,7 +709,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
     if (st.dbg && active && !in_reset) dump_debug(st, st.dbg);
   }
   if constexpr (ROLL) {
-    if (rollout) next_action<EVAL>(opaque(ka), smem, lane, env_id, tstep, real, act, epacc, rdone);
+    if (rollout) next_action<EVAL, NORM>(opaque(ka), smem, lane, env_id, tstep, real, act, epacc, rdone);
   }
   if (tape_handoff || tape_launch) signal_next_step(opaque(ka), lane, pair, set_tag, tape_handoff, deferred);
   if constexpr (HINTS) *hint = (will_reset_next ? STEP_WILL_RESET : 0) | (in_reset ? STEP_DID_RESET : 0);

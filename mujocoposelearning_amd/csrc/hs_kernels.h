@@ -189,6 +189,15 @@ struct EvalArgs {
   uint8_t* tr_done;           // [t_total][n_trace]
 };
 
+// Observation normalisation of the fused policy's obs load (hs_rollout_norm / hs_evaluate_norm, the NORM
+// kernel instances only): the policy reads clamp((obs - mean) inv_std, +-clip) (hs_norm.h) of each raw obs
+// value; the rollout buffer rows and the evaluation's staging row stay raw.
+struct NormArgs {
+  const float* mean;      // [D]
+  const float* inv_std;   // [D] 1 / sqrt(var + eps), fp32
+  float clip;
+};
+
 // p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape` (may be null), env
 // steps of one env pair run back to back on the chunk queue with the state handed over through
 // b.mid; no wide-tier launch follows (an overflow sets qsync[QS_ABORT], the host replays the tape).
@@ -196,7 +205,11 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape = nullptr,
-                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr);
+                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr, const NormArgs* nm = nullptr);
+
+// The fused rollout / evaluation instance with obs normalisation (KArgs::nm set) on the chunk queue: kargs is
+// launch_step's KArgs<double>, max_grid its grid (the launch takes no more waves than the instance holds)
+hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream);
 
 // waves of the resident step-kernel instance the current device holds at once (0 if unknown)
 template <typename T>
@@ -328,6 +341,16 @@ hipError_t launch_relu_colsum(const float* g, const float* y, size_t rows, size_
                               float* partial, hipStream_t stream);
 hipError_t launch_colsum_pair(const float* x0, size_t rows0, size_t cols0, float* out0, const float* x1, size_t rows1,
                               size_t cols1, float* out1, hipStream_t stream);
+// VecNormalize (ppo_norm.hip; include/hsim.h hs_obs_norm, hs_rms_merge, hs_return_moments, hs_reward_scale)
+size_t obs_norm_workspace(size_t R, int D);
+hipError_t launch_obs_norm(const float* x, size_t ldx, size_t R, int D, const float* mean, const float* inv_std,
+                           float clip, float* out, size_t ldo, double* moments, void* workspace, hipStream_t stream);
+hipError_t launch_rms_merge(double* state, int D, const double* sets, int nsets, size_t set_stride, double eps,
+                            float* mean32, float* inv_std32, hipStream_t stream);
+hipError_t launch_return_moments(const float* rew, const uint8_t* done, int T, int N, double gamma, double* carry,
+                                 double* ret_ws, double* out, hipStream_t stream);
+hipError_t launch_reward_scale(float* rew, int T, int N, double* state, const double* sets, int nsets,
+                               size_t set_stride, double eps, double clip, double* scale_ws, hipStream_t stream);
 // GAE reverse scan over [T][N] float32 rollout arrays (gae.hip)
 hipError_t launch_gae(const float* rew, const float* val, const float* start, const float* last_val,
                       const float* last_done, float* adv, float* ret, int T, int N, float gamma, float lam,

@@ -84,7 +84,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
 // policy forward's code and registers stay out of the per-step kernel
 // EVAL (with ROLL): the fused-evaluation instance (hs_evaluate): the rollout's loop without the RolloutBuffer
 // rows, a kernel of its own so that the rollout instance keeps its code and registers
-template <typename T, int NV, bool PGS, bool ROLL = false, bool EVAL = false>
+// NORM (with ROLL): the instances whose policy normalises its obs on load (hs_rollout_norm,
+// hs_evaluate_norm; KArgs::nm), kernels of their own so that every other instance keeps its code and registers
+template <typename T, int NV, bool PGS, bool ROLL = false, bool EVAL = false, bool NORM = false>
 __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via kernarg ptr */) {
   const KPtr<T> ka = (KPtr<T>)__builtin_amdgcn_kernarg_segment_ptr();
   // this launch's epoch (its hand-off tags are qtag(epoch, ...)): the epoch only changes after every
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
     const int wait_tag = tape ? (t > 0 ? qtag(epoch, t - 1, 1) : 0) : (last ? qtag(epoch, 0, 0) : 0);
     const int set_tag = tape ? (t < K - 1 ? qtag(epoch, t, 1) : 0) : (last ? 0 : qtag(epoch, 0, 0));
     int hint;   // (STEP_* bits, wave-uniform)
-    step_pair<T, NV, PGS, Resident<T>, ROLL, true, EVAL>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair,
+    step_pair<T, NV, PGS, Resident<T>, ROLL, true, EVAL, NORM>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair,
                                                          single && upper, wait_tag, set_tag, t, tape, &hint);
 #ifdef HS_TIMING
     // per item (indexed as step_pair's q0 stamps): its claim index within its chunk kind, and whether
@@ -394,7 +396,7 @@ int resident_waves(bool pgs) {
 // a claim (step_kernel_queue), so every wave of the grid has to be running from the start.  It is
 // below resident_waves() where the queue instance's occupancy is below the direct kernel's (the fp32
 // Newton engine: 1 wave per SIMD against 2).
-template <typename T, bool PGS, bool ROLL, bool EVAL = false>
+template <typename T, bool PGS, bool ROLL, bool EVAL = false, bool NORM = false>
 int queue_waves() {
   constexpr int MAXDEV = 64;
   static int cache[MAXDEV] = {};   // 0: not yet computed
@@ -404,7 +406,7 @@ int queue_waves() {
   int per_cu = 0, v = -1;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL>, WAVE, 0) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL, NORM>, WAVE, 0) == hipSuccess &&
       per_cu > 0)
     v = per_cu * prop.multiProcessorCount;
   cache[dev] = v;
@@ -415,12 +417,13 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape,
-                       const RolloutArgs* ro, const EvalArgs* ev) {
+                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm) {
   if (nenv <= 0) return hipSuccess;
   if (nv != 27) return hipErrorInvalidValue;
   KArgs<T> args{(MPtr<T>)dmodel, b, actions, reset_mask, noise_qpos, noise_qvel, p, nenv,
                 tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{},
-                ev ? *ev : EvalArgs{}};
+                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}};
+  if (nm && (!ro || !nm->mean || !nm->inv_std || !(nm->clip > 0.f))) return hipErrorInvalidValue;
   // fused rollouts: the fp64 Newton engine
   if (ro && (sizeof(T) != 8 || !ro->obs || p.solver == SOLVER_PGS)) return hipErrorInvalidValue;
   // fused evaluation: a rollout launch (the policy, ro.obs = the staging rows) with result slots
@@ -496,6 +499,8 @@ hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b
     rc = launch_tiers(std::true_type{});
   } else if (ro) {
     if constexpr (sizeof(T) == 8) {
+      // the NORM instances live in an object of their own (launch_queue_norm below)
+      if (nm) return launch_queue_norm(&args, grid.x, ev != nullptr, stream);
       const int held = ev ? queue_waves<T, false, true, true>() : queue_waves<T, false, true>();
       if (held <= 0) return hipErrorInvalidValue;
       if (ev)
@@ -516,11 +521,28 @@ hipError_t launch_kinematics(const DevModel<T>* dmodel, int nv, const T* qpos, T
   return hipGetLastError();
 }
 // The Makefile compiles this file once per precision (HS_ONLY_F32 / HS_ONLY_F64), so each engine
-// gets its own code-generation flags (the fp64 one without MachineLICM).
+// gets its own code-generation flags (the fp64 one without MachineLICM), and once more
+// (HS_ONLY_NORM, the fp64 flags) for the two fused instances whose policy normalises its obs
+// (hs_rollout_norm, hs_evaluate_norm): in a code object of their own they leave the engines' code objects,
+// kernel for kernel and byte for byte, what they are without them.
+#ifdef HS_ONLY_NORM
+hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream) {
+  const KArgs<double>& args = *static_cast<const KArgs<double>*>(kargs);
+  const int held = eval ? queue_waves<double, false, true, true, true>() : queue_waves<double, false, true, false, true>();
+  if (held <= 0) return hipErrorInvalidValue;
+  const dim3 grid(std::min(max_grid, (unsigned)held)), block(WAVE);
+  if (eval)
+    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, true, true, true>), grid, block, 0, stream, args);
+  else
+    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, true, false, true>), grid, block, 0, stream, args);
+  return hipGetLastError();
+}
+#else
 #ifndef HS_ONLY_F64
 template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuffers<float>&, const float*,
                                        const uint8_t*, const float*, const float*, const StepParams&, int,
-                                       hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*);
+                                       hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*,
+                                       const NormArgs*);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
 template hipError_t launch_reward_eval<float>(const RewardEvalArgs<float>&, hipStream_t);
@@ -529,11 +551,13 @@ template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 #ifndef HS_ONLY_F32
 template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvBuffers<double>&, const float*,
                                         const uint8_t*, const double*, const double*, const StepParams&, int,
-                                        hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*);
+                                        hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*,
+                                        const NormArgs*);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
 template hipError_t launch_reward_eval<double>(const RewardEvalArgs<double>&, hipStream_t);
 template hipError_t launch_pack<double>(const PackArgs<double>&, hipStream_t);
 #endif
+#endif   // HS_ONLY_NORM
 
 }  // namespace hs

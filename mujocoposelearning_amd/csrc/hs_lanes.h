@@ -191,7 +191,8 @@ struct KArgs {
   int nenv;
   TapeOut<T> tape;            // per-step outputs of a tape launch (p.nsteps > 1), or all null
   RolloutArgs ro;             // fused rollout (ro.obs != null): actions from the policy, see hs_kernels.h
-  EvalArgs ev;                // fused evaluation (the EVAL instance only; last, so every other offset stays)
+  EvalArgs ev;                // fused evaluation (the EVAL instance only; after ro, so every other offset stays)
+  NormArgs nm;                // obs normalisation of the fused policy (the NORM instances only; last, as above)
 };
 template <typename T>
 using KPtr = const __attribute__((address_space(4))) KArgs<T>*;

@@ -5,6 +5,7 @@
 
 #include "hs_act.h"
 #include "hs_lanes.h"
+#include "hs_norm.h"
 #include "hs_scratch.h"
 
 namespace hs {
@@ -40,7 +41,9 @@ __device__ __forceinline__ void pol_load(const float* p, float (&u)[R]) {
 }
 // UC: the obs row is the fused evaluation's staging row (uncached memory, rewritten every env step): read
 // at agent scope, as the hand-off rows (row_ld)
-template <int R, int ACT, bool UC = false, typename T, typename C>
+// NORM: the launch carries VecNormalize's moments (KArgs::nm): each obs value is normalised as it is staged
+// (hs_obs_normalize, the function hs_obs_norm runs over the buffer rows), the row in memory stays raw
+template <int R, int ACT, bool UC = false, bool NORM = false, typename T, typename C>
 __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   constexpr int H = 64 * R;
   const bool up = lane >= HL;
@@ -51,7 +54,17 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
   float* hb = smem[1].u.pol.h;
   const int D = k->ro.D, A = k->ro.A, ld1 = k->ro.ld1;
   float* xo = up ? xb : xa;
-  if constexpr (UC) {
+  if constexpr (NORM) {
+    const float* nmean = k->nm.mean;
+    const float* nscale = k->nm.inv_std;
+    const float nclip = k->nm.clip;
+    for (int i = sl; i < D; i += HL) {
+      float v;
+      if constexpr (UC) v = row_ld(obs + i);
+      else v = obs[i];
+      xo[i] = hs_obs_normalize(v, nmean[i], nscale[i], nclip);
+    }
+  } else if constexpr (UC) {
     for (int i = sl; i < D; i += HL) xo[i] = row_ld(obs + i);
   } else {
     for (int i = sl; i < D; i += HL) xo[i] = obs[i];
@@ -102,23 +115,23 @@ __device__ __forceinline__ float policy_mean_body(KPtr<T> k, const float* obs, S
 // registers (4 AGPRs more, profiles/rollout_widths.md), and a call per env step is noise next to the step.
 // The two 256-wide bodies (ReLU and Tanh) are inlined: together they leave every figure of the kernel
 // where it was, and as a call the Tanh one ran the rollout 5 % slower (profiles/tanh_policy.md).
-template <int R, int ACT, bool UC = false, typename T, typename C>
+template <int R, int ACT, bool UC = false, bool NORM = false, typename T, typename C>
 __device__ __noinline__ float policy_mean_call(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
-  return policy_mean_body<R, ACT, UC>(k, obs, smem, lane);
+  return policy_mean_body<R, ACT, UC, NORM>(k, obs, smem, lane);
 }
 // one wave-uniform dispatch on the hidden width and the activation (hs_rollout_act admits 64, 128 and 256,
 // ReLU and Tanh only)
-template <bool UC = false, typename T, typename C>
+template <bool UC = false, bool NORM = false, typename T, typename C>
 __device__ __forceinline__ float policy_mean(KPtr<T> k, const float* obs, Scratch<T, C>* smem, int lane) {
   const int H = k->ro.H;
   if (k->ro.hact == ACT_TANH) {
-    if (H == 256) return policy_mean_body<4, ACT_TANH, UC>(k, obs, smem, lane);
-    if (H == 128) return policy_mean_call<2, ACT_TANH, UC>(k, obs, smem, lane);
-    return policy_mean_call<1, ACT_TANH, UC>(k, obs, smem, lane);
+    if (H == 256) return policy_mean_body<4, ACT_TANH, UC, NORM>(k, obs, smem, lane);
+    if (H == 128) return policy_mean_call<2, ACT_TANH, UC, NORM>(k, obs, smem, lane);
+    return policy_mean_call<1, ACT_TANH, UC, NORM>(k, obs, smem, lane);
   }
-  if (H == 256) return policy_mean_body<4, ACT_RELU, UC>(k, obs, smem, lane);
-  if (H == 128) return policy_mean_call<2, ACT_RELU, UC>(k, obs, smem, lane);
-  return policy_mean_call<1, ACT_RELU, UC>(k, obs, smem, lane);
+  if (H == 256) return policy_mean_body<4, ACT_RELU, UC, NORM>(k, obs, smem, lane);
+  if (H == 128) return policy_mean_call<2, ACT_RELU, UC, NORM>(k, obs, smem, lane);
+  return policy_mean_call<1, ACT_RELU, UC, NORM>(k, obs, smem, lane);
 }
 
 }  // namespace

@@ -16,6 +16,11 @@ memory does not grow with the number of steps (the optional trace aside).  Anyth
 engine, host reward callables, other net shapes, a CPU env -- and the rest of an evaluation whose launch
 hit a resident-tier contact overflow run the same loop one ``step_tensors`` at a time.
 
+A model trained over ``VecNormalize`` (``model.vec_normalize``) is evaluated on normalised obs: its obs
+moments, frozen, are applied to the evaluation env's raw obs -- inside the kernel on the fused path
+(``hs_evaluate_norm``), by ``hs_obs_norm`` step by step -- and the episode returns stay the env's raw ones.
+An evaluation env that is itself wrapped is stepped through its raw env; its own moments are not used.
+
 Evaluating never changes a training run: the noise of a stochastic evaluation is the evaluation's own
 (its own Philox seed and device counter on the fused path, its own ``torch.Generator`` step by step), and
 neither ``PPO._noise_ctr`` nor the global torch RNG is touched.
@@ -71,6 +76,16 @@ def _batch_of(env):
     return getattr(env, "batch", None)
 
 
+def _policy_obs(model, obs):
+    """What the policy reads of the raw fp32 obs rows: a copy normalised with the model's frozen moments
+    when it was trained over VecNormalize, else the rows."""
+    vn = getattr(model, "vec_normalize", None)
+    if vn is None or not vn.norm_obs:
+        return obs
+    obs = obs.contiguous()
+    return vn.normalize_obs_tensor(obs, out=torch.empty_like(obs))
+
+
 def _terminal_info(env):
     """(terminal_total_reward, terminal_step_count) tensors of the env, or None: the finished episodes'
     final info (custom_env.py:216-224), from the env itself or its HsBatch."""
@@ -99,7 +114,7 @@ class _Stepwise:
     @torch.no_grad()
     def action(self, obs):
         pol = self.model.policy
-        mean = pol.net_forward(obs.float(), 0)
+        mean = pol.net_forward(_policy_obs(self.model, obs.float()), 0)
         if not self.deterministic:
             noise = torch.randn(mean.shape, generator=self.gen, device=mean.device, dtype=mean.dtype)
             mean = mean + pol.log_std.detach().exp() * noise
@@ -167,6 +182,10 @@ def evaluate_policy_device(model, env, n_episodes_per_env, deterministic=True, n
     x, y: those two are the previous step's).
     ``reset=False`` continues from the env's current state and obs.  ``seed``: the evaluation's own noise.
     """
+    from .vec_normalize import unwrap
+    env, _ = unwrap(env)             # raw obs and rewards; the moments applied are the model's
+    vn = getattr(model, "vec_normalize", None)
+    norm = vn.norm_args() if vn is not None and vn.norm_obs and torch.device(env.device).type == "cuda" else None
     E, N, nt = int(n_episodes_per_env), int(env.num_envs), int(n_trace)
     if E < 1:
         raise ValueError("n_episodes_per_env must be >= 1")
@@ -213,7 +232,7 @@ def evaluate_policy_device(model, env, n_episodes_per_env, deterministic=True, n
     act_clip = torch.zeros(N, A, dtype=f32, device=dev)
     scratch = [torch.zeros(N, A, dtype=f32, device=dev)] + [torch.zeros(N, dtype=f32, device=dev) for _ in range(4)]
     # step 0's action on the first obs: the per-step sampler, as PPO._rollout_fused
-    mean = pol.net_forward(obs.float(), 0)
+    mean = pol.net_forward(_policy_obs(model, obs.float()), 0)
     ppo_act(mean, scratch[1], pol.log_std.detach(), scratch[2], key, 0, deterministic, scratch[0], act_clip,
             scratch[3], scratch[4], scratch[2].clone(), counter_base=ctr)
     episode0 = b.episode.clone()
@@ -232,7 +251,12 @@ def evaluate_policy_device(model, env, n_episodes_per_env, deterministic=True, n
     t0 = 0
     while t0 < T:
         k = min(L, T - t0)
-        rc = _lib.check(_lib.lib().hs_evaluate(handle, C.byref(cpol), pol._act_id(), C.byref(eb), t0, k, T, stream))
+        if norm is not None:
+            rc = _lib.check(_lib.lib().hs_evaluate_norm(handle, C.byref(cpol), pol._act_id(), C.byref(eb),
+                                                        C.byref(norm), t0, k, T, stream))
+        else:
+            rc = _lib.check(_lib.lib().hs_evaluate(handle, C.byref(cpol), pol._act_id(), C.byref(eb), t0, k, T,
+                                                   stream))
         if rc == 1:
             # resident-tier overflow: the library restored the env state and act_clip; whatever the undone
             # launch wrote into the result slots is dropped, and the rest runs step by step from t0
@@ -323,8 +347,9 @@ def render_policy(model_path, out_path, num_steps=1000, camera="side", height=48
 
     from .ppo import PPO
     from .render import Renderer, write_video
-    from .sb3_format import load_sb3_zip
+    from .sb3_format import load_sb3_zip, read_member
     from .vec_env import HumanoidVecEnv
+    from .vec_normalize import VecNormalize
     xml = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "humanoid.xml")
     cfg = {"model_path": xml, "framerate": framerate, "duration": 10.0, "reward_config": {"type": "walk"},
            "frame_skip": 3}
@@ -335,10 +360,15 @@ def render_policy(model_path, out_path, num_steps=1000, camera="side", height=48
     pk = data.get("policy_kwargs") if isinstance(data.get("policy_kwargs"), dict) else {}
     env = HumanoidVecEnv(cfg, n_envs=1, device=device, precision="fp64")
     try:
-        model = PPO(env, n_steps=2, batch_size=2, n_epochs=1,
+        stats = read_member(zp, "vec_normalize.npz")     # a model trained over VecNormalize: frozen moments
+        penv = VecNormalize(env, training=False) if stats is not None else env
+        model = PPO(penv, n_steps=2, batch_size=2, n_epochs=1,
                     policy_kwargs={"net_arch": pk.get("net_arch", {"pi": [64, 64], "vf": [64, 64]}),
                                    "activation_fn": pk.get("activation_fn", "Tanh")})
         load_sb3_zip(zp, model.policy, map_location=model.device)
+        if stats is not None:
+            penv.from_bytes(stats)
+            penv.training = False
         res = evaluate_policy_device(model, env, 1, deterministic=True, n_trace=1)
         qpos = res.trace["qpos"][:, 0].double().cpu().numpy()
         dones = res.trace["dones"][:, 0].cpu().numpy()

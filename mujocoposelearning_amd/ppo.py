@@ -299,6 +299,10 @@ class PPO:
         if isinstance(act, str):
             act = getattr(nn, act)
         self.env = env
+        # PPO(VecNormalize(venv)): the wrapper's moments normalise what the policy sees;
+        # self.obs, ep_returns and the logger's ep_rew_mean stay raw
+        from .vec_normalize import VecNormalize
+        self.vec_normalize = env if isinstance(env, VecNormalize) else None
         self.policy_kwargs, self.net_arch, self.learning_rate = pk, net, learning_rate
         self.device = torch.device(env.device)
         torch.manual_seed(seed)          # identical initial weights on every rank
@@ -365,6 +369,9 @@ class PPO:
         self._noise_seed = (int(seed) + 7919 * rank) * 0x9E3779B97F4A7C15 % 2 ** 64
         self._noise_ctr = torch.zeros(1, dtype=torch.int64, device=dev)    # Philox step counter (device)
         self._rollout_graph = None
+        if self.vec_normalize is not None:      # normalised copies: one step's obs, the rollout's last obs
+            self._obs_step = torch.zeros(N, D, dtype=f, device=dev)
+            self._obs_last_n = torch.zeros(N, D, dtype=f, device=dev)
         self.logger = {}
         # with world > 1 the stop decision is taken from the global minibatch's approx_kl, which rides
         # as one extra element of the gradient bucket (only when target_kl is set: the bucket is the
@@ -422,6 +429,9 @@ class PPO:
         b, env, pol = self.buf, self.env, self.policy
         T, N = self.n_steps, env.num_envs
         pol.pack_heads()
+        vn = self.vec_normalize
+        if vn is not None:
+            vn.begin_rollout()
         if self._fused_rollout_args() is not None:
             self._rollout_fused()
         else:
@@ -431,10 +441,43 @@ class PPO:
                 self._rollout_graph.replay()
             else:
                 self._rollout_body()
+        if vn is not None:
+            self._normalize_rollout()                     # buffer obs, values, rewards (before the bootstrap)
         boot = b["boot"].view(-1).nonzero().squeeze(1)
         if boot.numel():                                        # deferred TimeLimit bootstrap
-            b["rew"].view(-1)[boot] += self.gamma * pol.value(b["tobs"].view(T * N, -1)[boot])
+            tobs = b["tobs"].view(T * N, -1)[boot]
+            if self._norm_obs():
+                vn.normalize_obs_tensor(tobs)                   # with the rollout-start moments
+            b["rew"].view(-1)[boot] += self.gamma * pol.value(tobs)
         return self._finish_rollout()
+
+    def _norm_obs(self):
+        vn = self.vec_normalize
+        return vn is not None and vn.norm_obs
+
+    def _policy_obs(self, obs, out):
+        """What the policy reads of the raw rows ``obs``: the rows themselves, or with VecNormalize their
+        normalised copy in ``out`` (hs_obs_norm with the rollout-start moments)."""
+        return self.vec_normalize.normalize_obs_tensor(obs, out=out) if self._norm_obs() else obs
+
+    def _normalize_rollout(self):
+        """After a rollout over a VecNormalize env (the buffers hold RAW obs and rewards): normalise the
+        buffered obs in place with the rollout-start moments -- the same pass yields the batch moments of the
+        returned obs obs_1 .. obs_T (and, in the first rollout, of the reset obs) --, a normalised copy of the
+        last obs for the last value, V(obs_t) over the buffer (device), and VecNormalize's reward path as a
+        post-pass.  The running moments absorb the batch moments in _finish_rollout."""
+        vn, b, T = self.vec_normalize, self.buf, self.n_steps
+        if vn.norm_obs:
+            train = vn.training
+            first = train and vn.absorb_reset()
+            vn.normalize_obs_tensor(b["obs"][0], moments_slot=0 if first else None)
+            if T > 1:
+                vn.normalize_obs_tensor(b["obs"][1:], moments_slot=1 if train else None)
+            vn.normalize_obs_tensor(self.obs, out=self._obs_last_n, moments_slot=2 if train else None)
+            if self.device.type == "cuda":
+                self._rollout_values()
+        vn.normalize_rewards_rollout(b["rew"], b["done"], self.world_size if self.sync_grads else 1,
+                                     self._comm_device() if self.sync_grads and self.world_size > 1 else None)
 
     def _finish_rollout(self):
         """The end of collect_rollouts on either path: finished-episode returns, the timestep count,
@@ -442,7 +485,11 @@ class PPO:
         b = self.buf
         self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
         self.num_timesteps += self.n_steps * self.n_envs_global
-        last_v = self.policy.value(self.obs)
+        last_v = self.policy.value(self._obs_last_n if self._norm_obs() else self.obs)
+        vn = self.vec_normalize
+        if vn is not None and vn.norm_obs and vn.training:     # between rollouts: the moments move
+            vn.merge_obs_moments(self.world_size if self.sync_grads else 1,
+                                 self._comm_device() if self.sync_grads and self.world_size > 1 else None)
         return gae(b["rew"], b["val"], b["start"], last_v, self.episode_start, self.gamma, self.gae_lambda)
 
     def _fused_rollout_args(self):
@@ -487,10 +534,11 @@ class PPO:
         T = self.n_steps
         handle, cpol, keep = self._fused_rollout_args()
         b["obs"][0].copy_(self.obs)
-        mean = pol.net_forward(b["obs"][0], 0)
+        mean = pol.net_forward(self._policy_obs(b["obs"][0], getattr(self, "_obs_step", None)), 0)
         ppo_act(mean, self._zero_n, pol.log_std.detach(), self.episode_start, self._noise_seed, 0, False,
                 b["act"][0], self._act_clip, b["logp"][0], self._val_scratch, b["start"][0],
                 counter_base=self._noise_ctr)
+        norm = self.vec_normalize.norm_args() if self._norm_obs() else None
         rb = _lib.hs_rollout_bufs(b["obs"].data_ptr(), self.obs.data_ptr(), b["act"].data_ptr(), b["logp"].data_ptr(),
                                   b["start"].data_ptr(), b["rew"].data_ptr(), b["done"].data_ptr(),
                                   b["epret"].data_ptr(), b["boot"].data_ptr(), b["tobs"].data_ptr(),
@@ -501,8 +549,12 @@ class PPO:
         t0 = 0
         while t0 < T:
             k = min(L, T - t0)
-            rc = _lib.check(_lib.lib().hs_rollout_act(handle, C.byref(cpol), pol._act_id(), C.byref(rb), t0, k, T,
-                                                      stream))
+            if norm is not None:       # the policy inside the kernel normalises its obs on load
+                rc = _lib.check(_lib.lib().hs_rollout_norm(handle, C.byref(cpol), pol._act_id(), C.byref(rb),
+                                                           C.byref(norm), t0, k, T, stream))
+            else:
+                rc = _lib.check(_lib.lib().hs_rollout_act(handle, C.byref(cpol), pol._act_id(), C.byref(rb), t0, k, T,
+                                                          stream))
             if rc == 0:                       # (env steps, kernel ms by HIP events) of the last launches
                 ms = C.c_double(0)
                 _lib.check(_lib.lib().hs_last_tape_ms(handle, C.byref(ms)))
@@ -524,7 +576,8 @@ class PPO:
         if t_from == 0:
             b["obs"][0].copy_(self.obs)
         for t in range(t_from, T):
-            mean = pol.net_forward(b["obs"][t], 0) if pol._packed is not None else pol.heads(b["obs"][t])[0]
+            x = self._policy_obs(b["obs"][t], getattr(self, "_obs_step", None))
+            mean = pol.net_forward(x, 0) if pol._packed is not None else pol.heads(x)[0]
             ppo_act(mean, self._zero_n, pol.log_std.detach(), self.episode_start, self._noise_seed, t, False,
                     b["act"][t], self._act_clip, b["logp"][t], self._val_scratch, b["start"][t],
                     counter_base=self._noise_ctr)
@@ -536,9 +589,13 @@ class PPO:
         self._rollout_tail()
 
     def _rollout_tail(self):
+        self._noise_ctr.add_(self.n_steps)
+        if not self._norm_obs():       # (VecNormalize: after the buffer's in-place pass, _normalize_rollout)
+            self._rollout_values()
+
+    def _rollout_values(self):
         b, pol = self.buf, self.policy
         T, N = self.n_steps, self.env.num_envs
-        self._noise_ctr.add_(T)
         # values of every buffered obs in one batched vf forward (SB3 stores V(obs_t) per step;
         # the policy does not change inside a rollout, so this is the same quantity)
         b["val"].view(-1).copy_(pol.net_forward(b["obs"].view(T * N, -1), 1) if pol._packed is not None
@@ -574,6 +631,8 @@ class PPO:
         timeout bootstrap r += gamma V(terminal_obs) is evaluated for every env and masked, and
         finished-episode returns are recorded in device buffers and read back once at the end."""
         b, env, pol = self.buf, self.env, self.policy
+        if self.vec_normalize is not None:
+            return self._collect_rollouts_torch_norm()
         for t in range(self.n_steps):
             a, logp, v = pol.act(self.obs)
             b["obs"][t] = self.obs
@@ -593,6 +652,37 @@ class PPO:
             self.ep_acc.masked_fill_(done, 0.0)
             self.obs = obs.float().clone()
             self.episode_start = done.float()
+        return self._finish_rollout()
+
+    def _collect_rollouts_torch_norm(self):
+        """_collect_rollouts_torch over a VecNormalize env, with the device path's semantics: the policy
+        reads obs normalised with the rollout-start moments, the buffers hold raw obs and rewards until
+        _normalize_rollout, and the TimeLimit bootstrap is added to the already normalised reward."""
+        b, env, pol, vn = self.buf, self.env, self.policy, self.vec_normalize
+        vn.begin_rollout()
+        tv_all = torch.zeros_like(b["rew"])
+        for t in range(self.n_steps):
+            a, logp, v = pol.act(self._policy_obs(self.obs, self._obs_step))
+            b["obs"][t] = self.obs
+            b["act"][t] = a
+            b["val"][t] = v
+            b["logp"][t] = logp
+            b["start"][t] = self.episode_start
+            obs, rew, term, trunc = env.step_tensors(a.clamp(-1.0, 1.0))
+            term, trunc = term.bool(), trunc.bool()
+            boot = trunc & ~term
+            tv = pol.value(self._policy_obs(env.terminal_obs.float().contiguous(), self._obs_last_n))
+            tv_all[t] = torch.where(boot, tv, torch.zeros_like(tv))
+            b["rew"][t] = rew.float()
+            done = term | trunc
+            self.ep_acc += rew.double()
+            b["done"][t] = done
+            b["epret"][t] = self.ep_acc
+            self.ep_acc.masked_fill_(done, 0.0)
+            self.obs = obs.float().clone()
+            self.episode_start = done.float()
+        self._normalize_rollout()
+        b["rew"] += self.gamma * tv_all
         return self._finish_rollout()
 
     # -- multi-rank lockstep ---------------------------------------------------------------------
@@ -1040,7 +1130,10 @@ class PPO:
         (actions clipped to [-1, 1] as numpy, None)."""
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.float32, device=self.device)
         single = obs.dim() == 1
-        a, _, _ = self.policy.act(obs[None] if single else obs, deterministic=deterministic)
+        obs = (obs[None] if single else obs).contiguous()
+        if self._norm_obs():         # frozen moments: predict never updates them
+            obs = self.vec_normalize.normalize_obs_tensor(obs, out=torch.empty_like(obs))
+        a, _, _ = self.policy.act(obs, deterministic=deterministic)
         a = a.clamp(-1.0, 1.0).cpu().numpy()
         return (a[0] if single else a), None
 
@@ -1060,12 +1153,21 @@ class PPO:
     def save(self, path):
         """SB3 checkpoint layout (train_sb3.py:234 ``model.save``): writes ``path``.zip."""
         from .sb3_format import save_sb3_zip
-        return save_sb3_zip(path, self.policy, self.opt, self._data())
+        vn = self.vec_normalize
+        extra = {"vec_normalize.npz": vn.to_bytes()} if vn is not None else None
+        return save_sb3_zip(path, self.policy, self.opt, self._data(), extra=extra)
 
     def load(self, path):
         """Load weights + optimizer state from an SB3-layout zip (ours or SB3's own)."""
-        from .sb3_format import load_sb3_zip
+        from .sb3_format import load_sb3_zip, read_member
+        raw = read_member(path, "vec_normalize.npz")
+        if raw is not None and self.vec_normalize is None:
+            raise ValueError(f"{path}: the model was saved with VecNormalize (vec_normalize.npz), but this PPO's env "
+                             "is not wrapped: build it as PPO(VecNormalize(env), ...) so the policy sees the obs "
+                             "it was trained on")
         data = load_sb3_zip(path, self.policy, self.opt, map_location=self.device)
+        if raw is not None:
+            self.vec_normalize.from_bytes(raw)
         self._graphs = None          # optimizer state tensors were replaced: recapture
         self.num_timesteps = int(data.get("num_timesteps", 0))
         self.n_updates = int(data.get("n_updates", 0))           # absent in older checkpoints

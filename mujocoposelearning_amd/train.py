@@ -95,6 +95,14 @@ def train_humanoid(env_kwargs: dict, ppo_kwargs: dict, xml_path: str = DEFAULT_X
                          precision=precision, seed=seed * 1_000_003 + start)
     if env.graph_safe:     # device reward: the trainer reads neither the aux row nor the ctrl copy
         env.batch.configure(aux=False, ctrl=False)
+    # env_kwargs["normalize"] (rl-zoo style): True, or a dict of VecNormalize's keywords
+    norm = env_kwargs.get("normalize", False)
+    raw_env = env
+    if norm:
+        from .vec_normalize import VecNormalize
+        nkw = dict(norm) if isinstance(norm, dict) else {}
+        nkw.setdefault("gamma", ppo_kwargs.get("gamma", 0.99))
+        env = VecNormalize(env, **nkw)
     kw = _resolve_activation(ppo_kwargs)
     # env_kwargs["stagger_episodes"] (hsim option, off by default: SubprocVecEnv resets every env
     # together): spread the episode clocks so that short rollouts see every episode phase
@@ -104,7 +112,7 @@ def train_humanoid(env_kwargs: dict, ppo_kwargs: dict, xml_path: str = DEFAULT_X
     if storage_path is not None and rank == 0:
         os.makedirs(storage_path, exist_ok=True)
         model.save(os.path.join(storage_path, "final_model"))     # -> final_model.zip (SB3 layout)
-    env.close()
+    raw_env.close()
     return model
 
 

@@ -26,7 +26,8 @@ STATS_STEPS = 3     # bench.py's stats_of() steps after the timed window
 
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-CODE_OBJECTS = [os.path.join(ROOT, "build", "obj", f"hs_kernels_{p}.o") for p in ("f32", "f64")]   # make -C .../csrc
+# make -C .../csrc (norm: the fused instances with obs normalisation, an object of their own)
+CODE_OBJECTS = [os.path.join(ROOT, "build", "obj", f"hs_kernels_{p}.o") for p in ("f32", "f64", "norm")]
 
 
 def code_object_resources(objs=None):
@@ -112,7 +113,7 @@ def resource_lines(kernel_name, out):
 def resources_report(path=None):
     """profiles/resources_<tag>.md: every step-kernel instance's registers from the code object."""
     res = code_object_resources()
-    lines = ["# Step-kernel resources from the gfx950 code object metadata (build/obj/hs_kernels_{f32,f64}.o)", "",
+    lines = ["# Step-kernel resources from the gfx950 code object metadata (build/obj/hs_kernels_{f32,f64,norm}.o)", "",
              "| kernel | arch VGPR | AGPR | unified | VGPR spilled | SGPR | SGPR spills (to VGPR lanes) | scratch B/lane | LDS B/wg |",
              "|---|---|---|---|---|---|---|---|---|"]
     for k in sorted(res):
