@@ -182,6 +182,18 @@ typedef struct {
 hs_model* hs_model_load(const char* xml_path, char* err, int errsz);
 void hs_model_free(hs_model* m);
 int hs_model_field(const hs_model* m, const char* name, double* out, int n);
+/* The model's lane table: the constants the step kernel reads at a per-lane index, packed by the model
+ * compiler for one precision (HS_FP32 / HS_FP64); the fp64 kernels keep a copy in LDS.  Introspection
+ * for tests, no device needed.
+ * hs_model_lane_table: the table's size in bytes (copied to `out` if nbytes holds it), -1 on error.
+ * hs_lane_layout: the number of entries; for 0 <= i < that, entry i's name (the compiled model's field
+ *   it packs), byte offset in the table, element count and element kind (0: the precision's real, 1: uint32,
+ *   2: int8).  Any output pointer may be NULL.
+ * hs_model_lane_source: the compiled model's field `name` itself, flattened, as doubles: the number of
+ *   values (written if n holds them), -1 if the table has no such entry. */
+int hs_model_lane_table(const hs_model* m, int precision, void* out, int nbytes);
+int hs_lane_layout(int precision, int i, char* name, int namesz, int* offset, int* count, int* kind);
+int hs_model_lane_source(const hs_model* m, int precision, const char* name, double* out, int n);
 
 /* external == NULL: the library allocates (hipMalloc) and owns the buffers.
  * external != NULL: every pointer must be a device buffer of the documented size on `device`;

@@ -100,6 +100,9 @@ def lib():
         "hs_model_load": (vp, [C.c_char_p, C.c_char_p, i]),
         "hs_model_free": (None, [vp]),
         "hs_model_field": (i, [vp, C.c_char_p, vp, i]),
+        "hs_model_lane_table": (i, [vp, i, vp, i]),
+        "hs_lane_layout": (i, [i, i, C.c_char_p, i, vp, vp, vp]),
+        "hs_model_lane_source": (i, [vp, i, C.c_char_p, vp, i]),
         "hs_batch_create": (vp, [vp, i, i, u64, i, vp]),
         "hs_batch_destroy": (None, [vp]),
         "hs_batch_get_info": (i, [vp, vp]),
@@ -181,7 +184,8 @@ def lib():
     return L
 
 
-EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_batch_create", "hs_batch_destroy",
+EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_table", "hs_lane_layout",
+            "hs_model_lane_source", "hs_batch_create", "hs_batch_destroy",
             "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_evaluate", "hs_set_autoreset_noise",
             "hs_physics_step", "hs_state_io", "hs_kinematics", "hs_set_debug", "hs_debug_lose_handoff", "hs_debug_queue_order", "hs_debug_queue_counters", "hs_get_debug", "hs_synchronize", "hs_batch_counters", "hs_gae",
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -388,6 +389,17 @@ done:
 }
 }  // namespace
 
+namespace {
+// f(compiled model) for the precision's DevModel built on the host (no device involved)
+template <typename T, typename F>
+int with_dev_model(const hs_model* m, F&& f) {
+  auto d = std::make_unique<hs::DevModel<T>>();
+  std::string err;
+  if (!hs::build_dev_model<T>(m->host, *d, err)) return fail(err);
+  return f(*d);
+}
+}  // namespace
+
 extern "C" {
 
 const char* hs_last_error(void) { return g_err.c_str(); }
@@ -413,6 +425,37 @@ int hs_model_field(const hs_model* m, const char* name, double* out, int n) {
   int r = hs::model_field(m->host, name, out, n);
   if (r < 0) return fail(std::string("unknown model field '") + name + "'");
   return r;
+}
+
+int hs_model_lane_table(const hs_model* m, int precision, void* out, int nbytes) {
+  if (!m || (precision != HS_FP32 && precision != HS_FP64)) return fail("hs_model_lane_table: bad argument");
+  auto copy = [&](const auto& d) {
+    const int sz = (int)sizeof d.lanes;
+    if (out && nbytes >= sz) std::memcpy(out, &d.lanes, sz);
+    return sz;
+  };
+  return precision == HS_FP64 ? with_dev_model<double>(m, copy) : with_dev_model<float>(m, copy);
+}
+
+int hs_lane_layout(int precision, int i, char* name, int namesz, int* offset, int* count, int* kind) {
+  if (precision != HS_FP32 && precision != HS_FP64) return fail("hs_lane_layout: bad precision");
+  const hs::LaneEntry* e = nullptr;
+  const int n = precision == HS_FP64 ? hs::lane_layout<double>(&e) : hs::lane_layout<float>(&e);
+  if (i < 0 || i >= n) return n;
+  if (name && namesz > 0) { std::strncpy(name, e[i].name, namesz - 1); name[namesz - 1] = 0; }
+  if (offset) *offset = e[i].offset;
+  if (count) *count = e[i].count;
+  if (kind) *kind = e[i].kind;
+  return n;
+}
+
+int hs_model_lane_source(const hs_model* m, int precision, const char* name, double* out, int n) {
+  if (!m || !name || (precision != HS_FP32 && precision != HS_FP64)) return fail("hs_model_lane_source: bad argument");
+  auto get = [&](const auto& d) {
+    const int r = hs::lane_source_field(d, name, out, n);
+    return r < 0 ? fail(std::string("the lane table has no entry '") + name + "'") : r;
+  };
+  return precision == HS_FP64 ? with_dev_model<double>(m, get) : with_dev_model<float>(m, get);
 }
 
 hs_batch* hs_batch_create(const hs_model* m, int n_envs, int device, uint64_t seed, int precision,

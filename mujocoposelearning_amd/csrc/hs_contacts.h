@@ -54,10 +54,10 @@ template <typename T, typename C>
 __device__ __forceinline__ int collide_pair(const Scratch<T, C>& s, const int4 info, const T (&sz)[4], Con<T>& c0,
                                            Con<T>& c1) {
   const int g1 = info.x, g2 = info.y, fn = info.z;
-  const T* p1 = s.u.k.gpos[g1];
-  const T* p2 = s.u.k.gpos[g2];
-  const T* a1 = s.u.k.gax[g1];
-  const T* a2 = s.u.k.gax[g2];
+  const T* p1 = HS_KTAIL(s).gpos[g1];
+  const T* p2 = HS_KTAIL(s).gpos[g2];
+  const T* a1 = HS_KTAIL(s).gax[g1];
+  const T* a2 = HS_KTAIL(s).gax[g2];
   const T r1 = sz[0], h1 = sz[1], r2 = sz[2], h2 = sz[3];
   int n = 0;
   if (fn >= PAIR_SPHERE_SPHERE) {
@@ -126,8 +126,8 @@ __device__ __forceinline__ void store_contact(MPtr<T> m, Scratch<T, C>& s, int s
   s.con_pair[slot] = p;
   const int b1 = m->pair_b1[p], b2 = m->pair_b2[p];
   s.con_bb[slot] = (uint32_t)b1 | (uint32_t)b2 << 8 | (uint32_t)m->pair_dim[p] << 16;
-  s.con_m1[slot] = b1 ? m->body_chainmask[b1] : 0u;
-  s.con_m2[slot] = m->body_chainmask[b2];
+  s.con_m1[slot] = b1 ? HS_LT(C, m).body_chainmask[b1] : 0u;
+  s.con_m2[slot] = HS_LT(C, m).body_chainmask[b2];
   s.con_mu[slot] = m->pair_mu[p];
 }
 
@@ -156,9 +156,9 @@ __device__ __forceinline__ T impedance(CPtr<T> si, T pos, T margin) {
 // ------------------------------------------------------------------ J x for all rows
 // s.vx (generalized vector) -> body spatial velocities -> contact frame velocities
 // ch: this body lane's dof chain mask (body_chainmask, 0 for the world), loaded by the caller
-template <typename T>
+template <typename C, typename T>
 __device__ __forceinline__ uint32_t chain_mask(MPtr<T> m, int sl, int nb) {
-  return (sl > 0 && sl < nb) ? m->body_chainmask[sl] : 0u;
+  return (sl > 0 && sl < nb) ? HS_LT(C, m).body_chainmask[sl] : 0u;
 }
 template <int NV, typename T, typename C>
 __device__ __forceinline__ void map_vx(Scratch<T, C>& s, int sl, int nb, uint32_t ch) {
@@ -206,7 +206,7 @@ __device__ __forceinline__ T row_Jx(MPtr<T> m, const Scratch<T, C>& s, int desc,
   if (kind <= RK_JHI) return coef * s.vx[j];
   if (kind <= RK_THI) {
     T v = 0;
-    for (int w = 0; w < m->ten_nwrap[j]; w++) v += m->ten_wrapcoef[j][w] * s.vx[m->ten_wrapdof[j][w]];
+    for (int w = 0; w < HS_LT(C, m).ten_nwrap[j]; w++) v += HS_LT(C, m).ten_wrapcoef[j][w] * s.vx[HS_LT(C, m).ten_wrapdof[j][w]];
     return coef * v;
   }
   int comp = kind == RK_CN ? 1 : 1 + ((kind - RK_P0) >> 1);
@@ -331,8 +331,8 @@ __device__ __forceinline__ T jtf_lane(MPtr<T> m, const Scratch<T, C>& s, int sl,
   for (int r = s.njl; r < s.nlim; r++) {
     int id = rk_id(s.row_kid[r]);
     T f = rk_kind(s.row_kid[r]) == RK_TLO ? s.row_f[r] : -s.row_f[r];
-    for (int w = 0; w < m->ten_nwrap[id]; w++)
-      if (m->ten_wrapdof[id][w] == sl) acc += f * m->ten_wrapcoef[id][w];
+    for (int w = 0; w < HS_LT(C, m).ten_nwrap[id]; w++)
+      if (HS_LT(C, m).ten_wrapdof[id][w] == sl) acc += f * HS_LT(C, m).ten_wrapcoef[id][w];
   }
   return acc;
 }

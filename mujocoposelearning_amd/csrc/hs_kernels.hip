@@ -19,7 +19,8 @@
 // nv x nv matrices (M, the Newton Hessian, M + h*B) live row-per-lane in VGPRs and are factored
 // with per-half v_readlane broadcasts.  The contact part of the Newton Hessian uses the
 // tree-structured form H_ij += jp_j' U jp_i (O(nv * ncon), no nefc x nv Jacobian in memory).
-// HBM traffic is only the per-env state in/out; the model is read through L1/L2.
+// HBM traffic is only the per-env state in/out; the model is read through L1/L2, and its per-lane
+// constants, in the fp64 resident-tier instances, from an LDS copy made once per launch (hs_lanes.h).
 //
 // Source map (private headers, included in definition order):
 //   hs_lanes.h        capacity tiers, fences, DPP / half-wave primitives, KArgs, small algebra
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
   // single-env schedule (small batches, p.single): env blockIdx.x on the lower half, its mirror on
   // the upper half (same data, so the same control flow), one env per wave
   const bool single = ka->p.single != 0;
+  if constexpr (Resident<T>::LANES) load_lane_table<T>(ka->m);
   step_pair<T, NV, PGS, Resident<T>>(ka, smem, pcache, single ? (int)blockIdx.x : 2 * blockIdx.x + (up ? 1 : 0),
                                      ka->nenv, nullptr, 0, ka->p.nsub, blockIdx.x, single && up);
 }
@@ -125,6 +127,8 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
   // fewer items than waves) leaves like one whose claim does.
   __shared__ int qheld;
   if (threadIdx.x == 0) qheld = (int)blockIdx.x;
+  // the model's lane table: one LDS copy per launch serves every item of the wave (hs_lanes.h)
+  if constexpr (Resident<T>::LANES) load_lane_table<T>(ka->m);
   WSYNC();
   for (;;) {
     const KPtr<T> k = opaque(ka);       // nothing uniform kept live across items
@@ -257,6 +261,7 @@ __global__ __launch_bounds__(64) void kin_kernel(MPtr<T> m, const T* __restrict_
   const int sl = lane & (HL - 1);
   Scratch<T, Resident<T>>& s = smem[up ? 1 : 0];
   for (int k = sl; k < m->nq; k += HL) s.qpos[k] = qpos[k];
+  if constexpr (Resident<T>::LANES) load_lane_table<T>(m);
   WSYNC();
   Stepper<T, NV, Resident<T>> st(m, s, lane);
   st.kinematics();
@@ -266,9 +271,9 @@ __global__ __launch_bounds__(64) void kin_kernel(MPtr<T> m, const T* __restrict_
   out += MAXBODY * 3;
   for (int k = sl; k < nb * 9; k += HL) out[k] = s.u.k.xmat[k / 9][k % 9];
   out += MAXBODY * 9;
-  for (int k = sl; k < ng * 3; k += HL) out[k] = s.u.k.gpos[k / 3][k % 3];
+  for (int k = sl; k < ng * 3; k += HL) out[k] = HS_KTAIL(s).gpos[k / 3][k % 3];
   out += MAXGEOM * 3;
-  for (int k = sl; k < ng * 3; k += HL) out[k] = s.u.k.gax[k / 3][k % 3];
+  for (int k = sl; k < ng * 3; k += HL) out[k] = HS_KTAIL(s).gax[k / 3][k % 3];
   out += MAXGEOM * 3;
   if (sl < 3) out[sl] = s.com[sl];
 }

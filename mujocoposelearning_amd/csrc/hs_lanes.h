@@ -20,17 +20,20 @@ static_assert(MAXDOF == HL, "one dof per sub-lane (lim_row slots, dof masks)");
 
 // Per-env contact / constraint-row capacity of a kernel instance (hs_model.h): the resident tier
 // every launch runs with and the wide tier that re-runs the (rare) envs overflowing it.
-template <int NCON, int NEFC, bool W = false>
+template <int NCON, int NEFC, bool W = false, bool LT = false>
 struct Cap {
   static constexpr int CON = NCON;        // contacts (at most one slot per lane per HL-slot pass)
   static constexpr int EFC = NEFC;        // constraint rows
   static constexpr int RPL = NEFC / HL;   // rows per lane (kept in registers by the row's lane)
   static constexpr bool WIDE = W;         // the wide (re-run) tier
+  static constexpr bool LANES = LT;       // the model's per-lane constants are read from LDS (lanes() below)
   static_assert((NCON % HL == 0 || HL % NCON == 0) && NEFC % HL == 0, "capacity in whole half-waves");
 };
-// resident tier per precision (hs_model.h)
+// resident tier per precision (hs_model.h).  The fp64 instances keep the lane table in LDS: at one wave
+// per SIMD nothing hides the latency of its reads through vector memory.  The fp32 engine (its direct
+// kernel fills LDS: 8 workgroups of 20,480 B per CU) and the wide tier read the model as before.
 template <typename T>
-using Resident = std::conditional_t<sizeof(T) == 8, Cap<MAXCON_F64, MAXEFC_F64>, Cap<MAXCON, MAXEFC>>;
+using Resident = std::conditional_t<sizeof(T) == 8, Cap<MAXCON_F64, MAXEFC_F64, false, true>, Cap<MAXCON, MAXEFC>>;
 using Wide = Cap<MAXCON_WIDE, MAXEFC_WIDE, true>;
 
 // scheduling fence: keeps the machine scheduler from hoisting loads across iterations of fully
@@ -174,6 +177,56 @@ template <typename T>
 using MPtr = const __attribute__((address_space(4))) DevModel<T>*;
 template <typename T>
 using CPtr = const __attribute__((address_space(4))) T*;      // pointer into the model
+// The wave's LDS copy of the model's lane table (hs_model.h LaneTable; one workgroup = one wave, both
+// halves step envs of the same model).  A function-scope static: only the kernels whose instances
+// call lanes() below with C::LANES allocate it, and every access is an LDS instruction at a constant
+// address (no pointer to launder or keep live).
+template <typename T>
+__device__ __forceinline__ LaneTable<T>& lane_table() {
+  __shared__ LaneTable<T> tab;
+  return tab;
+}
+// Once per launch, before the wave's first item: every lane copies 16-byte pieces, all loads in flight
+// before the first store (one wait).
+template <typename T>
+__device__ __forceinline__ void load_lane_table(MPtr<T> m) {
+  constexpr int N = (int)(sizeof(LaneTable<T>) / 16), PER = (N + WAVE - 1) / WAVE;
+  static_assert(sizeof(LaneTable<T>) % 16 == 0 && alignof(LaneTable<T>) == 16, "16-byte pieces");
+  typedef uint32_t Piece __attribute__((ext_vector_type(4)));
+  CPtr<Piece> src = (CPtr<Piece>)&m->lanes;
+  Piece* dst = reinterpret_cast<Piece*>(&lane_table<T>());
+  const int lane = threadIdx.x;
+  Piece v[PER];
+#pragma unroll
+  for (int i = 0; i < PER; i++) {
+    const int k = lane + i * WAVE;
+    v[i] = src[k < N ? k : N - 1];
+  }
+#pragma unroll
+  for (int i = 0; i < PER; i++) {
+    const int k = lane + i * WAVE;
+    if (k < N) dst[k] = v[i];
+  }
+  asm volatile("" ::: "memory");
+}
+// Where an instance reads the model's per-lane constants: lanes<C>(m).field[i] is the LDS copy for
+// C::LANES and m->field[i] otherwise (LaneTable and DevModel name the fields alike).
+template <typename C, typename T>
+__device__ __forceinline__ decltype(auto) lanes(MPtr<T> m) {
+  if constexpr (C::LANES) return (lane_table<T>());
+  else return (*m);
+}
+// The phases spell these reads HS_LT(C, m).field[i].  The fp32 pass over the kernels (HS_ONLY_F32) has
+// no instance with a lane table, and there the macro is the plain member access it replaces, so that
+// the fp32 code object stays byte for byte what it is without the table (the compiler's register
+// allocation for the fp32 direct kernel turns on less).  HS_KTAIL(s): the same for Scratch::ktail().
+#ifdef HS_ONLY_F32
+#define HS_LT(C, m) (*(m))
+#define HS_KTAIL(s) (s).u.k
+#else
+#define HS_LT(C, m) lanes<C>(m)
+#define HS_KTAIL(s) (s).ktail()
+#endif
 // All launch arguments travel as ONE by-value struct, so it sits at offset 0 of the kernarg
 // segment.  The kernel reads it through an opaque()-laundered constant-address-space pointer to
 // that segment: every use is a fresh scalar load (scalar cache) instead of ~80 SGPRs kept live

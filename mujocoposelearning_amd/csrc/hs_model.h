@@ -54,6 +54,35 @@ enum JointType { JNT_FREE = 0, JNT_HINGE = 3 };
 enum PairFn { PAIR_PLANE_SPHERE = 0, PAIR_PLANE_CAPSULE = 1, PAIR_SPHERE_SPHERE = 2, PAIR_SPHERE_CAPSULE = 3,
               PAIR_CAPSULE_CAPSULE = 4 };
 
+// Lane table: the model constants the step kernel reads at a per-lane index (m->field[sl], m->field[an
+// index loaded a moment ago]), packed for LDS.  The fp64 resident-tier kernels copy it into LDS once per
+// launch and read it there instead of through the vector L1/L2 path every substep (hs_lanes.h
+// lanes()); every other instance reads the DevModel fields of the same names.  Indices are stored as
+// int8_t (every capacity above is < 128; -1 = none).  Filled by build_dev_model from the DevModel's own
+// fields, so it belongs to the model; hs_lane_layout (mjcf.cpp) describes it entry by entry.
+template <typename T>
+struct alignas(16) LaneTable {
+  // T-valued per-dof / per-actuator / per-joint / per-body scalars
+  T dof_armature[MAXDOF], dof_damping[MAXDOF], dof_stiffness[MAXDOF], dof_springref[MAXDOF], dof_invweight0[MAXDOF];
+  T act_gear[MAXU], act_ctrlrange[MAXU][2];
+  T jnt_range[MAXJNT][2], jnt_margin[MAXJNT];
+  T body_mass[MAXBODY], body_invweight_tran[MAXBODY];
+  T ten_wrapcoef[MAXTEN][MAXWRAP], ten_range[MAXTEN][2];
+  T qpos0[MAXQ], body_pos[MAXBODY][3], body_quat[MAXBODY][4];
+  // masks
+  uint32_t body_chainmask[MAXBODY], body_descmask[MAXBODY], dof_ancmask[MAXDOF], dof_dotmask[MAXDOF];
+  // the integers that head a dependent chain
+  int8_t body_depth[MAXBODY], body_parentid[MAXBODY], body_jntadr[MAXBODY], body_jntnum[MAXBODY];
+  int8_t jnt_type[MAXJNT], jnt_qposadr[MAXJNT], jnt_dofadr[MAXJNT], jnt_limited[MAXJNT];
+  int8_t dof_bodyid[MAXDOF], dof_jntid[MAXDOF], dof_qposadr[MAXDOF], dof_actuator[MAXDOF];
+  int8_t geom_bodyid[MAXGEOM], act_ctrllimited[MAXU];
+  int8_t ten_nwrap[MAXTEN], ten_limited[MAXTEN], ten_wrapdof[MAXTEN][MAXWRAP], ten_wrapqadr[MAXTEN][MAXWRAP];
+};
+static_assert(MAXQ < 128 && MAXDOF < 128 && MAXJNT < 128 && MAXBODY < 128 && MAXU < 128, "lane table indices are int8_t");
+// 4 fp64 workgroups per CU hold 40,960 B of LDS each; the fp64 queue instance needs 35,752 B without the
+// table (38,568 less the 2,816 B that Scratch reclaims for it, hs_scratch.h)
+static_assert(sizeof(LaneTable<double>) <= 5208, "fp64 lane table: 4 workgroups per CU");
+
 template <typename T>
 struct DevModel {
   int nq, nv, nu, nbody, njnt, ngeom, ntendon, npair, nlevel, nhinge_limited;
@@ -95,6 +124,7 @@ struct DevModel {
   T ten_margin[MAXTEN], ten_invweight0[MAXTEN];
   T qpos0[MAXQ];
   T pgs_tol;                          // <option tolerance> (the PGS stopping rule; Newton solves exactly)
+  LaneTable<T> lanes;                 // the per-lane constants above once more, packed (last: no other offset moves)
 };
 
 }  // namespace hs

@@ -13,6 +13,10 @@ enum RowKind { RK_JLO = 0, RK_JHI = 1, RK_TLO = 2, RK_THI = 3, RK_CN = 4, RK_P0 
 __device__ __forceinline__ int rk_kind(int kid) { return kid >> 16; }
 __device__ __forceinline__ int rk_id(int kid) { return kid & 0xffff; }
 
+// kinematics' joint anchors / axes and geom frames (read until the end of collision)
+template <typename T>
+struct KinTail { T xanchor[MAXJNT][3]; T xaxis[MAXJNT][3]; T gpos[MAXGEOM][3]; T gax[MAXGEOM][3]; };
+
 template <typename T, typename C>
 struct Scratch {
   T qpos[MAXQ];
@@ -44,8 +48,24 @@ struct Scratch {
   T row_f[C::EFC];
   int ncon, nefc, nlim, njl;   // njl: joint-limit rows (tendon rows are [njl, nlim))
   int niter;                   // this env's Newton iterations (the wave's loop runs for the slower env)
-  struct Kin { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; T xanchor[MAXJNT][3];
-               T xaxis[MAXJNT][3]; T gpos[MAXGEOM][3]; T gax[MAXGEOM][3]; };
+  // Instances with the lane table in LDS (C::LANES) make room for it: their KinTail lies over con_v /
+  // con_U / con_F, which are first written in rows() (map_vx) and the solve (contact_aggregates), after
+  // collision's last read of the tail, and last read in post_constraint, before the next substep's
+  // kinematics (store_contact writes none of them).  The union's largest member is then the RNE one.
+  struct KinHead { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; };
+  struct KinFull { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; T xanchor[MAXJNT][3];
+                   T xaxis[MAXJNT][3]; T gpos[MAXGEOM][3]; T gax[MAXGEOM][3]; };
+  using Kin = std::conditional_t<C::LANES, KinHead, KinFull>;
+  static_assert(!C::LANES || sizeof(KinTail<T>) <= sizeof(T) * C::CON * 12, "KinTail fits con_v, con_U, con_F");
+  // xanchor, xaxis, gpos, gax: wherever the instance keeps them
+  __device__ __forceinline__ decltype(auto) ktail() {
+    if constexpr (C::LANES) return (*reinterpret_cast<KinTail<T>*>(&con_v[0][0]));
+    else return (u.k);
+  }
+  __device__ __forceinline__ decltype(auto) ktail() const {
+    if constexpr (C::LANES) return (*reinterpret_cast<const KinTail<T>*>(&con_v[0][0]));
+    else return (u.k);
+  }
   union {   // phase-local arrays (aliased)
     Kin k;                                                        // kinematics + collision
     struct { T crb[MAXBODY][10]; T buf[MAXDOF][6]; } c;          // composite rigid body

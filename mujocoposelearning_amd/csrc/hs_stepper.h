@@ -72,14 +72,14 @@ struct Stepper {
     T pl[3] = {0, 0, 0}, ql[4] = {1, 0, 0, 0};
     T anl[MAXJPB][3], axl[MAXJPB][3];
     if (isb) {
-      depth = m->body_depth[b];
-      par = m->body_parentid[b];
-      ja = m->body_jntadr[b];
-      jn = m->body_jntnum[b];
-      isfree = jn == 1 && m->jnt_type[ja] == JNT_FREE;
-      fqa = m->jnt_qposadr[ja];
-      for (int k = 0; k < 3; k++) pl[k] = m->body_pos[b][k];
-      for (int k = 0; k < 4; k++) ql[k] = m->body_quat[b][k];
+      depth = HS_LT(C, m).body_depth[b];
+      par = HS_LT(C, m).body_parentid[b];
+      ja = HS_LT(C, m).body_jntadr[b];
+      jn = HS_LT(C, m).body_jntnum[b];
+      isfree = jn == 1 && HS_LT(C, m).jnt_type[ja] == JNT_FREE;
+      fqa = HS_LT(C, m).jnt_qposadr[ja];
+      for (int k = 0; k < 3; k++) pl[k] = HS_LT(C, m).body_pos[b][k];
+      for (int k = 0; k < 4; k++) ql[k] = HS_LT(C, m).body_quat[b][k];
     }
     if (isfree) {
       for (int k = 0; k < 3; k++) pl[k] = s.qpos[fqa + k];
@@ -92,8 +92,8 @@ struct Stepper {
       T jp[3], jx[3], ang = 0;
       for (int k = 0; k < 3; k++) { jp[k] = use ? m->jnt_pos[j][k] : T(0); jx[k] = use ? m->jnt_axis[j][k] : T(0); }
       if (use) {
-        int qa = m->jnt_qposadr[j];
-        ang = s.qpos[qa] - m->qpos0[qa];
+        int qa = HS_LT(C, m).jnt_qposadr[j];
+        ang = s.qpos[qa] - HS_LT(C, m).qpos0[qa];
       }
       T sn, cs;
       sincos_t(T(0.5) * ang, sn, cs);
@@ -133,7 +133,7 @@ struct Stepper {
     }
     if (isb) {
       if (isfree) {
-        for (int k = 0; k < 3; k++) { s.u.k.xanchor[ja][k] = s.u.k.xpos[b][k]; s.u.k.xaxis[ja][k] = m->jnt_axis[ja][k]; }
+        for (int k = 0; k < 3; k++) { HS_KTAIL(s).xanchor[ja][k] = s.u.k.xpos[b][k]; HS_KTAIL(s).xaxis[ja][k] = m->jnt_axis[ja][k]; }
       } else {
         const T* Rp = s.u.k.xmat[par];
         const T* xp = s.u.k.xpos[par];
@@ -143,26 +143,26 @@ struct Stepper {
             T an[3], ax[3];
             mv3(Rp, anl[jj], an);
             mv3(Rp, axl[jj], ax);
-            for (int k = 0; k < 3; k++) { s.u.k.xanchor[ja + jj][k] = xp[k] + an[k]; s.u.k.xaxis[ja + jj][k] = ax[k]; }
+            for (int k = 0; k < 3; k++) { HS_KTAIL(s).xanchor[ja + jj][k] = xp[k] + an[k]; HS_KTAIL(s).xaxis[ja + jj][k] = ax[k]; }
           }
         }
       }
     }
     if (sl < m->ngeom) {
-      int g = sl, gb = m->geom_bodyid[g];
+      int g = sl, gb = HS_LT(C, m).geom_bodyid[g];
       T gp[3] = {m->geom_pos[g][0], m->geom_pos[g][1], m->geom_pos[g][2]};
       T gz[3] = {m->geom_zaxis[g][0], m->geom_zaxis[g][1], m->geom_zaxis[g][2]};
       T w[3];
       mv3(s.u.k.xmat[gb], gp, w);
-      for (int k = 0; k < 3; k++) s.u.k.gpos[g][k] = s.u.k.xpos[gb][k] + w[k];
-      mv3(s.u.k.xmat[gb], gz, s.u.k.gax[g]);
+      for (int k = 0; k < 3; k++) HS_KTAIL(s).gpos[g][k] = s.u.k.xpos[gb][k] + w[k];
+      mv3(s.u.k.xmat[gb], gz, HS_KTAIL(s).gax[g]);
     }
     T mx = 0, my = 0, mz = 0, xi[3] = {0, 0, 0};
     if (b > 0 && b < nb) {
       T ip[3] = {m->body_ipos[b][0], m->body_ipos[b][1], m->body_ipos[b][2]}, w[3];
       mv3(s.u.k.xmat[b], ip, w);
       for (int k = 0; k < 3; k++) xi[k] = s.u.k.xpos[b][k] + w[k];
-      T mb = m->body_mass[b];
+      T mb = HS_LT(C, m).body_mass[b];
       mx = mb * xi[0]; my = mb * xi[1]; mz = mb * xi[2];
     }
     // mj_comPos: single kinematic tree -> subtree_com[root] == subtree_com[0] == whole-model COM
@@ -184,7 +184,7 @@ struct Stepper {
       Ic[4] = A[0] * R[6] + A[1] * R[7] + A[2] * R[8];
       Ic[5] = A[3] * R[6] + A[4] * R[7] + A[5] * R[8];
       T d[3] = {xi[0] - c0, xi[1] - c1, xi[2] - c2};
-      T mass = m->body_mass[b];
+      T mass = HS_LT(C, m).body_mass[b];
       T* ci = s.cinert[b];
       ci[0] = Ic[0] + mass * (d[1] * d[1] + d[2] * d[2]);
       ci[1] = Ic[1] + mass * (d[0] * d[0] + d[2] * d[2]);
@@ -198,12 +198,12 @@ struct Stepper {
       for (int k = 0; k < 10; k++) s.cinert[0][k] = 0;
     for (int k = 0; k < 6; k++) cd[k] = 0;
     if (sl < NV) {   // cdof (mju_dofCom)
-      int j = m->dof_jntid[sl], db = m->dof_bodyid[sl];
-      T off[3] = {c0 - s.u.k.xanchor[j][0], c1 - s.u.k.xanchor[j][1], c2 - s.u.k.xanchor[j][2]};
+      int j = HS_LT(C, m).dof_jntid[sl], db = HS_LT(C, m).dof_bodyid[sl];
+      T off[3] = {c0 - HS_KTAIL(s).xanchor[j][0], c1 - HS_KTAIL(s).xanchor[j][1], c2 - HS_KTAIL(s).xanchor[j][2]};
       T ax[3];
       bool lin = false;
-      if (m->jnt_type[j] == JNT_FREE) {
-        int k = sl - m->jnt_dofadr[j];
+      if (HS_LT(C, m).jnt_type[j] == JNT_FREE) {
+        int k = sl - HS_LT(C, m).jnt_dofadr[j];
         if (k < 3) {   // no dynamic indexing of register arrays (it would demote the Stepper to scratch)
           lin = true;
           cd[3] = k == 0 ? T(1) : T(0); cd[4] = k == 1 ? T(1) : T(0); cd[5] = k == 2 ? T(1) : T(0);
@@ -212,7 +212,7 @@ struct Stepper {
           ax[0] = s.u.k.xmat[db][c]; ax[1] = s.u.k.xmat[db][3 + c]; ax[2] = s.u.k.xmat[db][6 + c];
         }
       } else {
-        ax[0] = s.u.k.xaxis[j][0]; ax[1] = s.u.k.xaxis[j][1]; ax[2] = s.u.k.xaxis[j][2];
+        ax[0] = HS_KTAIL(s).xaxis[j][0]; ax[1] = HS_KTAIL(s).xaxis[j][1]; ax[2] = HS_KTAIL(s).xaxis[j][2];
       }
       if (!lin) {
         cd[0] = ax[0]; cd[1] = ax[1]; cd[2] = ax[2];
@@ -267,7 +267,7 @@ struct Stepper {
   __device__ __forceinline__ void mass_matrix() {
     phase_begin();
     if (sl > 0 && sl < nb) {
-      const uint32_t dm = m->body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
+      const uint32_t dm = HS_LT(C, m).body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
       T a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       for_bits<T>(dm, [&](int c) { Vals<T, 10> r; for (int k = 0; k < 10; k++) r.v[k] = s.cinert[c][k]; return r; },
                   [&](int, const Vals<T, 10>& r) { for (int k = 0; k < 10; k++) a[k] += r.v[k]; });   // the subtree's bodies, ascending
@@ -278,10 +278,10 @@ struct Stepper {
     uint32_t anci = 0;
     T arm = 0;
     if (sl < NV) {
-      mul_inert(s.u.c.crb[m->dof_bodyid[sl]], cd, bf);
+      mul_inert(s.u.c.crb[HS_LT(C, m).dof_bodyid[sl]], cd, bf);
       for (int k = 0; k < 6; k++) s.u.c.buf[sl][k] = bf[k];
-      anci = m->dof_ancmask[sl];
-      arm = m->dof_armature[sl];
+      anci = HS_LT(C, m).dof_ancmask[sl];
+      arm = HS_LT(C, m).dof_armature[sl];
     }
     WSYNC();
     // one column per scheduling group (2 or 3 measured the same)
@@ -316,14 +316,14 @@ struct Stepper {
     if (sl < nb) {
       T v[6] = {0, 0, 0, 0, 0, 0};
       if (sl > 0) {
-        const uint32_t ch = m->body_chainmask[sl];
+        const uint32_t ch = HS_LT(C, m).body_chainmask[sl];
         for_bits<T>(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
                     [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) v[k] = fma(r.v[k], r.x, v[k]); });   // the chain's dofs, ascending
       }
       for (int k = 0; k < 6; k++) s.cvel[sl][k] = v[k];
     }
     if (sl < NV) {
-      const uint32_t dm = m->dof_dotmask[sl];
+      const uint32_t dm = HS_LT(C, m).dof_dotmask[sl];
       T v[6] = {0, 0, 0, 0, 0, 0}, cdd[6];
       for_bits<T>(dm, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
                   [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) v[k] = fma(r.v[k], r.x, v[k]); });   // ascending, set bits only
@@ -332,7 +332,7 @@ struct Stepper {
     }
     WSYNC();
     if (sl > 0 && sl < nb) {   // RNE: cacc, cfrc_body
-      const uint32_t ch = m->body_chainmask[sl];
+      const uint32_t ch = HS_LT(C, m).body_chainmask[sl];
       T a[6] = {0, 0, 0, -m->gravity[0], -m->gravity[1], -m->gravity[2]};
       for_bits<T>(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cdofdot[j][k]; return r; },
                   [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) a[k] = fma(r.v[k], r.x, a[k]); });   // the chain's dofs, ascending
@@ -344,7 +344,7 @@ struct Stepper {
     }
     WSYNC();
     if (sl > 0 && sl < nb) {   // subtree sums of cfrc_body
-      const uint32_t dm = m->body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
+      const uint32_t dm = HS_LT(C, m).body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
       T a[6] = {0, 0, 0, 0, 0, 0};
       for_bits<T>(dm, [&](int c) { Vals<T, 6> r; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cfrc[c][k]; return r; },
                   [&](int, const Vals<T, 6>& r) { for (int k = 0; k < 6; k++) a[k] += r.v[k]; });   // the subtree's bodies, ascending
@@ -354,15 +354,15 @@ struct Stepper {
     fsmooth = 0;
     qfa = 0;
     if (sl < NV) {
-      T bias = dot6(cd, s.u.r.csub[m->dof_bodyid[sl]]);
-      int qa = m->dof_qposadr[sl];
-      T pas = -m->dof_damping[sl] * s.qvel[sl];
-      if (qa >= 0) pas -= m->dof_stiffness[sl] * (s.qpos[qa] - m->dof_springref[sl]);
-      int u = m->dof_actuator[sl];
+      T bias = dot6(cd, s.u.r.csub[HS_LT(C, m).dof_bodyid[sl]]);
+      int qa = HS_LT(C, m).dof_qposadr[sl];
+      T pas = -HS_LT(C, m).dof_damping[sl] * s.qvel[sl];
+      if (qa >= 0) pas -= HS_LT(C, m).dof_stiffness[sl] * (s.qpos[qa] - HS_LT(C, m).dof_springref[sl]);
+      int u = HS_LT(C, m).dof_actuator[sl];
       if (u >= 0) {
         T c = s.ctrl[u];
-        if (m->act_ctrllimited[u]) c = fmin(m->act_ctrlrange[u][1], fmax(m->act_ctrlrange[u][0], c));
-        qfa = m->act_gear[u] * c;
+        if (HS_LT(C, m).act_ctrllimited[u]) c = fmin(HS_LT(C, m).act_ctrlrange[u][1], fmax(HS_LT(C, m).act_ctrlrange[u][0], c));
+        qfa = HS_LT(C, m).act_gear[u] * c;
       }
       fsmooth = pas - bias + qfa;
     }
@@ -372,16 +372,16 @@ struct Stepper {
   // mj_makeConstraint + mj_makeImpedance + reference (aref); row q of this lane: r = sl + 32 q
   __device__ __forceinline__ int rows(T (&D)[C::RPL], T (&ar)[C::RPL], int (&rd)[C::RPL], T (&rc)[C::RPL]) {
     phase_begin();
-    damp = sl < NV ? m->dof_damping[sl] : T(0);
+    damp = sl < NV ? HS_LT(C, m).dof_damping[sl] : T(0);
     int overflow = 0;
     int ncon = s.ncon;
     int nrow = 0;
     {   // joint limits (lower side first, MuJoCo side = -1 then +1)
       bool lo = false, hi = false;
-      if (sl < m->njnt && m->jnt_limited[sl]) {
-        T q = s.qpos[m->jnt_qposadr[sl]];
-        lo = (q - m->jnt_range[sl][0]) < m->jnt_margin[sl];
-        hi = (m->jnt_range[sl][1] - q) < m->jnt_margin[sl];
+      if (sl < m->njnt && HS_LT(C, m).jnt_limited[sl]) {
+        T q = s.qpos[HS_LT(C, m).jnt_qposadr[sl]];
+        lo = (q - HS_LT(C, m).jnt_range[sl][0]) < HS_LT(C, m).jnt_margin[sl];
+        hi = (HS_LT(C, m).jnt_range[sl][1] - q) < HS_LT(C, m).jnt_margin[sl];
       }
       uint32_t ml = hballot(lo, up), mh = hballot(hi, up);
       int pre = below(ml, sl) + below(mh, sl);
@@ -390,16 +390,16 @@ struct Stepper {
       nrow = __popc(ml) + __popc(mh);
       s.lim_row[sl] = 0;                       // MAXDOF == HL: one slot per sub-lane
       if (lo || hi)
-        s.lim_row[m->jnt_dofadr[sl]] = (uint16_t)((lo ? pre + 1 : 0) | (hi ? (pre + lo + 1) << 8 : 0));
+        s.lim_row[HS_LT(C, m).jnt_dofadr[sl]] = (uint16_t)((lo ? pre + 1 : 0) | (hi ? (pre + lo + 1) << 8 : 0));
     }
     const int njl = nrow;
     {   // tendon limits
       bool lo = false, hi = false;
-      if (sl < m->ntendon && m->ten_limited[sl]) {
+      if (sl < m->ntendon && HS_LT(C, m).ten_limited[sl]) {
         T L = 0;
-        for (int w = 0; w < m->ten_nwrap[sl]; w++) L += m->ten_wrapcoef[sl][w] * s.qpos[m->ten_wrapqadr[sl][w]];
-        lo = (L - m->ten_range[sl][0]) < m->ten_margin[sl];
-        hi = (m->ten_range[sl][1] - L) < m->ten_margin[sl];
+        for (int w = 0; w < HS_LT(C, m).ten_nwrap[sl]; w++) L += HS_LT(C, m).ten_wrapcoef[sl][w] * s.qpos[HS_LT(C, m).ten_wrapqadr[sl][w]];
+        lo = (L - HS_LT(C, m).ten_range[sl][0]) < m->ten_margin[sl];
+        hi = (HS_LT(C, m).ten_range[sl][1] - L) < m->ten_margin[sl];
       }
       uint32_t ml = hballot(lo, up), mh = hballot(hi, up);
       int pre = nrow + below(ml, sl) + below(mh, sl);
@@ -446,7 +446,7 @@ struct Stepper {
     if (sl == 0) { s.ncon = ncon; s.nefc = nrow; s.nlim = nlim; s.njl = njl; }
     if (sl < NV) s.vx[sl] = s.qvel[sl];
     WSYNC();
-    map_vx<NV>(s, sl, nb, chain_mask(m, sl, nb));     // row velocities J qvel for aref
+    map_vx<NV>(s, sl, nb, chain_mask<C>(m, sl, nb));     // row velocities J qvel for aref
 #pragma unroll
     for (int q = 0; q < C::RPL; q++) {
       int r = sl + HL * q;
@@ -462,18 +462,18 @@ struct Stepper {
         CPtr<T> sr;
         CPtr<T> si;
         if (kind <= RK_JHI) {
-          T qv = s.qpos[m->jnt_qposadr[id]];
-          pos = kind == RK_JLO ? qv - m->jnt_range[id][0] : m->jnt_range[id][1] - qv;
-          margin = m->jnt_margin[id];
+          T qv = s.qpos[HS_LT(C, m).jnt_qposadr[id]];
+          pos = kind == RK_JLO ? qv - HS_LT(C, m).jnt_range[id][0] : HS_LT(C, m).jnt_range[id][1] - qv;
+          margin = HS_LT(C, m).jnt_margin[id];
           sr = m->jnt_solref[id]; si = m->jnt_solimp[id];
-          int dof = m->jnt_dofadr[id];
-          dA = m->dof_invweight0[dof];
+          int dof = HS_LT(C, m).jnt_dofadr[id];
+          dA = HS_LT(C, m).dof_invweight0[dof];
           rd[q] = (kind << 16) | dof;
           rc[q] = kind == RK_JLO ? T(1) : T(-1);
         } else if (kind <= RK_THI) {
           T L = 0;
-          for (int w = 0; w < m->ten_nwrap[id]; w++) L += m->ten_wrapcoef[id][w] * s.qpos[m->ten_wrapqadr[id][w]];
-          pos = kind == RK_TLO ? L - m->ten_range[id][0] : m->ten_range[id][1] - L;
+          for (int w = 0; w < HS_LT(C, m).ten_nwrap[id]; w++) L += HS_LT(C, m).ten_wrapcoef[id][w] * s.qpos[HS_LT(C, m).ten_wrapqadr[id][w]];
+          pos = kind == RK_TLO ? L - HS_LT(C, m).ten_range[id][0] : HS_LT(C, m).ten_range[id][1] - L;
           margin = m->ten_margin[id];
           sr = m->ten_solref[id]; si = m->ten_solimp[id];
           dA = m->ten_invweight0[id];
@@ -486,7 +486,7 @@ struct Stepper {
           margin = m->pair_margin[p];
           sr = m->pair_solref[p]; si = m->pair_solimp[p];
           const uint32_t bb = s.con_bb[id];
-          T tran = m->body_invweight_tran[bb & 0xff] + m->body_invweight_tran[(bb >> 8) & 0xff];
+          T tran = HS_LT(C, m).body_invweight_tran[bb & 0xff] + HS_LT(C, m).body_invweight_tran[(bb >> 8) & 0xff];
           T mu = s.con_mu[id];
           dA = kind == RK_CN ? tran : tran + mu * mu * tran;
           // pyramidal edges share one R: Rpy = 2 mu^2 R_edge / impratio (impratio = 1, enforced by the
@@ -530,8 +530,8 @@ struct Stepper {
     bool vr[C::RPL];
 #pragma unroll
     for (int q = 0; q < C::RPL; q++) vr[q] = sl + HL * q < nefc;
-    const uint32_t anci = sl < NV ? m->dof_ancmask[sl] : 0u;
-    const uint32_t bch = chain_mask(m, sl, nb);     // loaded once per solve (map_vx per iteration)
+    const uint32_t anci = sl < NV ? HS_LT(C, m).dof_ancmask[sl] : 0u;
+    const uint32_t bch = chain_mask<C>(m, sl, nb);     // loaded once per solve (map_vx per iteration)
     const T scale = m->newton_scale;
     if (sl < NV) s.vx[sl] = x;
     WSYNC();
@@ -655,8 +655,8 @@ struct Stepper {
               int kind = rk_kind(kid), id = rk_id(kid);
               Dr = s.row_D[r];
               if (kind == RK_TLO || kind == RK_THI) {
-                for (int w = 0; w < m->ten_nwrap[id]; w++)
-                  if (m->ten_wrapdof[id][w] == sl) jr += m->ten_wrapcoef[id][w];
+                for (int w = 0; w < HS_LT(C, m).ten_nwrap[id]; w++)
+                  if (HS_LT(C, m).ten_wrapdof[id][w] == sl) jr += HS_LT(C, m).ten_wrapcoef[id][w];
                 if (kind == RK_THI) jr = -jr;
               } else {
                 int in2 = bit(s.con_m2[id], sl), in1 = bit(s.con_m1[id], sl);
@@ -773,11 +773,11 @@ struct Stepper {
     if (sl >= NV) return T(0);
     const int kid = s.row_kid[r];
     const int kind = rk_kind(kid), id = rk_id(kid);
-    if (kind <= RK_JHI) return m->jnt_dofadr[id] == sl ? (kind == RK_JLO ? T(1) : T(-1)) : T(0);
+    if (kind <= RK_JHI) return HS_LT(C, m).jnt_dofadr[id] == sl ? (kind == RK_JLO ? T(1) : T(-1)) : T(0);
     if (kind <= RK_THI) {
       T v = 0;
-      for (int w = 0; w < m->ten_nwrap[id]; w++)
-        if (m->ten_wrapdof[id][w] == sl) v += m->ten_wrapcoef[id][w];
+      for (int w = 0; w < HS_LT(C, m).ten_nwrap[id]; w++)
+        if (HS_LT(C, m).ten_wrapdof[id][w] == sl) v += HS_LT(C, m).ten_wrapcoef[id][w];
       return kind == RK_TLO ? v : -v;
     }
     const int in2 = bit(s.con_m2[id], sl), in1 = bit(s.con_m1[id], sl);
@@ -806,7 +806,7 @@ struct Stepper {
                                             const int (&rd)[C::RPL], const T (&rc)[C::RPL], PgsCache<T, C>& pc) {
     phase_begin();
     const int nefc = s.nefc;
-    const uint32_t bch = chain_mask(m, sl, nb);
+    const uint32_t bch = chain_mask<C>(m, sl, nb);
     const T fs = sl < NV ? fsmooth : T(0);
     constexpr int NC = PgsCache<T, C>::NC;
     constexpr int LA = PGS_LA;
@@ -1031,7 +1031,7 @@ struct Stepper {
     }
     WSYNC();
     if (b < nb) {
-      const uint32_t dm = b == 0 ? ((1u << nb) - 2u) : m->body_descmask[b];
+      const uint32_t dm = b == 0 ? ((1u << nb) - 2u) : HS_LT(C, m).body_descmask[b];
       T a[3] = {0, 0, 0}, ms = 0;
       for (int c = 1; c < nb; c++)
         if (bit(dm, c)) {
@@ -1060,8 +1060,8 @@ struct Stepper {
     if (sl < NV) s.qvel[sl] += h * a;
     WSYNC();
     if (sl < m->njnt) {
-      int qa = m->jnt_qposadr[sl], da = m->jnt_dofadr[sl];
-      if (m->jnt_type[sl] == JNT_FREE) {
+      int qa = HS_LT(C, m).jnt_qposadr[sl], da = HS_LT(C, m).jnt_dofadr[sl];
+      if (HS_LT(C, m).jnt_type[sl] == JNT_FREE) {
         for (int k = 0; k < 3; k++) s.qpos[qa + k] += h * s.qvel[da + k];
         T w[3] = {s.qvel[da + 3], s.qvel[da + 4], s.qvel[da + 5]};
         T ang = h * normalize3(w);

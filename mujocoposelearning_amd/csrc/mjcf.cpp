@@ -990,6 +990,64 @@ ContactBound contact_bound(const HostModel& m) {
   return b;
 }
 
+// ---------------------------------------------------------------------------------- lane table
+// every field of LaneTable, by the name it has in both LaneTable and DevModel
+#define HS_LANE_FIELDS(X)                                                                                     \
+  X(dof_armature) X(dof_damping) X(dof_stiffness) X(dof_springref) X(dof_invweight0) X(act_gear)              \
+  X(act_ctrlrange) X(jnt_range) X(jnt_margin) X(body_mass) X(body_invweight_tran) X(ten_wrapcoef)             \
+  X(ten_range) X(qpos0) X(body_pos) X(body_quat) X(body_chainmask) X(body_descmask) X(dof_ancmask)            \
+  X(dof_dotmask) X(body_depth) X(body_parentid) X(body_jntadr) X(body_jntnum) X(jnt_type) X(jnt_qposadr)      \
+  X(jnt_dofadr) X(jnt_limited) X(dof_bodyid) X(dof_jntid) X(dof_qposadr) X(dof_actuator) X(geom_bodyid)       \
+  X(act_ctrllimited) X(ten_nwrap) X(ten_limited) X(ten_wrapdof) X(ten_wrapqadr)
+
+namespace {
+template <typename A>
+using Elem = std::remove_all_extents_t<A>;
+template <typename A>
+constexpr int elems() { return (int)(sizeof(A) / sizeof(Elem<A>)); }
+template <typename E>
+constexpr int lane_kind() {
+  return std::is_floating_point<E>::value ? LANE_REAL : (sizeof(E) == 4 ? LANE_U32 : LANE_I8);
+}
+// dst = src element by element (arrays of the same shape, flattened)
+template <typename DA, typename SA>
+void lane_copy(DA& dst, const SA& src) {
+  static_assert(elems<DA>() == elems<SA>(), "lane table field and model field have the same shape");
+  Elem<DA>* d = reinterpret_cast<Elem<DA>*>(&dst);
+  const Elem<SA>* s = reinterpret_cast<const Elem<SA>*>(&src);
+  for (int i = 0; i < elems<DA>(); i++) d[i] = (Elem<DA>)s[i];
+}
+}  // namespace
+
+template <typename T>
+int lane_layout(const LaneEntry** entries) {
+#define X(f) {#f, (int)offsetof(LaneTable<T>, f), elems<decltype(LaneTable<T>::f)>(), lane_kind<Elem<decltype(LaneTable<T>::f)>>()},
+  static const LaneEntry tab[] = {HS_LANE_FIELDS(X)};
+#undef X
+  if (entries) *entries = tab;
+  return (int)(sizeof tab / sizeof tab[0]);
+}
+
+template <typename T>
+int lane_source_field(const DevModel<T>& d, const std::string& name, double* out, int n) {
+#define X(f)                                                                    \
+  if (name == #f) {                                                             \
+    const auto* s = reinterpret_cast<const Elem<decltype(d.f)>*>(&d.f);         \
+    const int cnt = elems<decltype(d.f)>();                                     \
+    if (out && n >= cnt)                                                        \
+      for (int i = 0; i < cnt; i++) out[i] = (double)s[i];                      \
+    return cnt;                                                                 \
+  }
+  HS_LANE_FIELDS(X)
+#undef X
+  return -1;
+}
+
+template int lane_layout<float>(const LaneEntry**);
+template int lane_layout<double>(const LaneEntry**);
+template int lane_source_field<float>(const DevModel<float>&, const std::string&, double*, int);
+template int lane_source_field<double>(const DevModel<double>&, const std::string&, double*, int);
+
 template <typename T>
 bool build_dev_model(const HostModel& m, DevModel<T>& d, std::string& err) {
   std::memset(&d, 0, sizeof d);
@@ -1186,6 +1244,11 @@ bool build_dev_model(const HostModel& m, DevModel<T>& d, std::string& err) {
   for (int t = 0; t < m.ntendon; t++) nlim += d.ten_limited[t];
   d.nhinge_limited = nlim;
   for (int k = 0; k < m.nq; k++) d.qpos0[k] = (T)m.qpos0[k];
+  // the lane table: the fields above that the kernel reads per lane, packed (every index fits int8_t:
+  // the capacities checked at the top)
+#define X(f) lane_copy(d.lanes.f, d.f);
+  HS_LANE_FIELDS(X)
+#undef X
   return true;
 }
 

@@ -59,4 +59,15 @@ ContactBound contact_bound(const HostModel& m);
 template <typename T>
 bool build_dev_model(const HostModel& m, DevModel<T>& d, std::string& err);
 
+// The lane table (hs_model.h LaneTable, DevModel::lanes) entry by entry: the DevModel field it packs,
+// its byte offset in the table, its element count and element kind.
+enum LaneKind { LANE_REAL = 0, LANE_U32 = 1, LANE_I8 = 2 };   // T, uint32_t, int8_t
+struct LaneEntry { const char* name; int offset, count, kind; };
+template <typename T>
+int lane_layout(const LaneEntry** entries);   // returns the number of entries
+// DevModel field `name` (one of the layout's names), flattened, as doubles: the number of values
+// (written if they fit n), -1 if the table does not pack that field.
+template <typename T>
+int lane_source_field(const DevModel<T>& d, const std::string& name, double* out, int n);
+
 }  // namespace hs
