@@ -131,6 +131,27 @@ __device__ __forceinline__ void store_contact(MPtr<T> m, Scratch<T, C>& s, int s
   s.con_mu[slot] = m->pair_mu[p];
 }
 
+// Near-pair list entry of the C::NEAR collision: pair | g1 << 8 | g2 << 16 | fn << 24.
+static_assert(MAXPAIR <= 256 && MAXGEOM <= 256 && PAIR_CAPSULE_CAPSULE < 256, "near-pair entry: one byte per field");
+__device__ __forceinline__ uint32_t near_entry(int p, int g1, int g2, int fn) {
+  return (uint32_t)p | (uint32_t)g1 << 8 | (uint32_t)g2 << 16 | (uint32_t)fn << 24;
+}
+// store_contact for a lane that holds its pair's geoms, condim and friction already: the pair's bodies are
+// its geoms' (pair_b1 / pair_b2 are geom_bodyid[g1] / [g2], mjcf.cpp), read from the lane table
+template <typename T, typename C>
+__device__ __forceinline__ void store_contact_near(MPtr<T> m, Scratch<T, C>& s, int slot, const Con<T>& c, int p,
+                                                   int g1, int g2, int dim, T mu) {
+  if (slot >= C::CON) return;
+  for (int k = 0; k < 3; k++) { s.con_pos[slot][k] = c.pos[k]; s.con_n[slot][k] = c.n[k]; s.con_t1[slot][k] = c.t1[k]; }
+  s.con_dist[slot] = c.dist;
+  s.con_pair[slot] = p;
+  const int b1 = lanes<C>(m).geom_bodyid[g1], b2 = lanes<C>(m).geom_bodyid[g2];
+  s.con_bb[slot] = (uint32_t)b1 | (uint32_t)b2 << 8 | (uint32_t)dim << 16;
+  s.con_m1[slot] = b1 ? lanes<C>(m).body_chainmask[b1] : 0u;
+  s.con_m2[slot] = lanes<C>(m).body_chainmask[b2];
+  s.con_mu[slot] = mu;
+}
+
 // impedance (mj_makeImpedance getimpedance), MuJoCo clamps d0/dmax to [1e-4, 0.9999].  The sigmoid
 // y = x^p / mid^(p-1) (x <= mid) or 1 - (1-x)^p / (1-mid)^(p-1) takes its constant denominators from
 // the model (si[5..7], fill_solimp) and one pow, skipped for the default power 2.

@@ -57,7 +57,11 @@ __device__ __forceinline__ void physics_step(Stepper<T, NV, C>& st, KPtr<T> k, T
     HS_STAMP(st.clk, 0);
     st.kinematics();
     HS_STAMP(st.clk, 1);
-    if (st.collision()) warn[WARN_OVERFLOW]++;
+    if constexpr (C::NEAR) {
+      if (st.collision_near()) warn[WARN_OVERFLOW]++;
+    } else {
+      if (st.collision()) warn[WARN_OVERFLOW]++;
+    }
     HS_STAMP(st.clk, 4);
     st.mass_matrix();
     HS_STAMP(st.clk, 2);

@@ -27,11 +27,19 @@ struct Cap {
   static constexpr int RPL = NEFC / HL;   // rows per lane (kept in registers by the row's lane)
   static constexpr bool WIDE = W;         // the wide (re-run) tier
   static constexpr bool LANES = LT;       // the model's per-lane constants are read from LDS (lanes() below)
+  // collision compacts the near pairs before the narrow phase (Stepper::collision_near).  A flag of its own
+  // for the phases to test, but no template parameter of its own: it holds for exactly the instances with
+  // the lane table (the list lies over con_F, where their kinematics tail ends, and store_contact_near
+  // reads the table), and another parameter would rename every fp32 function that carries its Cap.
+  static constexpr bool NEAR = LT;
   static_assert((NCON % HL == 0 || HL % NCON == 0) && NEFC % HL == 0, "capacity in whole half-waves");
 };
 // resident tier per precision (hs_model.h).  The fp64 instances keep the lane table in LDS: at one wave
 // per SIMD nothing hides the latency of its reads through vector memory.  The fp32 engine (its direct
 // kernel fills LDS: 8 workgroups of 20,480 B per CU) and the wide tier read the model as before.
+// The same instances run the collision narrow phase over a compacted list of near pairs (NEAR): their
+// capsule-capsule branch is fp64-heavy and a wave executes it in every pass where any lane holds a near
+// pair; the fp32 engine and the wide tier keep the five-pass loop.
 template <typename T>
 using Resident = std::conditional_t<sizeof(T) == 8, Cap<MAXCON_F64, MAXEFC_F64, false, true>, Cap<MAXCON, MAXEFC>>;
 using Wide = Cap<MAXCON_WIDE, MAXEFC_WIDE, true>;

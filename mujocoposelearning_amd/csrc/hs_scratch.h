@@ -52,6 +52,7 @@ struct Scratch {
   // con_U / con_F, which are first written in rows() (map_vx) and the solve (contact_aggregates), after
   // collision's last read of the tail, and last read in post_constraint, before the next substep's
   // kinematics (store_contact writes none of them).  The union's largest member is then the RNE one.
+  // (In fp64 the tail fills con_v and con_U exactly and ends where con_F begins: near_list() below.)
   struct KinHead { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; };
   struct KinFull { T xpos[MAXBODY][3]; T xmat[MAXBODY][9]; T xquat[MAXBODY][4]; T xanchor[MAXJNT][3];
                    T xaxis[MAXJNT][3]; T gpos[MAXGEOM][3]; T gax[MAXGEOM][3]; };
@@ -66,6 +67,19 @@ struct Scratch {
     if constexpr (C::LANES) return (*reinterpret_cast<const KinTail<T>*>(&con_v[0][0]));
     else return (u.k);
   }
+  // The near-pair list of the C::NEAR instances' collision (one word per pair, hs_contacts.h near_entry) lies over
+  // con_F, where those instances' KinTail ends.  con_F is dead for the whole of collision: its last writer
+  // before it is contact_aggregates at the end of the previous substep's solve, its readers are jtf_lane
+  // (inside the solve, after that write) and post_constraint (full_state, right after the solve), and its
+  // first writer after collision is contact_aggregates in this substep's solve -- a write, so nothing ever
+  // reads list words as forces.  dump_debug reads no con_F, commit(full) reads the union's cfrc / linv
+  // (post_constraint's outputs, taken from con_F before the next substep's kinematics); the acceleration
+  // check's second attempt restarts at kinematics and rebuilds the list.  store_contact writes none of
+  // con_v / con_U / con_F, so the list and the tail both outlive the narrow passes.
+  static_assert(!C::NEAR || (C::LANES && sizeof(uint32_t) * MAXPAIR <= sizeof(T) * C::CON * 3 &&
+                             sizeof(KinTail<T>) <= sizeof(T) * C::CON * 9),
+                "the near-pair list fits con_F, past the KinTail over con_v / con_U");
+  __device__ __forceinline__ uint32_t* near_list() { return reinterpret_cast<uint32_t*>(&con_F[0][0]); }
   union {   // phase-local arrays (aliased)
     Kin k;                                                        // kinematics + collision
     struct { T crb[MAXBODY][10]; T buf[MAXDOF][6]; } c;          // composite rigid body

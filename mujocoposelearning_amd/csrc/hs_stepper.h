@@ -263,6 +263,87 @@ struct Stepper {
     return overflow;
   }
 
+  // mj_collision of the C::NEAR instances (physics_step picks it), the same contacts in the same slots as
+  // collision().
+  // A wave runs collide_pair's capsule-capsule branch (IEEE divides, a square root, make_frame) in every
+  // pass where any of its 64 lanes holds a near pair, and a humanoid's ~26 near pairs lie scattered over
+  // the five passes.  So a broad pass first compacts each env's near pairs, ascending, into a list in LDS
+  // (Scratch::near_list), and the narrow phase runs ceil(max(near pairs of either half) / 32) passes over
+  // the list: usually one.  Ascending pair order in the list keeps the contact slots in MuJoCo's order.
+  __device__ __forceinline__ int collision_near() {
+    phase_begin();
+    const int npair = m->npair;
+    uint32_t* const list = s.near_list();
+    int nlo = 0, nhi = 0;       // near pairs of the wave's two envs so far (wave-uniform)
+    int4 info_n = make_int4(0, 0, 0, 0);
+    T sz_n[4] = {0, 0, 0, 0};
+    if (sl < npair) {
+      info_n = make_int4(m->pair_info[sl][0], m->pair_info[sl][1], m->pair_info[sl][2], m->pair_info[sl][3]);
+      for (int k = 0; k < 4; k++) sz_n[k] = m->pair_size[sl][k];
+    }
+    for (int base = 0; base < npair; base += HL) {
+      const int p = base + sl;
+      const int4 info = info_n;
+      const T sz[4] = {sz_n[0], sz_n[1], sz_n[2], sz_n[3]};
+      if (p + HL < npair) {
+        info_n = make_int4(m->pair_info[p + HL][0], m->pair_info[p + HL][1], m->pair_info[p + HL][2],
+                           m->pair_info[p + HL][3]);
+        for (int k = 0; k < 4; k++) sz_n[k] = m->pair_size[p + HL][k];
+      }
+      const int g1 = info.x, g2 = info.y, fn = info.z;
+      bool near = false;
+      if (p < npair) {
+        const T* p1 = HS_KTAIL(s).gpos[g1];
+        const T* p2 = HS_KTAIL(s).gpos[g2];
+        const T* a1 = HS_KTAIL(s).gax[g1];
+        const T d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+        // body pairs: collide_pair's own bounding-sphere test (it runs again there, on the same values).
+        // plane pairs: the geom's centre above the plane by more than radius + half-length.  Exact: a
+        // capsule's end spheres lie within h2 of its centre along a unit axis, so an end at cd_end <= r2
+        // has the centre at cd <= r2 + h2.  The slack (1e-9 relative, 1e-12 absolute, far above the
+        // rounding of these few operations) errs towards near only: a pair wrongly near costs a lane of
+        // the narrow pass and yields no contact, a pair wrongly far would lose one.
+        const T R = sz[0] + sz[1] + sz[2] + sz[3];
+        const bool far_body = dot3(d, d) > R * R;
+        const T reach = sz[2] + (fn == PAIR_PLANE_CAPSULE ? sz[3] : T(0));
+        const bool far_plane = dot3(d, a1) > reach * T(1 + 1e-9) + T(1e-12);
+        near = !(fn >= PAIR_SPHERE_SPHERE ? far_body : far_plane);
+      }
+      const uint64_t bm = __ballot(near);
+      const uint32_t mk = up ? (uint32_t)(bm >> 32) : (uint32_t)bm;
+      if (near) list[(up ? nhi : nlo) + below(mk, sl)] = near_entry(p, g1, g2, fn);
+      nlo += __popc((uint32_t)bm);
+      nhi += __popc((uint32_t)(bm >> 32));
+    }
+    const int nnear = up ? nhi : nlo;
+    const int nmax = nlo > nhi ? nlo : nhi;
+    WSYNC();
+    int ncon = 0;
+    for (int j0 = 0; j0 < nmax; j0 += HL) {
+      const int j = j0 + sl;
+      const bool on = j < nnear;
+      const uint32_t e = on ? list[j] : 0u;     // (idle lanes load pair 0's records and run nothing)
+      const int p = e & 0xff, g1 = (e >> 8) & 0xff, g2 = (e >> 16) & 0xff, fn = e >> 24;
+      // everything the pass reads from the model at the pair's index, issued together
+      const T sz[4] = {m->pair_size[p][0], m->pair_size[p][1], m->pair_size[p][2], m->pair_size[p][3]};
+      const T mu = m->pair_mu[p];
+      const int dim = m->pair_info[p][3];
+      Con<T> c0, c1;
+      int n = 0;
+      if (on) n = collide_pair(s, make_int4(g1, g2, fn, dim), sz, c0, c1);
+      uint32_t m1 = hballot(n >= 1, up), m2 = hballot(n >= 2, up);
+      int pre = below(m1, sl) + below(m2, sl);
+      if (n >= 1) store_contact_near(m, s, ncon + pre, c0, p, g1, g2, dim, mu);
+      if (n >= 2) store_contact_near(m, s, ncon + pre + 1, c1, p, g1, g2, dim, mu);
+      ncon += __popc(m1) + __popc(m2);
+    }
+    int overflow = ncon > C::CON;
+    if (overflow) ncon = C::CON;
+    if (sl == 0) s.ncon = ncon;
+    WSYNC();
+    return overflow;
+  }
+
   // mj_crb -> Mr rows (registers)
   __device__ __forceinline__ void mass_matrix() {
     phase_begin();
