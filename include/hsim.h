@@ -34,6 +34,10 @@
  *   hs_debug_queue_counters (test view of the chunk queue's claim / exit counters; no counterpart)
  *   hs_last_tape_ms, hs_tape_aborts, hs_stream_orders, hs_batch_counters   (diagnostics)
  *   hs_state_io          <- reads/writes of data.qpos/qvel/qacc_warmstart/time/ctrl (custom_env.py:105-117)
+ *   hs_kinematics        <- the pose fields mujoco.Renderer.update_scene reads from one mjData
+ *   hs_kinematics_batch  <- the same for n poses (env states or recorded qpos rows) in one launch, on the device
+ *   hs_render_frames     <- mujoco.Renderer.update_scene + render (custom_env.py:273-289) for n frames in one
+ *                           launch: the video path of custom_env.py:291-321, train_sb3.py:13-61, render_policy.py
  *   hs_get_buffers       <- data.* arrays as device buffers (obs, reward, terminated, ...)
  *   hs_last_error        <- mujoco's error callback / MjModel load error string
  *   hs_gae               <- SB3 RolloutBuffer.compute_returns_and_advantage (stable_baselines3 2.3.2
@@ -426,6 +430,39 @@ int hs_state_io(hs_batch* b, int dir, double* qpos, double* qvel, double* qacc_w
  * Synchronous; not on the step path. */
 int hs_kinematics(hs_batch* b, int env, const double* qpos, double* xpos, double* xmat, double* geom_xpos,
                   double* geom_zaxis, double* com);
+/* One kinematics record: [xpos MAXBODY*3][xmat MAXBODY*9][geom_xpos MAXGEOM*3][geom z-axis MAXGEOM*3][com 3]
+ * values of the batch's precision, with the engine's capacities MAXBODY = 20, MAXGEOM = 24 (rows past the
+ * model's nbody / ngeom are not written). */
+#define HS_KINDIM 387
+/* hs_kinematics for n poses in one launch, device to device: record i (HS_KINDIM values of the batch's
+ * precision) goes to kin_dev[i].  The poses are either rows of qpos_dev [n][nq] (device, the batch's
+ * precision) or, with envs (n env ids in HOST memory, read before the call returns), the current states of
+ * those envs; exactly one of the two is non-NULL.  The env ids are checked against [0, N) before anything is
+ * launched.  Asynchronous on `stream`, ordered like every launch of the batch; the env states are only
+ * read.  The device copy of the id list is the batch's own (grown on demand, no per-call allocation). */
+int hs_kinematics_batch(hs_batch* b, int n, const int32_t* envs, const void* qpos_dev, void* kin_dev, void* stream);
+
+/* The camera of hs_render_frames.  HS_CAM_BODY: position xpos[body] + xmat[body] pos, rotation
+ * xmat[body] rot (an MJCF camera of mode "fixed").  HS_CAM_COM: position com + pos, rotation rot (mode
+ * "trackcom" with its offset and rotation at qpos0, and the free camera, pos = -distance x forward).
+ * rot is row-major with the camera's x, y, z axes as columns (it looks along -z); fovy in degrees. */
+enum { HS_CAM_BODY = 0, HS_CAM_COM = 1 };
+typedef struct {
+  int mode;        /* HS_CAM_* */
+  int body;        /* HS_CAM_BODY: the body the camera is attached to, in [0, nbody) */
+  double pos[3];
+  double rot[9];
+  double fovy;     /* in (0, 180) */
+} hs_camera;
+/* Ray-cast n frames <- mujoco.Renderer.update_scene(data, camera) + render() (custom_env.py:284-288): frame i
+ * draws kinematics record kin_dev[i] (hs_kinematics_batch) from `cam` into rgb_dev[i] of
+ * uint8 rgb_dev[n][H][W][3] (device).  The scene is the model's plane, spheres and capsules in the "body"
+ * material, the 0.5 m checker floor, the gradient sky, a headlight and the "top" light above the COM;
+ * fp64 per pixel, the arithmetic of the package's host renderer.  H and W in [1, 4096].  Asynchronous on
+ * `stream`, ordered like every launch of the batch.  A bad argument (NULL pointer, n < 1, H / W / fovy out
+ * of range, unknown mode, body outside [0, nbody)) returns -1 with a message and launches nothing. */
+int hs_render_frames(hs_batch* b, int n, const void* kin_dev, const hs_camera* cam, int H, int W, uint8_t* rgb_dev,
+                     void* stream);
 /* Stage dump of env 0 after its last substep (parity debugging); n >= 16384 doubles. */
 int hs_set_debug(hs_batch* b, int enable);
 int hs_get_debug(hs_batch* b, double* out, int n);

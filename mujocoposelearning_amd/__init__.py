@@ -31,12 +31,16 @@ def __getattr__(name):
     if name == "train_humanoid":
         from .train import train_humanoid
         return train_humanoid
-    if name in ("evaluate_policy", "evaluate_policy_device", "EvalCallback", "EvalResult", "render_policy"):
+    if name in ("evaluate_policy", "evaluate_policy_device", "EvalCallback", "EvalResult", "render_policy",
+                "record_episode", "VideoRecorderCallback", "CallbackList"):
         from . import evaluation
         return getattr(evaluation, name)
     if name in ("VecNormalize", "RunningMeanStd"):
         from . import vec_normalize
         return getattr(vec_normalize, name)
+    if name in ("Renderer", "DeviceRenderer", "tile_images"):
+        from . import render
+        return getattr(render, name)
     if name == "HsBatch":
         from .batch import HsBatch
         return HsBatch

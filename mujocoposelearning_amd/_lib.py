@@ -27,6 +27,9 @@ HS_PPO_CTL_STOP, HS_PPO_CTL_EPOCH = 0, 1
  HS_PPO_STAT_LOSS_LAST, HS_PPO_STAT_COUNT, HS_PPO_STAT_KL_LAST, HS_PPO_STAT_EXPLAINED_VARIANCE, HS_PPO_STAT_STD,
  HS_PPO_STAT_KL) = range(11)
 DBGDIM = 32768
+HS_KINDIM = 387                  # one kinematics record (hs_kinematics_batch): 20 * 12 + 24 * 6 + 3 values
+KIN_MAXBODY, KIN_MAXGEOM = 20, 24
+HS_CAM_BODY, HS_CAM_COM = 0, 1   # hs_camera.mode
 
 
 class hs_env_config(C.Structure):
@@ -69,6 +72,11 @@ class hs_eval_bufs(C.Structure):
 
 class hs_obs_norm_args(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float), ("obs_dim", C.c_int)]
+
+
+class hs_camera(C.Structure):
+    _fields_ = [("mode", C.c_int), ("body", C.c_int), ("pos", C.c_double * 3), ("rot", C.c_double * 9),
+                ("fovy", C.c_double)]
 
 
 class hs_batch_info(C.Structure):
@@ -131,6 +139,8 @@ def lib():
         "hs_physics_step": (i, [vp, vp, i, vp]),
         "hs_state_io": (i, [vp, i, vp, vp, vp, vp, vp]),
         "hs_kinematics": (i, [vp, i, vp, vp, vp, vp, vp, vp]),
+        "hs_kinematics_batch": (i, [vp, i, vp, vp, vp, vp]),
+        "hs_render_frames": (i, [vp, i, vp, vp, i, i, vp, vp]),
         "hs_set_debug": (i, [vp, i]),
         "hs_debug_lose_handoff": (i, [vp, i]),
         "hs_debug_queue_order": (i, [vp, vp, i]),
@@ -198,7 +208,7 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_dgrad_act", "hs_colsum_pair",
             "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version",
             "hs_rollout_norm", "hs_evaluate_norm", "hs_obs_norm_workspace", "hs_obs_norm", "hs_rms_merge",
-            "hs_return_moments", "hs_reward_scale")
+            "hs_return_moments", "hs_reward_scale", "hs_kinematics_batch", "hs_render_frames")
 
 
 class HsimError(RuntimeError):

@@ -478,6 +478,58 @@ class HsBatch:
                                   *[out[k].ctypes.data for k in ("xpos", "xmat", "geom_xpos", "geom_zaxis", "com")]))
         return out
 
+    def kinematics_batch(self, envs=None, qpos=None):
+        """``kinematics`` for n poses in one launch, device to device (hs_kinematics_batch): a
+        ``[n, HS_KINDIM]`` tensor of the batch's dtype, record i = [xpos 20*3][xmat 20*9][geom_xpos 24*3]
+        [geom z-axis 24*3][com 3] of pose i (rows past nbody / ngeom are zero).  The poses are the current
+        states of the envs ``envs`` (a sequence of ids) or the rows of ``qpos`` [n, nq]; exactly one of
+        the two.  The env states are only read.  What ``render.DeviceRenderer`` draws."""
+        torch = _torch()
+        if (envs is None) == (qpos is None):
+            raise ValueError("kinematics_batch: exactly one of envs / qpos")
+        if envs is not None:
+            ids = np.ascontiguousarray(np.asarray(envs, dtype=np.int64).reshape(-1))
+            if ids.size and (ids.min() < 0 or ids.max() >= self.n):
+                bad = ids[(ids < 0) | (ids >= self.n)][0]
+                raise IndexError(f"env {int(bad)} out of range [0, {self.n})")
+            n = ids.size
+        else:
+            q = torch.as_tensor(qpos, device=self.device).to(self.dtype)
+            if q.dim() == 1:
+                q = q[None]
+            if q.dim() != 2 or q.shape[1] != self.model.nq:
+                raise ValueError(f"qpos must have shape (n, {self.model.nq})")
+            q = q.contiguous()
+            n = q.shape[0]
+        if n < 1:
+            raise ValueError("kinematics_batch: no poses")
+        out = torch.zeros(n, _lib.HS_KINDIM, dtype=self.dtype, device=self.device)
+        row = out.stride(0) * out.element_size()
+        if envs is None:
+            check(lib().hs_kinematics_batch(self._h, n, None, q.data_ptr(), out.data_ptr(), self.stream))
+            return out
+        if len(self._groups) == 1:
+            loc = ids.astype(np.int32)
+            check(lib().hs_kinematics_batch(self._h, n, loc.ctypes.data, None, out.data_ptr(), self.stream))
+            return out
+        # stream groups: each group poses its own envs (group-local ids) into a scratch block on its
+        # stream; the rows go to their places once the groups have joined
+        order = np.argsort(ids, kind="stable")
+        tmp = torch.zeros_like(out)
+        spans = {}
+        for g, (h, lo, hi) in enumerate(self._groups):
+            a, b_ = np.searchsorted(ids[order], [lo, hi])
+            if b_ > a:
+                spans[h] = (int(a), int(b_), np.ascontiguousarray(ids[order][a:b_] - lo, dtype=np.int32))
+
+        def go(h, lo, hi, st):
+            if h in spans:
+                a, b_, loc = spans[h]
+                check(lib().hs_kinematics_batch(h, b_ - a, loc.ctypes.data, None, tmp.data_ptr() + a * row, st))
+        self._launch(go, tmp)
+        out[torch.as_tensor(order, device=self.device)] = tmp
+        return out
+
     def set_debug(self, on=True):
         check(lib().hs_set_debug(self._h, int(bool(on))))
 

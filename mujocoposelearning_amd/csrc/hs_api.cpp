@@ -14,7 +14,11 @@
 #include "hs_act.h"
 #include "hs_api_error.h"
 #include "hs_kernels.h"
+#include "hs_render.h"
 #include "mjcf.h"
+
+static_assert(HS_KINDIM == hs::KINDIM, "include/hsim.h HS_KINDIM is the kernels' record size");
+static_assert(HS_CAM_BODY == hs::CAM_BODY && HS_CAM_COM == hs::CAM_COM, "include/hsim.h camera modes");
 
 struct hs_model {
   hs::HostModel host;
@@ -49,6 +53,8 @@ struct hs_batch {
   unsigned long long stream_orders = 0;      // cross-stream waits inserted (diagnostics)
   hipEvent_t tape_ev[2] = {nullptr, nullptr};   // around the last tape / rollout kernel launch
   float last_tape_ms = -1.f;                 // its duration (hs_last_tape_ms)
+  int* kin_envs = nullptr;                   // hs_kinematics_batch: the env-id list on the device (grown on demand)
+  int kin_envs_cap = 0;
 };
 
 thread_local std::string hs::g_err;
@@ -557,6 +563,7 @@ void hs_batch_destroy(hs_batch* b) {
   if (b->qsync) uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
   if (b->eval_obs) uc_release(b->device, (size_t)b->n * b->obs_dim * sizeof(float), b->eval_obs);
   if (b->tape_backup) (void)hipFree(b->tape_backup);
+  if (b->kin_envs) (void)hipFree(b->kin_envs);
   if (b->order_ev) (void)hipEventDestroy(b->order_ev);
   for (auto& e : b->tape_ev)
     if (e) (void)hipEventDestroy(e);
@@ -982,6 +989,77 @@ int hs_kinematics(hs_batch* b, int env, const double* qpos, double* xpos, double
   if (!hip_ok(hipDeviceSynchronize(), "sync")) return -1;
   return b->precision == HS_FP64 ? kinematics_io<double>(b, env, qpos, xpos, xmat, geom_xpos, geom_zaxis, com)
                                  : kinematics_io<float>(b, env, qpos, xpos, xmat, geom_xpos, geom_zaxis, com);
+}
+
+int hs_kinematics_batch(hs_batch* b, int n, const int32_t* envs, const void* qpos_dev, void* kin_dev, void* stream) {
+  if (!b) return fail("hs_kinematics_batch: null batch");
+  if (!kin_dev) return fail("hs_kinematics_batch: null kin_dev");
+  if (n < 1) return fail("hs_kinematics_batch: n must be >= 1");
+  if ((envs != nullptr) == (qpos_dev != nullptr))
+    return fail("hs_kinematics_batch: exactly one of envs / qpos_dev must be given");
+  if (envs)
+    for (int i = 0; i < n; i++)
+      if (envs[i] < 0 || envs[i] >= b->n)
+        return fail("hs_kinematics_batch: env id " + std::to_string(envs[i]) + " out of range [0, " +
+                    std::to_string(b->n) + ")");
+  DeviceGuard g(b->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (envs && n > b->kin_envs_cap) {
+    // (hipFree waits for the device: no earlier launch still reads the old list)
+    if (b->kin_envs) (void)hipFree(b->kin_envs);
+    b->kin_envs = nullptr;
+    b->kin_envs_cap = 0;
+    const int cap = std::max(64, n);
+    if (!hip_ok(hipMalloc(&b->kin_envs, (size_t)cap * sizeof(int)), "hipMalloc(kinematics env ids)")) return -1;
+    b->kin_envs_cap = cap;
+  }
+  if (order_streams(b, st)) return -1;
+  // pageable host memory: the copy has left `envs` when the call returns, and on the stream it is
+  // ordered after the previous launch that read the list
+  if (envs && !hip_ok(hipMemcpyAsync(b->kin_envs, envs, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st),
+                      "kinematics env ids"))
+    return -1;
+  const int nv = b->model->host.nv;
+  const int* de = envs ? b->kin_envs : nullptr;
+  hipError_t e = b->precision == HS_FP64
+      ? hs::launch_kinematics_batch<double>((const hs::DevModel<double>*)b->dmodel, nv, n, (const double*)qpos_dev,
+                                            (const double*)b->buf.qpos, de, (double*)kin_dev, st)
+      : hs::launch_kinematics_batch<float>((const hs::DevModel<float>*)b->dmodel, nv, n, (const float*)qpos_dev,
+                                           (const float*)b->buf.qpos, de, (float*)kin_dev, st);
+  if (e == hipErrorInvalidValue) return fail("no kernel instance for this model's nv (compiled: nv = 27)");
+  return hip_rc(e, "kinematics batch launch");
+}
+
+int hs_render_frames(hs_batch* b, int n, const void* kin_dev, const hs_camera* cam, int H, int W, uint8_t* rgb_dev,
+                     void* stream) {
+  if (!b) return fail("hs_render_frames: null batch");
+  if (!kin_dev || !cam || !rgb_dev) return fail("hs_render_frames: null argument");
+  if (n < 1) return fail("hs_render_frames: n must be >= 1");
+  if (H < 1 || H > 4096 || W < 1 || W > 4096) return fail("hs_render_frames: H and W must lie in [1, 4096]");
+  if (!(cam->fovy > 0.0 && cam->fovy < 180.0)) return fail("hs_render_frames: fovy must lie in (0, 180) degrees");
+  if (cam->mode != HS_CAM_BODY && cam->mode != HS_CAM_COM) return fail("hs_render_frames: unknown camera mode");
+  const auto& h = b->model->host;
+  if (cam->mode == HS_CAM_BODY && (cam->body < 0 || cam->body >= h.nbody))
+    return fail("hs_render_frames: camera body out of range [0, nbody)");
+  hs::RenderScene sc{};
+  sc.ngeom = h.ngeom;
+  for (int g = 0; g < h.ngeom; g++) {
+    sc.geom_type[g] = h.geom_type[g];
+    sc.geom_r[g] = h.geom_size[3 * g];
+    sc.geom_hl[g] = h.geom_size[3 * g + 1];
+  }
+  hs::RenderCam rc{};
+  rc.mode = cam->mode;
+  rc.body = cam->mode == HS_CAM_BODY ? cam->body : 0;
+  for (int k = 0; k < 3; k++) rc.pos[k] = cam->pos[k];
+  for (int k = 0; k < 9; k++) rc.rot[k] = cam->rot[k];
+  rc.f = 0.5 * H / std::tan(cam->fovy * (M_PI / 180.0) / 2);   // render.py: 0.5 H / tan(radians(fovy) / 2)
+  DeviceGuard g(b->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (order_streams(b, st)) return -1;
+  hipError_t e = b->precision == HS_FP64 ? hs::launch_render<double>((const double*)kin_dev, n, sc, rc, H, W, rgb_dev, st)
+                                         : hs::launch_render<float>((const float*)kin_dev, n, sc, rc, H, W, rgb_dev, st);
+  return hip_rc(e, "render launch");
 }
 
 int hs_set_debug(hs_batch* b, int enable) {

@@ -219,6 +219,11 @@ int resident_waves(bool pgs);
 constexpr int KINDIM = MAXBODY * 12 + MAXGEOM * 6 + 3;
 template <typename T>
 hipError_t launch_kinematics(const DevModel<T>* dmodel, int nv, const T* qpos, T* out, hipStream_t stream);
+// the same for n states in one launch -> out[n][KINDIM]: rows of qpos[n][nq], or (envs != null, a device
+// list of n env ids) rows envs[i] of the batch's state rows state_qpos (kin_batch_kernel)
+template <typename T>
+hipError_t launch_kinematics_batch(const DevModel<T>* dmodel, int nv, int n, const T* qpos, const T* state_qpos,
+                                   const int* envs, T* out, hipStream_t stream);
 
 // the step kernel's reward code (reward_formula) on caller-supplied per-env fields (hs_reward_eval)
 template <typename T>

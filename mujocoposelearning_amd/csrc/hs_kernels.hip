@@ -278,6 +278,40 @@ __global__ __launch_bounds__(64) void kin_kernel(MPtr<T> m, const T* __restrict_
   if (sl < 3) out[sl] = s.com[sl];
 }
 
+// The same for n poses in one launch (the device renderer's poses, hs_kinematics_batch): one wave per
+// pose, the upper half-wave duplicating the lower as in kin_kernel, so a record is kin_kernel's bit
+// for bit and n odd or 1 needs no special case.  Pose i is row i of qpos[n][nq], or, with `envs`,
+// row envs[i] of the batch's own state rows (state_qpos); record i goes to out[i][KINDIM].
+template <typename T, int NV>
+__global__ __launch_bounds__(64) void kin_batch_kernel(MPtr<T> m, const T* __restrict__ qpos,
+                                                       const T* __restrict__ state_qpos,
+                                                       const int* __restrict__ envs, T* __restrict__ out) {
+  __shared__ Scratch<T, Resident<T>> smem[2];
+  const int lane = threadIdx.x;
+  const bool up = lane >= HL;
+  const int sl = lane & (HL - 1);
+  Scratch<T, Resident<T>>& s = smem[up ? 1 : 0];
+  const size_t pose = blockIdx.x;
+  const T* q = envs ? state_qpos + (size_t)envs[pose] * m->nq : qpos + pose * m->nq;
+  for (int k = sl; k < m->nq; k += HL) s.qpos[k] = q[k];
+  if constexpr (Resident<T>::LANES) load_lane_table<T>(m);
+  WSYNC();
+  Stepper<T, NV, Resident<T>> st(m, s, lane);
+  st.kinematics();
+  if (up) return;
+  out += pose * KINDIM;
+  const int nb = m->nbody, ng = m->ngeom;
+  for (int k = sl; k < nb * 3; k += HL) out[k] = s.u.k.xpos[k / 3][k % 3];
+  out += MAXBODY * 3;
+  for (int k = sl; k < nb * 9; k += HL) out[k] = s.u.k.xmat[k / 9][k % 9];
+  out += MAXBODY * 9;
+  for (int k = sl; k < ng * 3; k += HL) out[k] = HS_KTAIL(s).gpos[k / 3][k % 3];
+  out += MAXGEOM * 3;
+  for (int k = sl; k < ng * 3; k += HL) out[k] = HS_KTAIL(s).gax[k / 3][k % 3];
+  out += MAXGEOM * 3;
+  if (sl < 3) out[sl] = s.com[sl];
+}
+
 // hs_reward_eval: the step kernel's reward code (np_sum_half + reward_formula) on caller-supplied
 // fields, one env per 32-lane half as in the step kernel.  Not on the step path: it exists so the
 // device formulas can be checked against the reference's own outputs on arbitrary states.
@@ -525,6 +559,15 @@ hipError_t launch_kinematics(const DevModel<T>* dmodel, int nv, const T* qpos, T
   hipLaunchKernelGGL((kin_kernel<T, 27>), dim3(1), dim3(WAVE), 0, stream, (MPtr<T>)dmodel, qpos, out);
   return hipGetLastError();
 }
+
+template <typename T>
+hipError_t launch_kinematics_batch(const DevModel<T>* dmodel, int nv, int n, const T* qpos, const T* state_qpos,
+                                   const int* envs, T* out, hipStream_t stream) {
+  if (nv != 27 || n < 1 || (envs ? !state_qpos : !qpos)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((kin_batch_kernel<T, 27>), dim3((unsigned)n), dim3(WAVE), 0, stream, (MPtr<T>)dmodel, qpos,
+                     state_qpos, envs, out);
+  return hipGetLastError();
+}
 // The Makefile compiles this file once per precision (HS_ONLY_F32 / HS_ONLY_F64), so each engine
 // gets its own code-generation flags (the fp64 one without MachineLICM), and once more
 // (HS_ONLY_NORM, the fp64 flags) for the two fused instances whose policy normalises its obs
@@ -550,6 +593,8 @@ template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuf
                                        const NormArgs*);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
+template hipError_t launch_kinematics_batch<float>(const DevModel<float>*, int, int, const float*, const float*,
+                                                   const int*, float*, hipStream_t);
 template hipError_t launch_reward_eval<float>(const RewardEvalArgs<float>&, hipStream_t);
 template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 #endif
@@ -560,6 +605,8 @@ template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvB
                                         const NormArgs*);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
+template hipError_t launch_kinematics_batch<double>(const DevModel<double>*, int, int, const double*, const double*,
+                                                    const int*, double*, hipStream_t);
 template hipError_t launch_reward_eval<double>(const RewardEvalArgs<double>&, hipStream_t);
 template hipError_t launch_pack<double>(const PackArgs<double>&, hipStream_t);
 #endif

@@ -4,8 +4,10 @@ Replaces, for envs stepped by this engine:
 
 * ``render_policy.py:6-51`` -- play a checkpoint with ``model.predict(obs, deterministic=True)`` ("make
   deterministic (critical)") and write the video: ``render_policy``;
-* ``train_sb3.py:52-60`` ``VideoRecorderCallback`` / SB3's ``EvalCallback`` -- whole episodes of the
-  current policy every so often during training: ``EvalCallback``;
+* ``train_sb3.py:13-61`` ``VideoRecorderCallback`` -- a video of the current policy every ``render_interval``
+  finished episodes: ``VideoRecorderCallback`` (``CallbackList`` runs it beside others, train_sb3.py:217);
+* SB3's ``EvalCallback`` -- whole episodes of the current policy every so often during training:
+  ``EvalCallback``;
 * SB3's ``evaluate_policy`` (common/evaluation.py, 2.3.2): ``evaluate_policy``.
 
 ``evaluate_policy_device`` is the engine under all three: every env plays ``n_episodes_per_env`` whole
@@ -33,7 +35,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-__all__ = ["EvalResult", "evaluate_policy_device", "evaluate_policy", "EvalCallback", "render_policy"]
+__all__ = ["EvalResult", "evaluate_policy_device", "evaluate_policy", "EvalCallback", "render_policy", "record_episode",
+           "VideoRecorderCallback", "CallbackList"]
 
 
 @dataclass
@@ -334,19 +337,59 @@ class EvalCallback:
         return True
 
 
+def record_episode(model, env, out_path, *, deterministic=True, camera="side", height=480, width=640, framerate=60,
+                   num_steps=1000, renderer="device", seed=0):
+    """One episode of env 0 of ``env`` under ``model``'s policy (at most ``num_steps`` steps of it) as a
+    video at ``out_path``: one traced ``evaluate_policy_device`` run; a frame is taken after a step while
+    ``len(frames) < time x framerate`` (custom_env.py:273-289), its pose from the traced qpos.
+    ``renderer="device"``: the selected qpos rows go from the trace to ``render.DeviceRenderer.render_qpos``
+    on the device -- one kinematics launch, one ray-cast launch, one copy of the uint8 frames
+    [F, H, W, 3]; ``renderer="host"``: ``render.Renderer`` frame by frame.  Returns the written path (None:
+    no frame)."""
+    from . import render
+    from .vec_normalize import unwrap
+    if renderer not in ("device", "host"):
+        raise ValueError(f"renderer must be 'device' or 'host', got {renderer!r}")
+    env, _ = unwrap(env)
+    res = evaluate_policy_device(model, env, 1, deterministic=deterministic, n_trace=1, seed=seed)
+    qpos = res.trace["qpos"][:, 0]
+    dones = res.trace["dones"][:, 0].cpu().numpy()
+    dt = float(env.model.opt.timestep)
+    picked = []
+    for t in range(min(int(num_steps), len(dones))):
+        time = dt * (1 + env.frame_skip * (t + 1))        # data.time after step t (the reset took one mj_step)
+        if len(picked) < time * framerate:
+            picked.append(t)
+        if dones[t]:
+            break
+    if not picked:
+        return None
+    if renderer == "device":
+        r = render.DeviceRenderer(env.model, env.batch, height=height, width=width)
+        rows = qpos[torch.as_tensor(picked, device=qpos.device)]
+        frames = r.render_qpos(rows, camera=camera).cpu().numpy()
+    else:
+        r = render.Renderer(env.model, height=height, width=width)
+        q = qpos.double().cpu().numpy()
+        frames = []
+        for t in picked:
+            r.update_scene_pose(env.batch.kinematics(0, qpos=q[t]), env.batch, camera=camera)
+            frames.append(r.render())
+        r.close()
+    return str(render.write_video(str(out_path), frames, fps=framerate))
+
+
 def render_policy(model_path, out_path, num_steps=1000, camera="side", height=480, width=640, framerate=60, device=0,
-                  env_config=None):
+                  env_config=None, renderer="device"):
     """render_policy.py:6-51: load an SB3-layout checkpoint (ours or SB3's own zip), play one
-    deterministic episode of one env (at most ``num_steps`` steps of it) and write the video.  The episode
-    is one traced ``evaluate_policy_device`` run; a frame is taken after a step while
-    ``len(frames) < time x framerate`` (custom_env.py:273-289), its pose from the traced qpos
-    (``HsBatch.kinematics``), drawn by ``render.Renderer``.  ``env_config`` overrides the env's keys
-    (train.py's defaults: duration 10.0, frame_skip 3, reward 'walk').  Returns the written path."""
+    deterministic episode of one env (at most ``num_steps`` steps of it) and write the video
+    (``record_episode``: the frames drawn on the GPU, or with ``renderer="host"`` by ``render.Renderer``).
+    ``env_config`` overrides the env's keys (train.py's defaults: duration 10.0, frame_skip 3, reward
+    'walk').  Returns the written path."""
     import json
     import zipfile
 
     from .ppo import PPO
-    from .render import Renderer, write_video
     from .sb3_format import load_sb3_zip, read_member
     from .vec_env import HumanoidVecEnv
     from .vec_normalize import VecNormalize
@@ -369,22 +412,79 @@ def render_policy(model_path, out_path, num_steps=1000, camera="side", height=48
         if stats is not None:
             penv.from_bytes(stats)
             penv.training = False
-        res = evaluate_policy_device(model, env, 1, deterministic=True, n_trace=1)
-        qpos = res.trace["qpos"][:, 0].double().cpu().numpy()
-        dones = res.trace["dones"][:, 0].cpu().numpy()
-        dt = float(env.model.opt.timestep)
-        renderer = Renderer(env.model, height=height, width=width)
-        frames = []
-        for t in range(min(int(num_steps), len(qpos))):
-            time = dt * (1 + env.frame_skip * (t + 1))        # data.time after step t (the reset took one mj_step)
-            if len(frames) < time * framerate:
-                renderer.update_scene_pose(env.batch.kinematics(0, qpos=qpos[t]), env.batch, camera=camera)
-                frames.append(renderer.render())
-            if dones[t]:
-                break
-        renderer.close()
-        if not frames:
-            return None
-        return str(write_video(str(out_path), frames, fps=framerate))
+        return record_episode(model, env, out_path, deterministic=True, camera=camera, height=height, width=width,
+                              framerate=framerate, num_steps=num_steps, renderer=renderer)
     finally:
         env.close()
+
+
+class VideoRecorderCallback:
+    """train_sb3.py:13-61's ``VideoRecorderCallback`` for ``PPO.learn(callback=...)``: after an iteration, when
+    the number of finished episodes (``len(model.ep_returns)``) has crossed one or more multiples of
+    ``render_interval`` since the last call, record ONE episode of the current policy on the callback's own
+    1-env evaluation env (``env_config_from_kwargs(env_kwargs)``, frames at ``env_kwargs["framerate"]``) and
+    write ``<out_dir>/<run_name>/episode_<largest multiple crossed>.gif``.  Stochastic by default, as the
+    reference's callback (it dropped ``deterministic=True``); a model trained over VecNormalize is played on
+    its frozen obs moments (``evaluate_policy_device``).  Rank 0 only; always returns True; the written
+    paths are kept in ``videos``."""
+
+    def __init__(self, render_interval, env_kwargs, run_name=None, out_dir="recordings", deterministic=False,
+                 height=480, width=640, camera="side", device=0):
+        if int(render_interval) < 1:
+            raise ValueError("render_interval must be >= 1")
+        self.render_interval = int(render_interval)
+        self.env_kwargs = dict(env_kwargs or {})
+        self.run_name = str(run_name) if run_name is not None else "run"
+        self.out_dir, self.deterministic = str(out_dir), bool(deterministic)
+        self.height, self.width, self.camera, self.device = int(height), int(width), camera, device
+        self.videos = []
+        self._seen = 0          # finished episodes at the last call
+        self._env = None
+
+    def _eval_env(self):
+        if self._env is None:
+            from .train import env_config_from_kwargs
+            from .vec_env import HumanoidVecEnv
+            self._env = HumanoidVecEnv(env_config_from_kwargs(self.env_kwargs), n_envs=1, device=self.device,
+                                       precision="fp64")
+        return self._env
+
+    def _record(self, model, path):
+        return record_episode(model, self._eval_env(), path, deterministic=self.deterministic, camera=self.camera,
+                              height=self.height, width=self.width,
+                              framerate=self.env_kwargs.get("framerate", 60), num_steps=10 ** 9,
+                              renderer="device", seed=len(self.videos))
+
+    def __call__(self, model):
+        done = len(model.ep_returns)
+        k = self.render_interval
+        crossed = done // k > self._seen // k
+        self._seen = done
+        if not crossed or getattr(model, "rank", 0) != 0:
+            return True
+        d = os.path.join(self.out_dir, self.run_name)
+        os.makedirs(d, exist_ok=True)
+        path = self._record(model, os.path.join(d, f"episode_{done // k * k}.gif"))
+        if path is not None:
+            self.videos.append(path)
+        return True
+
+    def close(self):
+        if self._env is not None:
+            self._env.close()
+            self._env = None
+
+
+class CallbackList:
+    """SB3's ``CallbackList`` for ``PPO.learn(callback=...)`` (train_sb3.py:217): calls every callback with
+    the model, each one every time, and returns False if any returned False (training then stops)."""
+
+    def __init__(self, callbacks):
+        self.callbacks = list(callbacks)
+
+    def __call__(self, model):
+        go = True
+        for cb in self.callbacks:
+            if cb(model) is False:
+                go = False
+        return go

@@ -119,19 +119,27 @@ def _sphere_hit(o, d, c, r):
     return np.where((h > 0) & (t > 0), t, np.inf)
 
 
-class Renderer:
-    """mujoco.Renderer(model, height, width) surface: update_scene(data, camera), render(), close()."""
+def _free_camera():
+    """The free camera's (forward, rotation): <visual><global> azimuth 120, elevation -20, 3 m from the COM."""
+    az, el = math.radians(120.0), math.radians(-20.0)
+    fwd = np.array([math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el)])
+    z = -fwd
+    x = np.cross(np.array([0.0, 0.0, 1.0]), z)
+    x /= np.linalg.norm(x)
+    return fwd, np.stack([x, np.cross(z, x), z], axis=1)
 
-    def __init__(self, model, height=240, width=320):
+
+CAM_BODY, CAM_COM = 0, 1   # include/hsim.h HS_CAM_BODY / HS_CAM_COM
+
+
+class _Cameras:
+    """The model's MJCF cameras and their poses, shared by the host and the device renderer."""
+
+    def __init__(self, model):
         self.model = model
-        self.height, self.width = int(height), int(width)
         self.cameras = parse_cameras(model.path)
-        self._gtype = np.asarray(model.geom_type, int)
-        self._gsize = np.asarray(model.geom_size, float)
-        self._scene = None
         self._cam0 = {}
 
-    # -- camera -----------------------------------------------------------------------------
     def _resolve(self, camera):
         if camera is None or camera == -1:
             return None
@@ -142,23 +150,48 @@ class Renderer:
             raise ValueError(f"camera {camera!r} not found in {self.model.path}")
         return self.cameras[int(camera)]
 
+    def _trackcom0(self, cam, batch, env):
+        """cam_pos0 / cam_mat0 of a trackcom camera: its offset from the COM and its rotation at qpos0
+        (mj_setConst), computed once."""
+        if cam.id not in self._cam0:
+            p0 = batch.kinematics(env, qpos=self.model.qpos0)
+            R0 = p0["xmat"][cam.body].reshape(3, 3)
+            self._cam0[cam.id] = (p0["xpos"][cam.body] + R0 @ cam.pos - p0["com"], R0 @ cam.rot)
+        return self._cam0[cam.id]
+
     def _camera_pose(self, cam, batch, env, pose):
         if cam is None:   # free camera: <visual><global> azimuth 120, elevation -20 around the COM
-            az, el = math.radians(120.0), math.radians(-20.0)
-            fwd = np.array([math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el)])
-            z = -fwd
-            x = np.cross(np.array([0.0, 0.0, 1.0]), z)
-            x /= np.linalg.norm(x)
-            return pose["com"] - 3.0 * fwd, np.stack([x, np.cross(z, x), z], axis=1), 45.0
+            fwd, R = _free_camera()
+            return pose["com"] - 3.0 * fwd, R, 45.0
         bx, bR = pose["xpos"][cam.body], pose["xmat"][cam.body].reshape(3, 3)
         if cam.mode == "trackcom":
-            if cam.id not in self._cam0:   # cam_pos0 / cam_mat0: offsets at qpos0 (mj_setConst)
-                p0 = batch.kinematics(env, qpos=self.model.qpos0)
-                R0 = p0["xmat"][cam.body].reshape(3, 3)
-                self._cam0[cam.id] = (p0["xpos"][cam.body] + R0 @ cam.pos - p0["com"], R0 @ cam.rot)
-            off, R = self._cam0[cam.id]
+            off, R = self._trackcom0(cam, batch, env)
             return pose["com"] + off, R, cam.fovy
         return bx + bR @ cam.pos, bR @ cam.rot, cam.fovy
+
+    def camera_pack(self, camera, batch, env=0):
+        """``camera`` (id, name or None) as the device renderer's ``(mode, body, pos, rot, fovy)``
+        (include/hsim.h hs_camera): what ``_camera_pose`` computes from a pose, for any pose --
+        CAM_BODY: xpos[body] + xmat[body] pos, xmat[body] rot; CAM_COM: com + pos, rot."""
+        cam = self._resolve(camera)
+        if cam is None:
+            fwd, R = _free_camera()
+            return CAM_COM, 0, -3.0 * fwd, R, 45.0
+        if cam.mode == "trackcom":
+            off, R = self._trackcom0(cam, batch, env)
+            return CAM_COM, 0, off, R, cam.fovy
+        return CAM_BODY, cam.body, cam.pos, cam.rot, cam.fovy
+
+
+class Renderer(_Cameras):
+    """mujoco.Renderer(model, height, width) surface: update_scene(data, camera), render(), close()."""
+
+    def __init__(self, model, height=240, width=320):
+        super().__init__(model)
+        self.height, self.width = int(height), int(width)
+        self._gtype = np.asarray(model.geom_type, int)
+        self._gsize = np.asarray(model.geom_size, float)
+        self._scene = None
 
     def update_scene(self, data, camera=None):
         """``data``: an env's data view (HsData).  ``camera``: id, name or None (free camera)."""
@@ -276,6 +309,72 @@ class Renderer:
 
     def close(self):
         self._scene = None
+
+
+class DeviceRenderer(_Cameras):
+    """``Renderer`` for many frames at once, on the GPU: one batched kinematics launch
+    (``hs_kinematics_batch``) and one ray-cast launch (``hs_render_frames``, the arithmetic of
+    ``Renderer.render`` in fp64) for n frames; the frames stay on the device.  ``batch``: the ``HsBatch``
+    whose env states / precision the poses come from."""
+
+    MAX_LAUNCH_BYTES = 1 << 30   # of output per render launch
+
+    def __init__(self, model, batch, height=240, width=320):
+        super().__init__(model)
+        self.batch = batch
+        self.height, self.width = int(height), int(width)
+
+    def _camera(self, camera):
+        import ctypes as C
+
+        from . import _lib
+        mode, body, pos, rot, fovy = self.camera_pack(camera, self.batch)
+        return _lib.hs_camera(int(mode), int(body), (C.c_double * 3)(*np.asarray(pos, float)),
+                              (C.c_double * 9)(*np.asarray(rot, float).reshape(9)), float(fovy))
+
+    def render_kin(self, kin, camera=None):
+        """Frames of n kinematics records ``kin`` [n, KINDIM] (``HsBatch.kinematics_batch``):
+        a ``torch.uint8`` device tensor [n, H, W, 3]."""
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        b, H, W = self.batch, self.height, self.width
+        if kin.dim() != 2 or kin.shape[1] != _lib.HS_KINDIM or kin.dtype != b.dtype or not kin.is_cuda:
+            raise ValueError(f"kin must be a [n, {_lib.HS_KINDIM}] {b.dtype} device tensor")
+        kin = kin.contiguous()
+        n = kin.shape[0]
+        cam = self._camera(camera)
+        out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=b.device)
+        per = max(1, self.MAX_LAUNCH_BYTES // (H * W * 3))
+        with torch.cuda.device(b.device):
+            st = torch.cuda.current_stream().cuda_stream
+            for f0 in range(0, n, per):
+                k = min(per, n - f0)
+                _lib.check(_lib.lib().hs_render_frames(b._h, k, kin[f0:f0 + k].data_ptr(), C.byref(cam), H, W,
+                                                       out[f0:f0 + k].data_ptr(), st))
+        return out
+
+    def render_envs(self, indices, camera=None):
+        """One frame per env of ``indices`` from its current state."""
+        return self.render_kin(self.batch.kinematics_batch(envs=indices), camera)
+
+    def render_qpos(self, qpos, camera=None):
+        """One frame per row of ``qpos`` [n, nq] (a device tensor stays on the device)."""
+        return self.render_kin(self.batch.kinematics_batch(qpos=qpos), camera)
+
+
+def tile_images(images):
+    """SB3's ``tile_images`` (common/vec_env/base_vec_env.py): n images (h, w, c) in one of
+    ``rows = ceil(sqrt(n))`` by ``cols = ceil(n / rows)`` tiles, row-major, the rest black."""
+    imgs = np.asarray(images)
+    n, h, w, c = imgs.shape
+    rows = int(math.ceil(math.sqrt(n)))
+    cols = int(math.ceil(n / rows))
+    out = np.zeros((rows * cols, h, w, c), imgs.dtype)
+    out[:n] = imgs
+    return out.reshape(rows, cols, h, w, c).transpose(0, 2, 1, 3, 4).reshape(rows * h, cols * w, c)
 
 
 def write_video(path, frames, fps):

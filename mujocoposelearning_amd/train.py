@@ -8,8 +8,10 @@ Differences by design (the hot path is on device):
   same keyword arguments; under a launcher (one process per GPU, torchrun) train_humanoid
   initialises the nccl (RCCL) group itself (init_distributed) and gradients are all-reduced once
   per optimizer step, in lockstep for any n_envs.
-* Callbacks (progress bar, reward stats, video recorder, train_sb3.py:41-106) and tensorboard are
-  out of scope; ``callback(model)`` receives the PPO object after each iteration.
+* ``callback(model)`` receives the PPO object after each iteration.  The video recorder
+  (train_sb3.py:13-61) is ``evaluation.VideoRecorderCallback`` -- its frames are drawn on the GPU --
+  and ``evaluation.CallbackList`` runs it beside ``EvalCallback`` (train_sb3.py:217); the progress bar,
+  the reward-stats callback (train_sb3.py:66-106) and tensorboard are out of scope.
 """
 from __future__ import annotations
 

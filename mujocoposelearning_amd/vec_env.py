@@ -332,20 +332,41 @@ class HumanoidVecEnv(_Base):
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False for _ in self._indices(indices)]
 
-    def get_images(self, indices=None, camera="side", height=480, width=640):
-        """SB3 VecEnv.get_images: one rgb frame per env (render.Renderer over GPU kinematics;
-        host ray casting, ~0.15 s per 480x640 frame, so meant for a few envs)."""
+    def get_images(self, indices=None, camera="side", height=480, width=640, renderer="device"):
+        """SB3 VecEnv.get_images: one rgb frame per env, a list of (H, W, 3) uint8 arrays.
+        ``renderer="device"`` (default): ``render.DeviceRenderer`` -- one kinematics launch, one ray-cast
+        launch and one device-to-host copy for all the envs, so it serves a whole batch.
+        ``renderer="host"``: ``render.Renderer``, numpy ray casting over one ``hs_kinematics`` call per
+        env (profiles/render_device.md has both paths' times)."""
         from types import SimpleNamespace
 
-        from .render import Renderer
+        from .render import DeviceRenderer, Renderer
+        idx = [int(i) for i in self._indices(indices)]
+        if renderer == "device":
+            r = getattr(self, "_device_renderer", None)
+            if r is None or (r.height, r.width) != (height, width):
+                r = self._device_renderer = DeviceRenderer(self.model, self.batch, height=height, width=width)
+            if not idx:
+                return []
+            return list(r.render_envs(idx, camera=camera).cpu().numpy())
+        if renderer != "host":
+            raise ValueError(f"renderer must be 'device' or 'host', got {renderer!r}")
         if getattr(self, "_renderer", None) is None or (self._renderer.height, self._renderer.width) != (height, width):
             self._renderer = Renderer(self.model, height=height, width=width)
         out = []
-        for i in self._indices(indices):
+        for i in idx:
             self._renderer.update_scene(SimpleNamespace(_env=SimpleNamespace(_batch=self.batch, _idx=int(i))),
                                         camera=camera)
             out.append(self._renderer.render())
         return out
+
+    def render(self, mode="rgb_array", **kw):
+        """SB3 VecEnv.render: the images of ``get_images(**kw)`` tiled into one (``render.tile_images``:
+        ceil(sqrt(n)) rows, row-major, black padding).  Only ``mode="rgb_array"`` (no window here)."""
+        if mode != "rgb_array":
+            raise NotImplementedError(f"render mode {mode!r}: only 'rgb_array'")
+        from .render import tile_images
+        return tile_images(self.get_images(**kw))
 
     def _indices(self, indices):
         if indices is None:
