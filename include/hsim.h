@@ -29,6 +29,10 @@
  *   hs_reward_eval       <- REWARD_FUNCTIONS[type](data, params) reward_functions.py:66-269 (the device
  *                           formulas of hs_step on supplied fields)
  *   hs_reward            <- the same on the batch's current states (custom_env.py:263-271 _compute_reward)
+ *   hs_reward_program_*  <- a user's entry in REWARD_FUNCTIONS (reward_functions.py:264-269), compiled to a
+ *                           reward program: create / destroy / info, eval_host (CPU, double), eval (device
+ *                           fields), batch (the batch's states)
+ *   hs_step_program      <- HumanoidEnv.step with such a reward (custom_env.py:152-230): step, program, masked reset
  *   hs_debug_lose_handoff   (test hook: mj_step's warning + mj_resetData path, custom_env.py:160)
  *   hs_debug_queue_order    (test view of the chunk queue's next claim order; no counterpart)
  *   hs_debug_queue_counters (test view of the chunk queue's claim / exit counters; no counterpart)
@@ -495,6 +499,74 @@ int hs_reward_eval(const hs_model* m, int precision, int reward_id, const double
  * the step rewards 0, custom_env.py:201-211) and envs that auto-reset (whose buffers hold the reset
  * state).  Asynchronous. */
 int hs_reward(hs_batch* b, int reward_id, const double* kneel_params, void* out, void* stream);
+
+/* Reward programs <- one more entry in REWARD_FUNCTIONS (reward_functions.py:264-269; the reference's "addition
+ * and selection of custom reward function"), evaluated on the device.  A program is a user's reward function
+ * traced once (reward_program.py) into a flat, branch-free list of n_instr instructions (op, dst, a, b, c),
+ * int32 each, over numbered value slots, with n_consts float64 constants and n_params float64 parameter slots
+ * that every call supplies (reward_config["params"] over the function's defaults, custom_env.py:263-271).  The
+ * opcode table, the operand meaning and one op's arithmetic are csrc/hs_reward_prog.h; every op is one
+ * correctly rounded operation or libm call of the batch precision, never contracted, comparisons with a NaN
+ * are false, and a select evaluates both arms.  The limits (a program is bounded by its LIVE values, the
+ * slots, not by its length): */
+#define HS_RP_MAX_INSTR 4096
+#define HS_RP_MAX_SLOTS 64
+#define HS_RP_MAX_CONSTS 256
+#define HS_RP_MAX_PARAMS 32
+typedef struct hs_reward_program hs_reward_program;
+/* The env_data fields a program may read (reward_functions.py's `env_data.*`), one array per field, each
+ * [n][row] contiguous in the call's precision: qpos [nq], qvel [nv], ctrl [nu], time [1], qfrc_actuator [nv],
+ * cinert [nbody][10], cvel [nbody][6], subtree_com0 [3] (subtree_com[0], the root's row), cfrc_ext [nbody][6],
+ * subtree_linvel [nbody][3].  A field the program does not read may be NULL. */
+typedef struct {
+  const void* qpos;
+  const void* qvel;
+  const void* ctrl;
+  const void* time;
+  const void* qfrc_actuator;
+  const void* cinert;
+  const void* cvel;
+  const void* subtree_com0;
+  const void* cfrc_ext;
+  const void* subtree_linvel;
+} hs_reward_fields;
+/* hs_reward_program_create VALIDATES the encoding against the limits and the model's dimensions before anything
+ * is uploaded: an unknown opcode, a slot / constant / parameter index out of range, a field index outside
+ * the model's nq / nv / nu / nbody, a slot read before it is written, a missing result (the last instruction
+ * must be the one result) or an over-limit count returns -1 with the reason (hs_last_error) and *prog = NULL;
+ * such a program is never launched.  With a GPU present the code is copied to the current device here
+ * (synchronously), so later calls on that device allocate nothing; without one the program still serves
+ * hs_reward_program_eval_host.  hs_reward_program_info: instruction count, slots used and the bit set of the
+ * fields read (bit k = the k-th member of hs_reward_fields); any pointer may be NULL. */
+int hs_reward_program_create(const hs_model* m, const int32_t* code, int n_instr, const double* consts, int n_consts,
+                             int n_params, hs_reward_program** prog);
+void hs_reward_program_destroy(hs_reward_program* prog);
+int hs_reward_program_info(const hs_reward_program* prog, int* n_instr, int* n_slots, unsigned* fields);
+/* The program interpreted on the CPU in double on n states (host arrays of double): needs no GPU.  params:
+ * n_params host doubles.  Synchronous. */
+int hs_reward_program_eval_host(const hs_reward_program* prog, const double* params, int n,
+                                const hs_reward_fields* fields, double* out);
+/* The program on caller-supplied device fields of `precision` (HS_FP32 / HS_FP64), the counterpart of
+ * hs_reward_eval: writes out [n] (device) on the current device.  Asynchronous on `stream`. */
+int hs_reward_program_eval(const hs_reward_program* prog, int precision, const double* params, int n,
+                           const hs_reward_fields* fields, void* out, void* stream);
+/* The program on the batch's own buffers, the counterpart of hs_reward: cinert / cvel / qfrc_actuator are the
+ * obs row's, subtree_com0 the aux row's, cfrc_ext / subtree_linvel zeros unless HS_FULL_STATE.  Refused (before
+ * any launch) when the program reads ctrl or subtree_com and the batch's outputs do not carry them
+ * (HS_OUT_CTRL / HS_OUT_AUX) or data.ctrl is stale, and when a full-state batch has no cfrc_ext /
+ * subtree_linvel buffers.  out: [N] of the batch precision (device).  Asynchronous. */
+int hs_reward_program_batch(hs_batch* b, const hs_reward_program* prog, const double* params, void* out, void* stream);
+/* One env step with a program reward <- HumanoidEnv.step with REWARD_FUNCTIONS[type] a user's function
+ * (custom_env.py:152-230 + SB3 auto-reset), as launches only -- no host synchronisation, no copy:
+ *   1. hs_step with no reward and no auto-reset, whatever the batch's config says;
+ *   2. the program on the post-step, pre-reset state: reward (0 for a truncated env, custom_env.py:203-206),
+ *      total_reward += reward, and for finished envs terminal_obs, terminal_step_count, terminal_total_reward;
+ *   3. if the batch's config has autoreset on: hs_reset masked by the finished envs, with the reset noise an
+ *      auto-reset inside hs_step draws (the bound arrays of hs_set_autoreset_noise or the device RNG).
+ * The same refusals as hs_reward_program_batch, made before step 1 (the step itself rewrites data.ctrl).  For a
+ * program that restates a built-in reward every buffer equals hs_step's with that reward id, bitwise. */
+int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* prog, const double* params,
+                    void* stream);
 
 /* GAE(gamma, lambda) reverse scan over a device rollout buffer, SB3 semantics: [T][N] float32
  * rewards, values, episode_starts; [N] last_values, last_dones; writes [T][N] advantages and

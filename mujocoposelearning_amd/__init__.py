@@ -41,6 +41,10 @@ def __getattr__(name):
     if name in ("Renderer", "DeviceRenderer", "tile_images"):
         from . import render
         return getattr(render, name)
+    if name in ("register_device_reward", "device_reward_program", "DeviceReward", "TracedProgram", "CompiledProgram",
+                "stand_program", "kneeling_program", "walk_program"):
+        from . import reward_program
+        return getattr(reward_program, name)
     if name == "HsBatch":
         from .batch import HsBatch
         return HsBatch

@@ -79,6 +79,18 @@ class hs_camera(C.Structure):
                 ("fovy", C.c_double)]
 
 
+class hs_reward_fields(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel",
+                                          "subtree_com0", "cfrc_ext", "subtree_linvel")]
+
+
+# reward_program.FIELDS name -> hs_reward_fields member
+REWARD_FIELD_MEMBER = {n: ("subtree_com0" if n == "subtree_com" else n)
+                       for n in ("qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel", "subtree_com",
+                                 "cfrc_ext", "subtree_linvel")}
+HS_RP_MAX_INSTR, HS_RP_MAX_SLOTS, HS_RP_MAX_CONSTS, HS_RP_MAX_PARAMS = 4096, 64, 256, 32
+
+
 class hs_batch_info(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_envs", "precision", "nq", "nv", "nu", "nbody", "obs_dim", "elem_size",
                                        "resident_con", "resident_efc", "wide_con", "wide_efc", "resident_waves",
@@ -152,6 +164,13 @@ def lib():
         "hs_reward_eval": (i, [vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hs_pack_outputs": (i, [vp, vp, i, i, vp]),
         "hs_reward": (i, [vp, i, vp, vp, vp]),
+        "hs_reward_program_create": (i, [vp, vp, i, vp, i, i, vp]),
+        "hs_reward_program_destroy": (None, [vp]),
+        "hs_reward_program_info": (i, [vp, vp, vp, vp]),
+        "hs_reward_program_eval_host": (i, [vp, vp, i, vp, vp]),
+        "hs_reward_program_eval": (i, [vp, i, vp, i, vp, vp, vp]),
+        "hs_reward_program_batch": (i, [vp, vp, vp, vp, vp]),
+        "hs_step_program": (i, [vp, vp, vp, vp, vp]),
         "hs_ppo_act": (i, [vp, i, vp, i, vp, vp, u64, u64, vp, i, vp, vp, vp, vp, vp, i, i, vp]),
         "hs_ppo_post": (i, [vp, vp, vp, vp, vp, vp, vp, i, C.c_float, vp, vp, u64, vp, vp, vp, vp, vp, i, vp]),
         "hs_gauss_logp": (i, [vp, i, vp, vp, vp, i, i, vp]),
@@ -208,7 +227,9 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_dgrad_mask_workspace", "hs_dgrad_mask", "hs_dgrad_act", "hs_colsum_pair",
             "hs_colsum_workspace", "hs_colsum", "hs_last_error", "hs_version",
             "hs_rollout_norm", "hs_evaluate_norm", "hs_obs_norm_workspace", "hs_obs_norm", "hs_rms_merge",
-            "hs_return_moments", "hs_reward_scale", "hs_kinematics_batch", "hs_render_frames")
+            "hs_return_moments", "hs_reward_scale", "hs_kinematics_batch", "hs_render_frames",
+            "hs_reward_program_create", "hs_reward_program_destroy", "hs_reward_program_info",
+            "hs_reward_program_eval_host", "hs_reward_program_eval", "hs_reward_program_batch", "hs_step_program")
 
 
 class HsimError(RuntimeError):

@@ -48,19 +48,29 @@ def report_warnings(new, where="step"):
 
 
 def reward_eval(model, name, qpos, qvel, ctrl, time, subtree_com0, subtree_linvel0, cfrc_ext, qfrc_actuator,
-                params=None, registry=None):
+                params=None, registry=None, cinert=None, cvel=None):
     """``REWARD_FUNCTIONS[name](data, params)`` for n states at once, computed by the device reward
     code of the step kernel (``hs_reward_eval``; reward_functions.py:66-269).  Arguments are CUDA
     tensors of one float dtype (float64 = the fp64 engine's formulas, float32 = the fp32 engine's):
     qpos [n][nq], qvel [n][nv], ctrl [n][nu], time [n], subtree_com0 / subtree_linvel0 [n][3],
     cfrc_ext [n][nbody][6], qfrc_actuator [n][nv].  ``params`` are the kneeling reward's overrides
     (merged over its defaults like reward_functions.py:83).  Returns a [n] tensor.  Unknown names raise
-    ValueError like custom_env.py:268-269; user callables have no device formula (HsimError)."""
+    ValueError like custom_env.py:268-269; plain user callables have no device formula (HsimError).
+    A reward registered as a program (``reward_program.register_device_reward``) runs through
+    ``hs_reward_program_eval``; ``params`` are then its parameter overrides, ``cinert`` [n][nbody][10] and
+    ``cvel`` [n][nbody][6] the two further fields a program may read, and of ``subtree_linvel`` a program
+    sees row 0 as given and zeros elsewhere."""
     from .reward_functions import device_reward_id
     torch = _torch()
     rid = device_reward_id(name, registry)
     if rid is None:
-        raise _lib.HsimError(f"reward {name!r} is a host callable: no device formula")
+        from .reward_program import device_reward_program
+        rec = device_reward_program(name, registry)
+        if rec is None:
+            raise _lib.HsimError(f"reward {name!r} is a host callable: no device formula")
+        return _reward_program_eval(model, rec, params, qpos=qpos, qvel=qvel, ctrl=ctrl, time=time,
+                                    subtree_com=subtree_com0, subtree_linvel0=subtree_linvel0, cfrc_ext=cfrc_ext,
+                                    qfrc_actuator=qfrc_actuator, cinert=cinert, cvel=cvel)
     args = [qpos, qvel, ctrl, time, subtree_com0, subtree_linvel0, cfrc_ext, qfrc_actuator]
     dt = qpos.dtype
     if dt not in (torch.float32, torch.float64):
@@ -82,6 +92,38 @@ def reward_eval(model, name, qpos, qvel, ctrl, time, subtree_com0, subtree_linve
         check(lib().hs_reward_eval(model.handle, 1 if dt == torch.float64 else 0, rid,
                                    C.cast(kn, C.c_void_p) if kn is not None else None, n,
                                    *[a.data_ptr() for a in args], out.data_ptr(), st))
+    return out
+
+
+def _reward_program_eval(model, rec, params, subtree_linvel0=None, **fields):
+    """``reward_eval`` for a reward program: the fields it reads, checked, through hs_reward_program_eval."""
+    torch = _torch()
+    prog = rec.compile(model)
+    qpos = fields["qpos"]
+    dt, n = qpos.dtype, qpos.shape[0]
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError("reward_eval: float32 or float64 tensors")
+    if "subtree_linvel" in prog.fields:
+        lv = torch.zeros(n, model.nbody, 3, dtype=dt, device=qpos.device)
+        lv[:, 0] = subtree_linvel0
+        fields["subtree_linvel"] = lv
+    shapes = dict(qpos=(n, model.nq), qvel=(n, model.nv), ctrl=(n, model.nu), time=(n,), subtree_com=(n, 3),
+                  subtree_linvel=(n, model.nbody, 3), cfrc_ext=(n, model.nbody, 6), qfrc_actuator=(n, model.nv),
+                  cinert=(n, model.nbody, 10), cvel=(n, model.nbody, 6))
+    f = _lib.hs_reward_fields()
+    for k in prog.fields:
+        a = fields.get(k)
+        if a is None:
+            raise ValueError(f"reward_eval: the program reads {k}, which was not given")
+        if not a.is_cuda or a.dtype != dt or tuple(a.shape) != shapes[k] or not a.is_contiguous():
+            raise ValueError(f"reward_eval: expected a contiguous CUDA {dt} tensor of shape {shapes[k]} for {k}, got "
+                             f"{tuple(a.shape)} {a.dtype} on {a.device}")
+        setattr(f, _lib.REWARD_FIELD_MEMBER[k], a.data_ptr())
+    out = torch.empty(n, dtype=dt, device=qpos.device)
+    with torch.cuda.device(qpos.device):
+        st = torch.cuda.current_stream().cuda_stream
+        check(lib().hs_reward_program_eval(prog.handle, 1 if dt == torch.float64 else 0, prog.params(params), n,
+                                           C.byref(f), out.data_ptr(), st))
     return out
 
 
@@ -306,6 +348,30 @@ class HsBatch:
         self._launch(lambda h, lo, hi, st: check(lib().hs_step(h, a.data_ptr() + lo * row, st)), a, join=join)
         return self.t["obs"], self.t["reward"], self.t["terminated"], self.t["truncated"]
 
+    def compile_reward(self, name, registry=None):
+        """The native program of the registered program reward ``name`` for this batch's model, resident on
+        this batch's GPU (``reward_program.DeviceReward.compile``); None for any other entry."""
+        from .reward_program import device_reward_program
+        rec = device_reward_program(name, registry)
+        if rec is None:
+            return None
+        with _torch().cuda.device(self.device):
+            return rec.compile(self.model)
+
+    def step_program(self, actions, program, params=None):
+        """One env step with a program reward (``hs_step_program``): the step without reward and auto-reset,
+        the program on the post-step state (reward, total_reward, a finished env's terminal rows), then --
+        with auto-reset configured -- the masked reset, all as launches.  ``program``: a
+        ``reward_program.CompiledProgram`` (``compile_reward``); ``params``: its parameter overrides.
+        One stream group only."""
+        torch = _torch()
+        if len(self._groups) != 1:
+            raise NotImplementedError("step_program: one stream group only")
+        a = torch.as_tensor(actions, device=self.device).to(torch.float32).contiguous()
+        assert a.shape == (self.n, self.model.nu), a.shape
+        check(lib().hs_step_program(self._h, a.data_ptr(), program.handle, program.params(params), self.stream))
+        return self.t["obs"], self.t["reward"], self.t["terminated"], self.t["truncated"]
+
     def step_tape(self, actions, outputs=True):
         """K consecutive ``step`` calls over an action tape [K, N, nu] (float32, on device) in one
         launch (hs_step_tape: a pair's step t + 1 starts once its own step t is committed, so the
@@ -390,7 +456,14 @@ class HsBatch:
         torch = _torch()
         rid = device_reward_id(name, registry)
         if rid is None:
-            raise _lib.HsimError(f"reward {name!r} is a host callable: no device formula")
+            prog = self.compile_reward(name, registry)
+            if prog is None:
+                raise _lib.HsimError(f"reward {name!r} is a host callable: no device formula")
+            if len(self._groups) != 1:
+                raise NotImplementedError("compute_reward with a reward program: one stream group only")
+            out = torch.empty(self.n, dtype=self.dtype, device=self.device)
+            check(lib().hs_reward_program_batch(self._h, prog.handle, prog.params(params), out.data_ptr(), self.stream))
+            return out
         kn = None
         if params is not None:
             p = {**dict(zip(KNEEL_KEYS, KNEEL_DEFAULTS)), **params}

@@ -15,10 +15,15 @@
 #include "hs_api_error.h"
 #include "hs_kernels.h"
 #include "hs_render.h"
+#include "hs_reward_prog.h"
 #include "mjcf.h"
 
 static_assert(HS_KINDIM == hs::KINDIM, "include/hsim.h HS_KINDIM is the kernels' record size");
 static_assert(HS_CAM_BODY == hs::CAM_BODY && HS_CAM_COM == hs::CAM_COM, "include/hsim.h camera modes");
+static_assert(HS_RP_MAX_INSTR == hs::RP_MAX_INSTR && HS_RP_MAX_SLOTS == hs::RP_MAX_SLOTS &&
+                  HS_RP_MAX_CONSTS == hs::RP_MAX_CONSTS && HS_RP_MAX_PARAMS == hs::RP_MAX_PARAMS,
+              "include/hsim.h reward program limits");
+static_assert(sizeof(hs_reward_fields) == hs::RP_NFIELDS * sizeof(void*), "hs_reward_fields: one pointer per field");
 
 struct hs_model {
   hs::HostModel host;
@@ -55,6 +60,19 @@ struct hs_batch {
   float last_tape_ms = -1.f;                 // its duration (hs_last_tape_ms)
   int* kin_envs = nullptr;                   // hs_kinematics_batch: the env-id list on the device (grown on demand)
   int kin_envs_cap = 0;
+  uint8_t* prog_done = nullptr;              // hs_step_program: the per-env done bytes, the mask of its reset launch
+};
+
+// a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on
+struct hs_reward_program {
+  hs::RpDims dims{};
+  std::vector<int32_t> code;
+  std::vector<double> consts;
+  int n_params = 0;
+  hs::RpInfo info;
+  struct Dev { int device; int32_t* code; double* consts; };
+  std::vector<Dev> dev;
+  std::mutex mu;
 };
 
 thread_local std::string hs::g_err;
@@ -529,6 +547,7 @@ hs_batch* hs_batch_create(const hs_model* m, int n_envs, int device, uint64_t se
   if (!hip_ok(hipMalloc(&b->dbg, hs::DBGDIM * 8), "hipMalloc(dbg)") ||
       !hip_ok(hipMalloc((void**)&b->redo, (N + 2) * sizeof(int)), "hipMalloc(redo)") ||
       !hip_ok(hipMalloc((void**)&b->redo_total, sizeof(unsigned long long)), "hipMalloc(redo_total)") ||
+      !hip_ok(hipMalloc((void**)&b->prog_done, N), "hipMalloc(prog_done)") ||
       // chunk-queue hand-off rows, claim counters and pair flags: UNCACHED device memory from the UC
       // pool above, so a hand-off between waves on different CUs / XCDs needs no L2 write-back or
       // invalidate (hs_env_step.h step_pair)
@@ -559,6 +578,7 @@ void hs_batch_destroy(hs_batch* b) {
   if (b->dbg) (void)hipFree(b->dbg);
   if (b->redo) (void)hipFree(b->redo);
   if (b->redo_total) (void)hipFree(b->redo_total);
+  if (b->prog_done) (void)hipFree(b->prog_done);
   if (b->mid) uc_release(b->device, (size_t)b->n * hs::MIDDIM * (b->precision == HS_FP64 ? 8 : 4), b->mid);
   if (b->qsync) uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
   if (b->eval_obs) uc_release(b->device, (size_t)b->n * b->obs_dim * sizeof(float), b->eval_obs);
@@ -1129,6 +1149,8 @@ int hs_reward(hs_batch* b, int reward_id, const double* kneel_params, void* out,
   if (!(b->cfg.outputs & HS_OUT_AUX) || !(b->cfg.outputs & HS_OUT_CTRL) || b->ctrl_stale)
     return fail("hs_reward: needs the aux row (subtree com) and the data.ctrl copy (HS_OUT_AUX | HS_OUT_CTRL) "
                 "written by the last step");
+  if (!b->buf.cfrc_ext || !b->buf.subtree_linvel)
+    return fail("hs_reward: the batch has no cfrc_ext / subtree_linvel buffers (external buffers without them)");
   const hs::HostModel& h = b->model->host;
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
@@ -1159,6 +1181,234 @@ int hs_reward(hs_batch* b, int reward_id, const double* kneel_params, void* out,
     return hip_rc(hs::launch_reward_eval<T>(a, (hipStream_t)stream), "reward_eval_kernel");
   };
   return b->precision == HS_FP64 ? run(0.0) : run(0.0f);
+}
+
+// -- reward programs (hs_reward_prog.h) --------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+const char* const kRpFieldNames[hs::RP_NFIELDS] = {"qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel",
+                                                   "subtree_com[0]", "cfrc_ext", "subtree_linvel"};
+
+// the program's code and constants on `device` (uploaded on first use there; hs_reward_program_create
+// uploads to the device current at the time, so a later launch -- possibly under graph capture -- allocates nothing)
+const hs_reward_program::Dev* rp_resident(hs_reward_program* p, int device) {
+  std::lock_guard<std::mutex> lk(p->mu);
+  for (auto& d : p->dev)
+    if (d.device == device) return &d;
+  DeviceGuard g(device);
+  hs_reward_program::Dev d{device, nullptr, nullptr};
+  const size_t cb = p->code.size() * sizeof(int32_t), kb = std::max<size_t>(p->consts.size(), 1) * sizeof(double);
+  if (!hip_ok(hipMalloc((void**)&d.code, cb), "hipMalloc(reward program)") ||
+      !hip_ok(hipMalloc((void**)&d.consts, kb), "hipMalloc(reward program)") ||
+      !hip_ok(hipMemcpy(d.code, p->code.data(), cb, hipMemcpyHostToDevice), "reward program upload") ||
+      (!p->consts.empty() &&
+       !hip_ok(hipMemcpy(d.consts, p->consts.data(), p->consts.size() * sizeof(double), hipMemcpyHostToDevice),
+               "reward program upload"))) {
+    if (d.code) (void)hipFree(d.code);
+    if (d.consts) (void)hipFree(d.consts);
+    return nullptr;
+  }
+  p->dev.push_back(d);
+  return &p->dev.back();
+}
+
+template <typename T>
+hs::RpArgs<T> rp_args(const hs_reward_program* p, const hs_reward_program::Dev* d, const double* params, int n) {
+  hs::RpArgs<T> a{};
+  a.code = d->code;
+  a.consts = d->consts;
+  a.n_instr = (int)(p->code.size() / 5);
+  a.n_slots = p->info.n_slots;
+  a.n = n;
+  for (int k = 0; k < p->n_params; k++) a.params[k] = params[k];
+  return a;
+}
+
+// the batch's own buffers as a program's fields: cinert / cvel / qfrc_actuator are the obs row's
+// (custom_env.py:242-256), subtree_com[0] the aux row's; cfrc_ext / subtree_linvel read as zeros
+// unless HS_FULL_STATE, as the built-in rewards see them (mj_step leaves them uncomputed)
+template <typename T>
+void rp_batch_fields(const hs_batch* b, hs::RpArgs<T>& a) {
+  const hs::HostModel& h = b->model->host;
+  const int o2 = (h.nq - 2) + h.nv, o3 = o2 + 10 * h.nbody, o4 = o2 + 16 * h.nbody;
+  auto set = [&](int f, const void* p, long long ld) { a.field[f] = (const T*)p; a.ld[f] = ld; };
+  set(hs::RP_F_QPOS, b->buf.qpos, h.nq);
+  set(hs::RP_F_QVEL, b->buf.qvel, h.nv);
+  set(hs::RP_F_CTRL, b->buf.ctrl, h.nu);
+  set(hs::RP_F_TIME, b->buf.time, 1);
+  set(hs::RP_F_QFRC, (const T*)b->buf.obs + o4, b->obs_dim);
+  set(hs::RP_F_CINERT, (const T*)b->buf.obs + o2, b->obs_dim);
+  set(hs::RP_F_CVEL, (const T*)b->buf.obs + o3, b->obs_dim);
+  set(hs::RP_F_COM, (const T*)b->buf.aux + hs::MAXDOF, hs::AUXDIM);
+  set(hs::RP_F_CFRC, b->full_state ? b->buf.cfrc_ext : nullptr, 6 * h.nbody);
+  set(hs::RP_F_LINVEL, b->full_state ? b->buf.subtree_linvel : nullptr, 3 * h.nbody);
+}
+
+// what a program needs of a batch before anything is launched; `stepped`: the check runs ahead of the
+// step that will write the outputs (hs_step_program), so a stale data.ctrl does not matter
+int rp_check_batch(const char* who, const hs_batch* b, const hs_reward_program* p, const double* params, bool stepped) {
+  const std::string w(who);
+  if (!b || !p) return fail(w + ": null argument");
+  if (p->n_params > 0 && !params) return fail(w + ": the program has parameters, params must not be NULL");
+  const hs::HostModel& h = b->model->host;
+  if (p->dims.nq != h.nq || p->dims.nv != h.nv || p->dims.nu != h.nu || p->dims.nbody != h.nbody)
+    return fail(w + ": the program was compiled for a model of other dimensions");
+  const unsigned f = p->info.fields;
+  if ((f & (1u << hs::RP_F_CTRL)) && (!(b->cfg.outputs & HS_OUT_CTRL) || (!stepped && b->ctrl_stale)))
+    return fail(w + ": the program reads ctrl, which needs the data.ctrl copy (HS_OUT_CTRL) written by the last step");
+  if ((f & (1u << hs::RP_F_COM)) && !(b->cfg.outputs & HS_OUT_AUX))
+    return fail(w + ": the program reads subtree_com, which needs the aux row (HS_OUT_AUX) written by the last step");
+  if (b->full_state && (f & ((1u << hs::RP_F_CFRC) | (1u << hs::RP_F_LINVEL))) &&
+      (!b->buf.cfrc_ext || !b->buf.subtree_linvel))
+    return fail(w + ": the batch has no cfrc_ext / subtree_linvel buffers");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hs_reward_program_create(const hs_model* m, const int32_t* code, int n_instr, const double* consts, int n_consts,
+                             int n_params, hs_reward_program** prog) {
+  if (!m || !prog) return fail("hs_reward_program_create: null argument");
+  *prog = nullptr;
+  const hs::HostModel& h = m->host;
+  const hs::RpDims dims{h.nq, h.nv, h.nu, h.nbody};
+  hs::RpInfo info;
+  const std::string why = hs::rp_validate(dims, code, n_instr, consts, n_consts, n_params, &info);
+  if (!why.empty()) return fail("hs_reward_program_create: " + why);
+  auto* p = new hs_reward_program();
+  p->dims = dims;
+  p->code.assign(code, code + 5 * (size_t)n_instr);
+  if (n_consts > 0) p->consts.assign(consts, consts + n_consts);
+  p->n_params = n_params;
+  p->info = info;
+  int ndev = 0, cur = 0;   // with a GPU: resident on the current device now, so no launch has to allocate
+  if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipGetDevice(&cur) == hipSuccess && !rp_resident(p, cur)) {
+    delete p;
+    return -1;
+  }
+  *prog = p;
+  return 0;
+}
+
+void hs_reward_program_destroy(hs_reward_program* p) {
+  if (!p) return;
+  for (auto& d : p->dev) {
+    DeviceGuard g(d.device);
+    (void)hipFree(d.code);
+    (void)hipFree(d.consts);
+  }
+  delete p;
+}
+
+int hs_reward_program_info(const hs_reward_program* p, int* n_instr, int* n_slots, unsigned* fields) {
+  if (!p) return fail("hs_reward_program_info: null program");
+  if (n_instr) *n_instr = (int)(p->code.size() / 5);
+  if (n_slots) *n_slots = p->info.n_slots;
+  if (fields) *fields = p->info.fields;
+  return 0;
+}
+
+int hs_reward_program_eval_host(const hs_reward_program* p, const double* params, int n, const hs_reward_fields* f,
+                                double* out) {
+  if (!p || !f) return fail("hs_reward_program_eval_host: null argument");
+  if (n < 0) return fail("hs_reward_program_eval_host: negative n");
+  if (n == 0) return 0;
+  if (!out || (p->n_params > 0 && !params)) return fail("hs_reward_program_eval_host: null out or params");
+  const double* const* fp = reinterpret_cast<const double* const*>(f);
+  for (int k = 0; k < hs::RP_NFIELDS; k++)
+    if ((p->info.fields & (1u << k)) && !fp[k])
+      return fail(std::string("hs_reward_program_eval_host: the program reads ") + kRpFieldNames[k] + ", which is NULL");
+  hs::rp_eval_host(p->dims, p->code.data(), (int)(p->code.size() / 5), p->consts.data(), params, n, fp, out);
+  return 0;
+}
+
+int hs_reward_program_eval(const hs_reward_program* p, int precision, const double* params, int n,
+                           const hs_reward_fields* f, void* out, void* stream) {
+  if (!p || !f) return fail("hs_reward_program_eval: null argument");
+  if (n < 0) return fail("hs_reward_program_eval: negative n");
+  const int prec = precision & 0xFF;
+  if (prec != HS_FP32 && prec != HS_FP64) return fail("hs_reward_program_eval: precision must be HS_FP32 or HS_FP64");
+  if (n == 0) return 0;
+  if (!out || (p->n_params > 0 && !params)) return fail("hs_reward_program_eval: null out or params");
+  const void* const* fp = reinterpret_cast<const void* const*>(f);
+  for (int k = 0; k < hs::RP_NFIELDS; k++)
+    if ((p->info.fields & (1u << k)) && !fp[k])
+      return fail(std::string("hs_reward_program_eval: the program reads ") + kRpFieldNames[k] + ", which is NULL");
+  int cur = 0;
+  if (!hip_ok(hipGetDevice(&cur), "hipGetDevice")) return -1;
+  const auto* d = rp_resident(const_cast<hs_reward_program*>(p), cur);
+  if (!d) return -1;
+  auto run = [&](auto zero) -> int {
+    using T = decltype(zero);
+    hs::RpArgs<T> a = rp_args<T>(p, d, params, n);
+    for (int k = 0; k < hs::RP_NFIELDS; k++) {
+      a.field[k] = (const T*)fp[k];
+      a.ld[k] = hs::rp_field_len(p->dims, k);
+    }
+    a.out = (T*)out;
+    return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
+  };
+  return prec == HS_FP64 ? run(0.0) : run(0.0f);
+}
+
+int hs_reward_program_batch(hs_batch* b, const hs_reward_program* p, const double* params, void* out, void* stream) {
+  if (!out) return fail("hs_reward_program_batch: null argument");
+  if (rp_check_batch("hs_reward_program_batch", b, p, params, false)) return -1;
+  DeviceGuard g(b->device);
+  const auto* d = rp_resident(const_cast<hs_reward_program*>(p), b->device);
+  if (!d) return -1;
+  if (order_streams(b, (hipStream_t)stream)) return -1;
+  auto run = [&](auto zero) -> int {
+    using T = decltype(zero);
+    hs::RpArgs<T> a = rp_args<T>(p, d, params, b->n);
+    rp_batch_fields<T>(b, a);
+    a.out = (T*)out;
+    return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
+  };
+  return b->precision == HS_FP64 ? run(0.0) : run(0.0f);
+}
+
+int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* p, const double* params, void* stream) {
+  if (!actions) return fail("hs_step_program: actions must not be NULL");
+  if (rp_check_batch("hs_step_program", b, p, params, true)) return -1;
+  DeviceGuard g(b->device);
+  const auto* d = rp_resident(const_cast<hs_reward_program*>(p), b->device);
+  if (!d) return -1;
+  // 1. the env step without a reward and without auto-reset: the program sees the post-step state
+  const hs_env_config saved = b->cfg;
+  b->cfg.reward_id = HS_REWARD_NONE;
+  b->cfg.autoreset = 0;
+  int rc = hs_step(b, actions, stream);
+  b->cfg = saved;
+  if (rc) return rc;
+  // 2. the program, and the step's outcome rows
+  auto run = [&](auto zero) -> int {
+    using T = decltype(zero);
+    hs::RpArgs<T> a = rp_args<T>(p, d, params, b->n);
+    rp_batch_fields<T>(b, a);
+    a.outcome = 1;
+    a.reward = (T*)b->buf.reward;
+    a.total_reward = (T*)b->buf.total_reward;
+    a.terminated = b->buf.terminated;
+    a.truncated = b->buf.truncated;
+    a.obs = (const T*)b->buf.obs;
+    a.terminal_obs = (T*)b->buf.terminal_obs;
+    a.obs_dim = b->obs_dim;
+    a.step_count = b->buf.step_count;
+    a.term_step_count = b->buf.terminal_step_count;
+    a.term_total_reward = (T*)b->buf.terminal_total_reward;
+    a.done = b->prog_done;
+    return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
+  };
+  rc = b->precision == HS_FP64 ? run(0.0) : run(0.0f);
+  if (rc) return rc;
+  // 3. SB3's auto-reset of the finished envs: the masked reset, with the noise an in-kernel auto-reset draws
+  if (!saved.autoreset) return 0;
+  return launch(b, hs::MODE_RESET, nullptr, b->prog_done, b->ar_qpos_noise, b->ar_qvel_noise, 1, stream);
 }
 
 int hs_pack_outputs(hs_batch* b, double* out, int ncols, int warnings, void* stream) {

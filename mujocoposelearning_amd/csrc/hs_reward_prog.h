@@ -1,0 +1,232 @@
+// Reward programs (include/hsim.h hs_reward_program_*): a user's reward function, traced once in Python
+// (reward_program.py) into a flat, branch-free instruction list, evaluated for every env of a batch by
+// reward_program_kernel (hs_reward_prog.hip) or on the host in double (rp_eval_host below).
+// This header is the one definition of the opcode table, the limits, one op's arithmetic (host and
+// device, the same expression) and the validator; it compiles as plain C++ too (tools/reward_prog_check.cpp).
+//
+// Encoding: n_instr x (op, dst, a, b, c) int32, n_consts float64 constants, n_params float64 parameter
+// slots supplied at every call.  Values live in numbered slots (the tracer allocates them by liveness);
+// dst is the slot an instruction writes, a / b / c the slots it reads, except:
+//   RP_CONST  a = constant index      RP_PARAM  a = parameter index
+//   RP_LOAD   a = field (RP_F_*), b = the flat index within the env's row of that field
+//   RP_RESULT a = the slot holding the reward; exactly one, the last instruction
+// Comparisons and the logical ops give 1 or 0; RP_WHERE and the logical ops read "not zero" as true.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RP_HD __host__ __device__
+#else
+#define RP_HD
+#endif
+
+namespace hs {
+
+// the limits (include/hsim.h HS_RP_MAX_*); a program is bounded by its LIVE values, not its length
+constexpr int RP_MAX_INSTR = 4096, RP_MAX_SLOTS = 64, RP_MAX_CONSTS = 256, RP_MAX_PARAMS = 32;
+
+enum RpOp : int32_t {
+  RP_CONST = 0, RP_PARAM, RP_LOAD,
+  RP_ADD, RP_SUB, RP_MUL, RP_DIV, RP_ATAN2, RP_LT, RP_LE, RP_GT, RP_GE, RP_EQ, RP_NE, RP_AND, RP_OR,   // binary
+  RP_NEG, RP_ABS, RP_SQRT, RP_EXP, RP_LOG, RP_SIN, RP_COS, RP_TANH, RP_ASIN, RP_ACOS, RP_NOT,          // unary
+  RP_WHERE,                                                                                             // ternary
+  RP_RESULT,
+  RP_NOPS
+};
+
+// the env_data fields a program may read, and the row each is indexed within
+enum RpField : int32_t {
+  RP_F_QPOS = 0,   // [nq]
+  RP_F_QVEL,       // [nv]
+  RP_F_CTRL,       // [nu]
+  RP_F_TIME,       // [1]
+  RP_F_QFRC,       // qfrc_actuator [nv]
+  RP_F_CINERT,     // [nbody][10]
+  RP_F_CVEL,       // [nbody][6]
+  RP_F_COM,        // subtree_com[0] [3] (the root's row: what the aux row holds)
+  RP_F_CFRC,       // cfrc_ext [nbody][6]
+  RP_F_LINVEL,     // subtree_linvel [nbody][3]
+  RP_NFIELDS
+};
+
+struct RpDims { int nq, nv, nu, nbody; };
+
+inline int rp_field_len(const RpDims& d, int f) {
+  switch (f) {
+    case RP_F_QPOS: return d.nq;
+    case RP_F_QVEL: return d.nv;
+    case RP_F_CTRL: return d.nu;
+    case RP_F_TIME: return 1;
+    case RP_F_QFRC: return d.nv;
+    case RP_F_CINERT: return 10 * d.nbody;
+    case RP_F_CVEL: return 6 * d.nbody;
+    case RP_F_COM: return 3;
+    case RP_F_CFRC: return 6 * d.nbody;
+    case RP_F_LINVEL: return 3 * d.nbody;
+  }
+  return 0;
+}
+
+// slots an op reads (0 for RP_CONST / RP_PARAM / RP_LOAD, whose operands are indices; RP_RESULT reads one)
+RP_HD inline int rp_arity(int op) {
+  if (op >= RP_ADD && op <= RP_OR) return 2;
+  if ((op >= RP_NEG && op <= RP_NOT) || op == RP_RESULT) return 1;
+  if (op == RP_WHERE) return 3;
+  return 0;
+}
+
+// One op's arithmetic: each a single correctly rounded operation (or one libm call) of T, never
+// contracted, so a program rounds exactly as the same expression written out in reward_formula.
+// A comparison with a NaN is false (RP_NE: true); RP_WHERE selects, both arms are always evaluated.
+template <typename T>
+RP_HD inline T rp_op(int op, T a, T b, T c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  switch (op) {
+    case RP_ADD: return a + b;
+    case RP_SUB: return a - b;
+    case RP_MUL: return a * b;
+    case RP_DIV: return a / b;
+    case RP_ATAN2: return atan2(a, b);
+    case RP_LT: return a < b ? T(1) : T(0);
+    case RP_LE: return a <= b ? T(1) : T(0);
+    case RP_GT: return a > b ? T(1) : T(0);
+    case RP_GE: return a >= b ? T(1) : T(0);
+    case RP_EQ: return a == b ? T(1) : T(0);
+    case RP_NE: return a != b ? T(1) : T(0);
+    case RP_AND: return (a != T(0) && b != T(0)) ? T(1) : T(0);
+    case RP_OR: return (a != T(0) || b != T(0)) ? T(1) : T(0);
+    case RP_NEG: return -a;
+    case RP_ABS: return fabs(a);
+    case RP_SQRT: return sqrt(a);
+    case RP_EXP: return exp(a);
+    case RP_LOG: return log(a);
+    case RP_SIN: return sin(a);
+    case RP_COS: return cos(a);
+    case RP_TANH: return tanh(a);
+    case RP_ASIN: return asin(a);
+    case RP_ACOS: return acos(a);
+    case RP_NOT: return a != T(0) ? T(0) : T(1);
+    case RP_WHERE: return a != T(0) ? b : c;
+  }
+  return T(0);
+}
+
+// What validation learns about a program.
+struct RpInfo {
+  int n_slots = 0;        // highest slot written + 1
+  unsigned fields = 0;    // bit f set: the program reads field f
+};
+
+// Validate an encoding against the limits and a model's dimensions.  Returns "" and fills `info`, or
+// the reason a program is refused: nothing that fails here is ever uploaded or launched.
+inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr, const double* consts,
+                               int n_consts, int n_params, RpInfo* info) {
+  auto at = [](int i) { return " (instruction " + std::to_string(i) + ")"; };
+  if (n_instr < 1 || n_instr > RP_MAX_INSTR)
+    return "reward program: " + std::to_string(n_instr) + " instructions, the limit is " + std::to_string(RP_MAX_INSTR);
+  if (n_consts < 0 || n_consts > RP_MAX_CONSTS)
+    return "reward program: " + std::to_string(n_consts) + " constants, the limit is " + std::to_string(RP_MAX_CONSTS);
+  if (n_params < 0 || n_params > RP_MAX_PARAMS)
+    return "reward program: " + std::to_string(n_params) + " parameters, the limit is " + std::to_string(RP_MAX_PARAMS);
+  if (!code || (n_consts > 0 && !consts)) return "reward program: null code or constants";
+  bool written[RP_MAX_SLOTS] = {};
+  RpInfo r;
+  for (int i = 0; i < n_instr; i++) {
+    const int32_t* in = code + 5 * (size_t)i;
+    const int op = in[0], dst = in[1];
+    if (op < 0 || op >= RP_NOPS) return "reward program: unknown opcode " + std::to_string(op) + at(i);
+    if (op == RP_RESULT && i != n_instr - 1) return "reward program: a result before the last instruction" + at(i);
+    if (op != RP_RESULT && i == n_instr - 1) return "reward program: missing result (the last instruction must be the result)";
+    const int ar = rp_arity(op);
+    for (int k = 0; k < ar; k++) {
+      const int s = in[2 + k];
+      if (s < 0 || s >= RP_MAX_SLOTS)
+        return "reward program: slot " + std::to_string(s) + " out of range [0, " + std::to_string(RP_MAX_SLOTS) + ")" + at(i);
+      if (!written[s]) return "reward program: slot " + std::to_string(s) + " is read before it is written" + at(i);
+    }
+    if (op == RP_CONST && (in[2] < 0 || in[2] >= n_consts))
+      return "reward program: constant index " + std::to_string(in[2]) + " out of range" + at(i);
+    if (op == RP_PARAM && (in[2] < 0 || in[2] >= n_params))
+      return "reward program: parameter index " + std::to_string(in[2]) + " out of range" + at(i);
+    if (op == RP_LOAD) {
+      if (in[2] < 0 || in[2] >= RP_NFIELDS) return "reward program: unknown field " + std::to_string(in[2]) + at(i);
+      if (in[3] < 0 || in[3] >= rp_field_len(d, in[2]))
+        return "reward program: field index " + std::to_string(in[3]) + " outside the model's dimensions (field " +
+               std::to_string(in[2]) + " has " + std::to_string(rp_field_len(d, in[2])) + " values)" + at(i);
+      r.fields |= 1u << in[2];
+    }
+    if (op == RP_RESULT) continue;
+    if (dst < 0 || dst >= RP_MAX_SLOTS)
+      return "reward program: slot " + std::to_string(dst) + " out of range [0, " + std::to_string(RP_MAX_SLOTS) + ")" + at(i);
+    written[dst] = true;
+    if (dst + 1 > r.n_slots) r.n_slots = dst + 1;
+  }
+  if (info) *info = r;
+  return "";
+}
+
+// The host interpreter: a VALIDATED program on n states in double.  field[f]: [n][rp_field_len(d, f)]
+// contiguous doubles, or NULL for a field the program does not read (checked by the caller).
+inline void rp_eval_host(const RpDims& d, const int32_t* code, int n_instr, const double* consts, const double* params,
+                         int n, const double* const* field, double* out) {
+  int len[RP_NFIELDS];
+  for (int f = 0; f < RP_NFIELDS; f++) len[f] = rp_field_len(d, f);
+  for (int e = 0; e < n; e++) {
+    double v[RP_MAX_SLOTS];
+    double res = 0;
+    for (int i = 0; i < n_instr; i++) {
+      const int32_t* in = code + 5 * (size_t)i;
+      const int op = in[0];
+      double r;
+      if (op == RP_CONST) r = consts[in[2]];
+      else if (op == RP_PARAM) r = params[in[2]];
+      else if (op == RP_LOAD) r = field[in[2]][(size_t)e * len[in[2]] + in[3]];
+      else if (op == RP_RESULT) { res = v[in[2]]; break; }
+      else {
+        const int ar = rp_arity(op);
+        r = rp_op<double>(op, v[in[2]], ar > 1 ? v[in[3]] : 0.0, ar > 2 ? v[in[4]] : 0.0);
+      }
+      v[in[1]] = r;
+    }
+    out[e] = res;
+  }
+}
+
+#if defined(__HIPCC__)
+// reward_program_kernel's arguments.  field[f] is the base of field f and ld[f] its env stride in
+// values (a NULL field reads as 0: cfrc_ext / subtree_linvel without HS_FULL_STATE).  outcome = 0:
+// out[env] = the program's value.  outcome = 1 (hs_step_program, after a step without reward or
+// auto-reset): the env step's outcome rows, see the kernel.
+template <typename T>
+struct RpArgs {
+  const int32_t* code;
+  const double* consts;
+  int n_instr, n_slots, n, outcome;
+  const T* field[RP_NFIELDS];
+  long long ld[RP_NFIELDS];
+  double params[RP_MAX_PARAMS];
+  T* out;
+  // outcome mode: the batch's rows
+  T* reward;
+  T* total_reward;
+  const uint8_t* terminated;
+  const uint8_t* truncated;
+  const T* obs;
+  T* terminal_obs;
+  int obs_dim;
+  const int32_t* step_count;
+  int32_t* term_step_count;
+  T* term_total_reward;
+  uint8_t* done;
+};
+
+template <typename T>
+hipError_t launch_reward_program(const RpArgs<T>& a, hipStream_t stream);
+#endif
+
+}  // namespace hs

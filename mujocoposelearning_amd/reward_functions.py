@@ -5,6 +5,8 @@
 Each built-in also has a DEVICE implementation inside the step kernel (``hs_reward.h``
 ``compute_reward``); envs use the device path for built-ins and fall back to calling the
 Python function on a read-only ``data`` view for user-registered callables (slow, correct).
+A user's reward registered through ``reward_program.register_device_reward`` runs on the device
+too: its entry here is the function's numeric twin, and the envs step it as a reward program.
 """
 import numpy as np
 

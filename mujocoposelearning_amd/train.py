@@ -95,8 +95,9 @@ def train_humanoid(env_kwargs: dict, ppo_kwargs: dict, xml_path: str = DEFAULT_X
     start, stop = shard_envs(n_total, world, rank)
     env = HumanoidVecEnv(env_config_from_kwargs(env_kwargs, xml_path), n_envs=stop - start, device=local_rank,
                          precision=precision, seed=seed * 1_000_003 + start)
-    if env.graph_safe:     # device reward: the trainer reads neither the aux row nor the ctrl copy
-        env.batch.configure(aux=False, ctrl=False)
+    if env.graph_safe:     # device reward: the trainer reads neither the aux row nor the ctrl copy;
+        aux, ctrl = env.required_outputs()   # a reward program keeps the ones it reads, and only those
+        env.batch.configure(aux=aux, ctrl=ctrl)
     # env_kwargs["normalize"] (rl-zoo style): True, or a dict of VecNormalize's keywords
     norm = env_kwargs.get("normalize", False)
     raw_env = env

@@ -80,15 +80,25 @@ class HumanoidVecEnv(_Base):
         rtype = self.reward_config.get("type", "default")
         rid = _rf.device_reward_id(rtype)
         params = self.reward_config.get("params")
+        # a reward registered as a program (reward_program.register_device_reward) runs on the device:
+        # hs_step_program evaluates it after the step and resets the finished envs, all as launches
+        self._program = self.batch.compile_reward(rtype) if rid is None else None
+        self._program_params = None
+        if self._program is not None:
+            if len(self.batch._groups) != 1:
+                raise NotImplementedError("a reward program steps one stream group (groups=1)")
+            self._program.params(params)          # an unknown key raises here, not at the first step
+            self._program_params = params
         # user-registered reward callables run on the host over per-env data views (slow, correct):
         # the kernel then steps without a reward and without auto-reset, so the callable sees the
         # pre-reset state; finished envs are reset by a second (masked) launch
-        self._host_reward = None if rid is not None else _rf.REWARD_FUNCTIONS[rtype]
+        on_device = rid is not None or self._program is not None
+        self._host_reward = None if on_device else _rf.REWARD_FUNCTIONS[rtype]
         # each SubprocVecEnv worker holds its own copy of reward_config (the callables may mutate params)
         self._host_params = ([copy.deepcopy(params) for _ in range(n_envs)] if self._host_reward is not None
                              else None)
         self.batch.configure(frame_skip=self.frame_skip, duration=self.duration, max_steps=750,
-                             reward_id=rid if rid is not None else -1, autoreset=1 if rid is not None else 0,
+                             reward_id=rid if rid is not None else -1, autoreset=1 if on_device else 0,
                              max_newton=max_newton, init_height=1.282, noise_scale=0.01,
                              kneel_params=params if rid == 1 and params else None)
         obs_space = Box(low=-np.inf, high=np.inf, shape=(self.batch.obs_dim,), dtype=np.float64)
@@ -128,7 +138,8 @@ class HumanoidVecEnv(_Base):
         engine with the device reward and on-device reset noise (graph_safe), one stream group and
         auto-reset on."""
         b = self.batch
-        if (not self.graph_safe or b.precision != "fp64" or not b.cfg.autoreset or len(b._groups) != 1
+        if (not self.graph_safe or self._program is not None or b.precision != "fp64" or not b.cfg.autoreset
+                or len(b._groups) != 1
                 or int(self.model.field("opt_solver")[0]) != 0):
             return None
         return b._groups[0][0]
@@ -147,7 +158,7 @@ class HumanoidVecEnv(_Base):
             return self.batch.reset()
         qn, vn = self._draw_noise(range(self.num_envs))
         obs = self.batch.reset(qpos_noise=qn, qvel_noise=vn)
-        if self._host_reward is None:    # device auto-reset reads the pre-drawn next noise
+        if self._host_reward is None and self._program is None:   # device auto-reset reads the pre-drawn next noise
             self._bind_next_noise()
         return obs
 
@@ -157,10 +168,42 @@ class HumanoidVecEnv(_Base):
         call; ``self.batch.terminal_obs`` holds pre-reset obs of envs that just finished."""
         if self._host_reward is not None:
             return self._step_host_reward(actions)
+        if self._program is not None:
+            return self._step_program(actions)
         out = self.batch.step(actions)
         if self._streams is not None:     # host noise streams: refresh the envs that auto-reset (syncs)
             self._refresh_noise(((out[2] != 0) | (out[3] != 0)).cpu().numpy())
         return out
+
+    def _step_program(self, actions):
+        """The env step with a program reward.  On-device reset noise: hs_step_program's three launches, no
+        host sync.  SB3-seeded host noise streams: the step and the program with auto-reset off, then the
+        finished envs are read back and reset with noise drawn from their streams, as on the host path."""
+        b = self.batch
+        if self._streams is None:
+            return b.step_program(actions, self._program, self._program_params)
+        import torch
+        b.configure(autoreset=0)
+        try:
+            out = b.step_program(actions, self._program, self._program_params)
+        finally:
+            b.configure(autoreset=1)
+        done = (out[2] != 0) | (out[3] != 0)
+        if bool(done.any()):
+            qn, vn = self._draw_noise(np.flatnonzero(done.cpu().numpy()))
+            b.reset(mask=done.to(torch.uint8), qpos_noise=qn, qvel_noise=vn)
+        return out
+
+    def required_outputs(self):
+        """(aux, ctrl): the optional per-env outputs this env's reward needs written at every step -- what a
+        trainer that otherwise needs neither (train.py) keeps on.  Built-in rewards run inside the step
+        kernel and need none; a reward program needs the aux row if it reads subtree_com, the data.ctrl copy
+        if it reads ctrl; a host callable needs both."""
+        if self._host_reward is not None:
+            return True, True
+        if self._program is not None:
+            return "subtree_com" in self._program.fields, "ctrl" in self._program.fields
+        return False, False
 
     def _step_host_reward(self, actions):
         """custom_env.py:201-211 with a host reward callable: step (no auto-reset), evaluate

@@ -1,0 +1,105 @@
+"""Cost of a reward program against the built-in reward and against the host-callable path
+(profiles/reward_programs.md): env steps/s of HumanoidVecEnv.step_tensors at 4096 fp64 envs with bench.py's
+headline protocol (random-action tape T1, episode clocks staggered, one untimed episode of preconditioning,
+warm-up, then timed steps between synchronisations), for
+
+  builtin   reward_config {"type": "stand"}: one launch per env step;
+  program   the same reward restated as a program (reward_program.stand_program): three launches;
+  host      the same function's numeric twin registered as a plain callable: the host path (six fields copied
+            out, one Python call per env, rewards copied back).  It steps 4096 Python calls per env step, so
+            it is timed over --host-steps steps only and takes its preconditioned state from the program env
+            (qpos, qvel, warm start, clocks, step counts) instead of running an episode itself.
+
+Prints one JSON line per leg.  Under `rocprofv3 --kernel-trace --stats -- python ... --legs program` the trace
+holds the program launch's and the masked reset's kernel times.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+XML = os.path.join(ROOT, "mujocoposelearning_amd", "assets", "humanoid.xml")
+FRAME_SKIP, DURATION, TIMESTEP = 3, 10.0, 0.005
+EPISODE = math.ceil(DURATION / (FRAME_SKIP * TIMESTEP) - 1e-9)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--host-steps", type=int, default=3)
+    ap.add_argument("--legs", default="builtin,program,host")
+    ap.add_argument("--no-precondition", action="store_true")
+    args = ap.parse_args()
+    from mujocoposelearning_amd import reward_functions as rf
+    from mujocoposelearning_amd import reward_program as rw
+    from mujocoposelearning_amd.model import HsModel
+    from mujocoposelearning_amd.vec_env import HumanoidVecEnv
+    rw.register_device_reward("stand_program", rw.stand_program)
+    twin = rf.REWARD_FUNCTIONS["stand_program"]
+    rf.REWARD_FUNCTIONS["stand_callable"] = lambda data, params=None: twin(data, params)
+    dev = torch.device("cuda", 0)
+    model = HsModel(XML)
+    n = args.envs
+    g = torch.Generator(device=dev).manual_seed(1)
+    tape = (torch.rand(1024, n, model.nu, device=dev, generator=g) * 2 - 1).contiguous()
+
+    def make(rtype):
+        e = HumanoidVecEnv({"model_path": XML, "duration": DURATION, "frame_skip": FRAME_SKIP,
+                            "reward_config": {"type": rtype}}, n_envs=n, precision="fp64", seed=0, model=model)
+        aux, ctrl = e.required_outputs()
+        e.batch.configure(aux=aux, ctrl=ctrl)        # what a trainer keeps (train.py)
+        e.reset_tensors()
+        return e
+
+    def precondition(e):
+        if args.no_precondition:
+            return
+        e.batch.set_state(time=np.floor(np.arange(n) * EPISODE / n) * FRAME_SKIP * TIMESTEP + TIMESTEP)
+        for k in range(EPISODE):
+            e.step_tensors(tape[k % 1024])
+
+    def timed(e, steps, warmup):
+        for k in range(warmup):
+            e.step_tensors(tape[(EPISODE + k) % 1024])
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for k in range(steps):
+            e.step_tensors(tape[(EPISODE + warmup + k) % 1024])
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t0
+
+    legs = args.legs.split(",")
+    envs = {}
+    for leg, rtype in (("builtin", "stand"), ("program", "stand_program")):
+        if leg in legs or (leg == "program" and "host" in legs):
+            e = envs[leg] = make(rtype)
+            precondition(e)
+            if leg in legs:
+                el = timed(e, args.steps, args.warmup)
+                print(json.dumps({"leg": leg, "envs": n, "steps": args.steps, "env_steps_per_s": n * args.steps / el,
+                                  "ms_per_step": 1e3 * el / args.steps,
+                                  "reward_mean": float(e.batch.reward.mean())}), flush=True)
+    if "host" in legs:
+        src = envs["program"]
+        e = make("stand_callable")
+        assert e._host_reward is not None
+        e.batch.set_state(**{k: v for k, v in src.batch.get_state().items() if k != "ctrl"})
+        for k in ("step_count", "episode", "total_reward"):
+            e.batch.t[k].copy_(src.batch.t[k])
+        el = timed(e, args.host_steps, 1)
+        print(json.dumps({"leg": "host", "envs": n, "steps": args.host_steps,
+                          "env_steps_per_s": n * args.host_steps / el, "ms_per_step": 1e3 * el / args.host_steps,
+                          "reward_mean": float(e.batch.reward.mean())}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
