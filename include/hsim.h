@@ -33,6 +33,10 @@
  *                           reward program: create / destroy / info, eval_host (CPU, double), eval (device
  *                           fields), batch (the batch's states)
  *   hs_step_program      <- HumanoidEnv.step with such a reward (custom_env.py:152-230): step, program, masked reset
+ *   hs_set_termination   <- the fall conditions custom_env.py:167-200 holds commented out (height < 0.8 for a
+ *                           grace period; height < 0.8 or |roll|, |pitch| > 45 deg): a predicate on the post-step
+ *                           state that ends the episode; hs_apply_termination (its outcome launch alone),
+ *                           hs_termination_state (its buffers), hs_termination_eval_host (CPU, double)
  *   hs_debug_lose_handoff   (test hook: mj_step's warning + mj_resetData path, custom_env.py:160)
  *   hs_debug_queue_order    (test view of the chunk queue's next claim order; no counterpart)
  *   hs_debug_queue_counters (test view of the chunk queue's claim / exit counters; no counterpart)
@@ -567,6 +571,54 @@ int hs_reward_program_batch(hs_batch* b, const hs_reward_program* prog, const do
  * program that restates a built-in reward every buffer equals hs_step's with that reward id, bitwise. */
 int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* prog, const double* params,
                     void* stream);
+
+/* Termination conditions <- the fall conditions custom_env.py:167-200 holds commented out (`height < 0.8` held
+ * for a grace period, custom_env.py:169-180 without its reward scaling; `height < 0.8` or |roll|, |pitch| > 45
+ * degrees, custom_env.py:183-200) and Gymnasium Humanoid's terminate_when_unhealthy: an episode that ends on a
+ * condition of the state.  A condition is a PREDICATE, a program of the reward-program language above whose value
+ * is read as a truth value (it holds iff the value is non-zero and not NaN; comparisons with a NaN are false),
+ * plus an integer grace period: the episode ends at the first env step at which the predicate has held for
+ * grace_steps >= 1 consecutive env steps of that episode.  The per-env counter lives in the batch and belongs
+ * to the episode: it is stored with the env's `episode` number and reads as 0 when that number differs from the
+ * current one, so every reset (auto, masked, hs_reset) clears it; hs_state_io leaves it alone.
+ *
+ * hs_set_termination: predicate NULL clears the condition.  Otherwise the predicate is checked against the
+ * batch as hs_reward_program_batch checks a program (model dimensions; ctrl / subtree_com need HS_OUT_CTRL /
+ * HS_OUT_AUX) and refused before anything is launched; params (n_params doubles) are copied, the predicate is
+ * NOT (it must outlive its use); the counter, its episode tag and the early_terminated bytes are allocated
+ * once per batch and cleared at every call.  Synchronous.  Off (the default) nothing changes: a batch without
+ * a condition runs exactly the launches it ran before.
+ *
+ * With a condition set, hs_step (with a device reward) and hs_step_program are, as launches only:
+ *   1. the step without auto-reset (hs_step_program: and without reward), whatever the config says;
+ *   2. ONE outcome launch on the post-step, pre-reset state: the reward program if there is one (else the step
+ *      kernel's reward / total_reward stay), the predicate, the grace counter, early = count >= grace_steps,
+ *      terminated |= early (whether or not the env is truncated; TimeLimit.truncated stays truncated &&
+ *      !terminated), the early_terminated byte, and every finished env's terminal_obs / terminal_step_count /
+ *      terminal_total_reward;
+ *   3. if the config has autoreset on: hs_reset masked by terminated || truncated, with the auto-reset's noise.
+ * hs_step with HS_REWARD_NONE is the step alone, as configured: the reward is the caller's, and so is the
+ * outcome that must follow it -- write reward / total_reward, then call hs_apply_termination, which is launch 2
+ * on the batch's current state with no reset (call it once per env step: it advances the grace counter).
+ * One stream group.
+ *
+ * THE LIMIT: the fused launches -- hs_step_tape, hs_rollout*, hs_evaluate* -- refuse a batch with a condition
+ * set (-1, the reason in hs_last_error).  The host bounds such a launch so that each env finishes at most one
+ * episode in it, from the shortest possible episode; a state-dependent end makes that bound unknowable.
+ *
+ * hs_termination_state: returns 1 if a condition is set, else 0; *grace_steps (0 when none) and the device
+ * pointers of the [N] early_terminated bytes, grace counters and their episode tags (NULL before the first
+ * hs_set_termination); any out pointer may be NULL.
+ * hs_termination_eval_host: predicate + grace update over n host states in double, the counterpart of
+ * hs_reward_program_eval_host (needs no GPU): episode [n] the envs' current episode numbers, count /
+ * episode_tag [n] read and updated in place, early [n] written. */
+int hs_set_termination(hs_batch* b, const hs_reward_program* predicate, const double* params, int grace_steps);
+int hs_apply_termination(hs_batch* b, void* stream);
+int hs_termination_state(const hs_batch* b, int* grace_steps, const uint8_t** early_terminated,
+                         const int32_t** grace_count, const int32_t** grace_episode);
+int hs_termination_eval_host(const hs_reward_program* predicate, const double* params, int grace_steps, int n,
+                             const hs_reward_fields* fields, const int32_t* episode, int32_t* count,
+                             int32_t* episode_tag, uint8_t* early);
 
 /* GAE(gamma, lambda) reverse scan over a device rollout buffer, SB3 semantics: [T][N] float32
  * rewards, values, episode_starts; [N] last_values, last_dones; writes [T][N] advantages and

@@ -42,7 +42,8 @@ def __getattr__(name):
         from . import render
         return getattr(render, name)
     if name in ("register_device_reward", "device_reward_program", "DeviceReward", "TracedProgram", "CompiledProgram",
-                "stand_program", "kneeling_program", "walk_program"):
+                "stand_program", "kneeling_program", "walk_program", "register_device_termination",
+                "device_termination", "DeviceTermination", "TERMINATION_FUNCTIONS"):
         from . import reward_program
         return getattr(reward_program, name)
     if name == "HsBatch":

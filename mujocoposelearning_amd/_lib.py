@@ -171,6 +171,10 @@ def lib():
         "hs_reward_program_eval": (i, [vp, i, vp, i, vp, vp, vp]),
         "hs_reward_program_batch": (i, [vp, vp, vp, vp, vp]),
         "hs_step_program": (i, [vp, vp, vp, vp, vp]),
+        "hs_set_termination": (i, [vp, vp, vp, i]),
+        "hs_apply_termination": (i, [vp, vp]),
+        "hs_termination_state": (i, [vp, vp, vp, vp, vp]),
+        "hs_termination_eval_host": (i, [vp, vp, i, i, vp, vp, vp, vp, vp]),
         "hs_ppo_act": (i, [vp, i, vp, i, vp, vp, u64, u64, vp, i, vp, vp, vp, vp, vp, i, i, vp]),
         "hs_ppo_post": (i, [vp, vp, vp, vp, vp, vp, vp, i, C.c_float, vp, vp, u64, vp, vp, vp, vp, vp, i, vp]),
         "hs_gauss_logp": (i, [vp, i, vp, vp, vp, i, i, vp]),
@@ -229,7 +233,8 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_rollout_norm", "hs_evaluate_norm", "hs_obs_norm_workspace", "hs_obs_norm", "hs_rms_merge",
             "hs_return_moments", "hs_reward_scale", "hs_kinematics_batch", "hs_render_frames",
             "hs_reward_program_create", "hs_reward_program_destroy", "hs_reward_program_info",
-            "hs_reward_program_eval_host", "hs_reward_program_eval", "hs_reward_program_batch", "hs_step_program")
+            "hs_reward_program_eval_host", "hs_reward_program_eval", "hs_reward_program_batch", "hs_step_program",
+            "hs_set_termination", "hs_apply_termination", "hs_termination_state", "hs_termination_eval_host")
 
 
 class HsimError(RuntimeError):

@@ -47,6 +47,14 @@ def report_warnings(new, where="step"):
                       if new[:3].any() else ""), RuntimeWarning, stacklevel=3)
 
 
+class _DeviceBytes:
+    """A [n] uint8 buffer of the native library as torch sees it (``torch.as_tensor`` reads the interface)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "|u1", "data": (int(ptr), False),
+                                         "strides": None, "version": 2}
+
+
 def reward_eval(model, name, qpos, qvel, ctrl, time, subtree_com0, subtree_linvel0, cfrc_ext, qfrc_actuator,
                 params=None, registry=None, cinert=None, cvel=None):
     """``REWARD_FUNCTIONS[name](data, params)`` for n states at once, computed by the device reward
@@ -372,12 +380,70 @@ class HsBatch:
         check(lib().hs_step_program(self._h, a.data_ptr(), program.handle, program.params(params), self.stream))
         return self.t["obs"], self.t["reward"], self.t["terminated"], self.t["truncated"]
 
+    # -- termination conditions (hs_set_termination) -----------------------------------------
+    def set_termination(self, condition=None, params=None, grace_steps=1, registry=None):
+        """End episodes on a condition of the state (``hs_set_termination``).  ``condition``: the name of an entry
+        of ``reward_program.TERMINATION_FUNCTIONS`` (``"fallen"``, ``"lost_balance"``, or one registered with
+        ``register_device_termination``), or None to clear it; ``params``: its parameter overrides (unknown key:
+        ValueError); ``grace_steps`` >= 1: the episode ends at the first env step at which the predicate has held
+        for that many consecutive env steps of the episode.  From then on ``step`` (with a device reward) and
+        ``step_program`` are three launches -- the step without auto-reset, one outcome launch (reward program,
+        predicate, grace counter, terminated |= early, ``early_terminated``, the terminal rows), the masked
+        reset when auto-reset is configured -- and the fused launches are refused (``step_tape`` falls back to
+        one ``step`` per tape row).  With ``reward_id`` -1 (a host reward) ``step`` stays the step alone and the
+        caller runs ``apply_termination()`` after writing reward / total_reward.  The grace counter belongs to
+        the episode: every reset clears it, ``set_state`` leaves it alone.  One stream group only."""
+        if condition is None:
+            for h, _, _ in self._groups:
+                check(lib().hs_set_termination(h, None, None, 1))
+            self._termination = None
+            self.__dict__.pop("_early_view", None)
+            return None
+        if len(self._groups) != 1:
+            raise NotImplementedError("set_termination: one stream group only")
+        from .reward_program import termination_from_config
+        rec, params, grace = termination_from_config(
+            {"type": condition, "params": params, "grace_steps": grace_steps}, registry)
+        with _torch().cuda.device(self.device):
+            prog = rec.compile(self.model)
+            check(lib().hs_set_termination(self._h, prog.handle, prog.params(params), grace))
+        self._termination = (prog, params, grace)      # the native batch does not own the predicate: keep it alive
+        self.__dict__.pop("_early_view", None)
+        return prog
+
+    @property
+    def termination(self):
+        """(compiled predicate, parameter overrides, grace_steps) of the condition set, or None."""
+        return self.__dict__.get("_termination")
+
+    def apply_termination(self):
+        """The outcome launch alone on the batch's current state, no reset (``hs_apply_termination``): for a
+        caller that steps with ``reward_id`` -1 and writes the reward itself.  Once per env step: it advances
+        the grace counter."""
+        check(lib().hs_apply_termination(self._h, self.stream))
+        return self.t["terminated"], self.early_terminated
+
+    @property
+    def early_terminated(self):
+        """[N] uint8 device view: 1 for the envs whose episode the condition ended in the last outcome launch
+        (valid until the next step; the buffer is the native batch's)."""
+        v = self.__dict__.get("_early_view")
+        if v is None:
+            if self.termination is None:
+                raise _lib.HsimError("early_terminated: the batch has no termination condition (set_termination)")
+            p = C.c_void_p()
+            check(lib().hs_termination_state(self._h, None, C.byref(p), None, None))
+            v = self._early_view = _torch().as_tensor(_DeviceBytes(p.value, self.n), device=self.device)
+        return v
+
     def step_tape(self, actions, outputs=True):
         """K consecutive ``step`` calls over an action tape [K, N, nu] (float32, on device) in one
         launch (hs_step_tape: a pair's step t + 1 starts once its own step t is committed, so the
         launch does not end every step on its slowest pair).  Bitwise the results of K ``step``
         calls.  outputs=True returns the per-step (obs [K, N, obs_dim], reward [K, N], terminated,
-        truncated [K, N] uint8); the batch's own buffers hold the last step either way.  Open loop:
+        truncated [K, N] uint8); the batch's own buffers hold the last step either way.  With a termination
+        condition set (``set_termination``) the tape is stepped one ``step`` at a time instead: the same
+        results, slower.  Open loop:
         benchmarks, trajectory evaluation -- a policy in the loop steps with ``step`` (or, for the PPO pi
         net, inside the launch: hs_rollout, PPO._rollout_fused).  Synchronous;
         one stream group only."""
@@ -395,6 +461,15 @@ class HsBatch:
                    torch.empty(K, self.n, dtype=torch.uint8, device=self.device),
                    torch.empty(K, self.n, dtype=torch.uint8, device=self.device))
             out = _lib.hs_tape_out(*[x.data_ptr() for x in res])
+        if self.termination is not None:
+            # a termination condition: hs_step_tape refuses (a fused launch is bounded by the shortest possible
+            # episode), so the tape is stepped one ``step`` at a time -- the same results, slower
+            for k in range(K):
+                step = self.step(a[k])
+                if outputs:
+                    for dst, src in zip(res, step):
+                        dst[k].copy_(src)
+            return res if outputs else step
         h = self._groups[0][0]
         check(lib().hs_step_tape(h, a.data_ptr(), K, C.byref(out) if out is not None else None, self.stream))
         if outputs:
@@ -521,6 +596,8 @@ class HsBatch:
         return out
 
     def set_state(self, qpos=None, qvel=None, qacc_warmstart=None, time=None, ctrl=None):
+        """Overwrite the given state fields from fp64 host arrays (broadcast to every env).  The episode number
+        is not part of the state, so a termination condition's grace counter is left alone."""
         def p(x, shape):
             if x is None:
                 return None, None
@@ -658,6 +735,7 @@ class HsBatch:
                 lib().hs_batch_destroy(h)
         self._groups = []
         self._h = None
+        self.__dict__.pop("_early_view", None)       # a view of the native batch's buffer, gone with it
 
     def __del__(self):
         try:

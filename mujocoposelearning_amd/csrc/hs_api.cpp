@@ -61,6 +61,14 @@ struct hs_batch {
   int* kin_envs = nullptr;                   // hs_kinematics_batch: the env-id list on the device (grown on demand)
   int kin_envs_cap = 0;
   uint8_t* prog_done = nullptr;              // hs_step_program: the per-env done bytes, the mask of its reset launch
+  // hs_set_termination: the predicate (not owned), its parameters (copied) and the grace period; the per-env
+  // grace counter, the episode number it belongs to and the early_terminated bytes (allocated once)
+  const hs_reward_program* term_prog = nullptr;
+  double term_params[HS_RP_MAX_PARAMS] = {};
+  int grace_steps = 1;
+  int32_t* grace_count = nullptr;
+  int32_t* grace_episode = nullptr;
+  uint8_t* early = nullptr;
 };
 
 // a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on
@@ -422,6 +430,23 @@ int with_dev_model(const hs_model* m, F&& f) {
   if (!hs::build_dev_model<T>(m->host, *d, err)) return fail(err);
   return f(*d);
 }
+
+// the env step's one launch, as the batch's config has it
+int step_launch(hs_batch* b, const float* actions, void* stream) {
+  int rc = launch(b, hs::MODE_ENV_STEP, actions, nullptr, b->ar_qpos_noise, b->ar_qvel_noise, b->cfg.frame_skip, stream);
+  // a step with the ctrl copy on rewrites every env's data.ctrl (commit), one with it off leaves it stale
+  if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
+  return rc;
+}
+
+// hs_step / hs_step_program on a batch with a termination set, and hs_step_program on any batch: the step
+// without auto-reset, the outcome launch, the masked reset (defined with the reward programs below)
+int step_outcome_reset(hs_batch* b, const float* actions, const hs_reward_program* prog, const double* params,
+                       void* stream);
+const char kNoFusedWithTermination[] =
+    ": the batch has a termination condition set (hs_set_termination), and a fused launch is bounded by the "
+    "shortest possible episode, which a state-dependent end makes unknowable -- step with hs_step / "
+    "hs_step_program, or clear the condition";
 }  // namespace
 
 extern "C" {
@@ -579,6 +604,9 @@ void hs_batch_destroy(hs_batch* b) {
   if (b->redo) (void)hipFree(b->redo);
   if (b->redo_total) (void)hipFree(b->redo_total);
   if (b->prog_done) (void)hipFree(b->prog_done);
+  if (b->grace_count) (void)hipFree(b->grace_count);
+  if (b->grace_episode) (void)hipFree(b->grace_episode);
+  if (b->early) (void)hipFree(b->early);
   if (b->mid) uc_release(b->device, (size_t)b->n * hs::MIDDIM * (b->precision == HS_FP64 ? 8 : 4), b->mid);
   if (b->qsync) uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
   if (b->eval_obs) uc_release(b->device, (size_t)b->n * b->obs_dim * sizeof(float), b->eval_obs);
@@ -655,10 +683,10 @@ int hs_reset(hs_batch* b, const uint8_t* mask, const void* qpos_noise, const voi
 int hs_step(hs_batch* b, const float* actions, void* stream) {
   if (!actions) return fail("hs_step: actions must not be NULL");
   if (!b) return fail("null batch");
-  int rc = launch(b, hs::MODE_ENV_STEP, actions, nullptr, b->ar_qpos_noise, b->ar_qvel_noise, b->cfg.frame_skip, stream);
-  // a step with the ctrl copy on rewrites every env's data.ctrl (commit), one with it off leaves it stale
-  if (rc == 0) b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL);
-  return rc;
+  // a termination condition: step, outcome launch, masked reset.  Without a device reward the reward is the
+  // caller's, and so is the outcome that follows it (hs_apply_termination): the step alone
+  if (b->term_prog && b->cfg.reward_id != HS_REWARD_NONE) return step_outcome_reset(b, actions, nullptr, nullptr, stream);
+  return step_launch(b, actions, stream);
 }
 
 int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_out* out, void* stream) {
@@ -667,6 +695,7 @@ int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_o
   if (n_steps < 1) return fail("hs_step_tape: n_steps must be >= 1");
   if (out && (!out->obs || !out->reward || !out->terminated || !out->truncated))
     return fail("hs_step_tape: pass all four per-step output arrays, or out = NULL");
+  if (b->term_prog) return fail(std::string("hs_step_tape") + kNoFusedWithTermination);
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
   const auto& h = b->model->host;
@@ -759,6 +788,7 @@ namespace {
 int fused_policy_check(const hs_batch* b, const hs_policy* pol, int act, int t_begin, int n_steps, int t_total,
                        const std::string& who, int* hidden_out) {
   const auto& h = b->model->host;
+  if (b->term_prog) return fail(who + kNoFusedWithTermination);
   if (b->precision != HS_FP64 || h.solver == 1)
     return fail(who + ": the fused rollout runs on the fp64 Newton engine");
   if (!b->cfg.autoreset || b->ar_qpos_noise || b->cfg.reward_id == HS_REWARD_NONE)
@@ -1214,15 +1244,21 @@ const hs_reward_program::Dev* rp_resident(hs_reward_program* p, int device) {
   return &p->dev.back();
 }
 
+hs::RpCode rp_code(const hs_reward_program* p, const hs_reward_program::Dev* d, const double* params) {
+  hs::RpCode c{};
+  c.code = d->code;
+  c.consts = d->consts;
+  c.n_instr = (int)(p->code.size() / 5);
+  for (int k = 0; k < p->n_params; k++) c.params[k] = params[k];
+  return c;
+}
+
 template <typename T>
 hs::RpArgs<T> rp_args(const hs_reward_program* p, const hs_reward_program::Dev* d, const double* params, int n) {
   hs::RpArgs<T> a{};
-  a.code = d->code;
-  a.consts = d->consts;
-  a.n_instr = (int)(p->code.size() / 5);
+  a.prog = rp_code(p, d, params);
   a.n_slots = p->info.n_slots;
   a.n = n;
-  for (int k = 0; k < p->n_params; k++) a.params[k] = params[k];
   return a;
 }
 
@@ -1264,6 +1300,68 @@ int rp_check_batch(const char* who, const hs_batch* b, const hs_reward_program* 
       (!b->buf.cfrc_ext || !b->buf.subtree_linvel))
     return fail(w + ": the batch has no cfrc_ext / subtree_linvel buffers");
   return 0;
+}
+
+// The outcome launch on the batch's post-step, pre-reset state (hs_reward_prog.hip): the reward program `p`
+// if there is one, the batch's termination predicate if one is set, the terminal rows and the done bytes.
+// One launch; the caller has checked the batch and ordered the streams.
+int outcome_launch(hs_batch* b, const hs_reward_program* p, const double* params, void* stream) {
+  const hs_reward_program* t = b->term_prog;
+  const hs_reward_program::Dev* dp = p ? rp_resident(const_cast<hs_reward_program*>(p), b->device) : nullptr;
+  const hs_reward_program::Dev* dt = t ? rp_resident(const_cast<hs_reward_program*>(t), b->device) : nullptr;
+  if ((p && !dp) || (t && !dt)) return -1;
+  auto run = [&](auto zero) -> int {
+    using T = decltype(zero);
+    hs::RpArgs<T> a{};
+    if (p) a.prog = rp_code(p, dp, params);
+    if (t) a.pred = rp_code(t, dt, b->term_params);
+    a.n_slots = std::max(p ? p->info.n_slots : 1, t ? t->info.n_slots : 1);
+    a.n = b->n;
+    rp_batch_fields<T>(b, a);
+    a.outcome = 1;
+    a.reward = (T*)b->buf.reward;
+    a.total_reward = (T*)b->buf.total_reward;
+    a.terminated = b->buf.terminated;
+    a.truncated = b->buf.truncated;
+    a.obs = (const T*)b->buf.obs;
+    a.terminal_obs = (T*)b->buf.terminal_obs;
+    a.obs_dim = b->obs_dim;
+    a.step_count = b->buf.step_count;
+    a.term_step_count = b->buf.terminal_step_count;
+    a.term_total_reward = (T*)b->buf.terminal_total_reward;
+    a.done = b->prog_done;
+    if (t) {
+      a.episode = (const int32_t*)b->buf.episode;
+      a.grace_count = b->grace_count;
+      a.grace_episode = b->grace_episode;
+      a.early = b->early;
+      a.grace_steps = b->grace_steps;
+    }
+    return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
+  };
+  return b->precision == HS_FP64 ? run(0.0) : run(0.0f);
+}
+
+int step_outcome_reset(hs_batch* b, const float* actions, const hs_reward_program* p, const double* params,
+                       void* stream) {
+  // the predicate's needs once more, in case the config changed after hs_set_termination: before any launch
+  if (b->term_prog && rp_check_batch("hs_step", b, b->term_prog, b->term_params, true)) return -1;
+  DeviceGuard g(b->device);
+  if ((p && !rp_resident(const_cast<hs_reward_program*>(p), b->device))) return -1;
+  // 1. the env step without auto-reset -- and, for a reward program, without a reward: the program and the
+  //    predicate see the post-step state
+  const hs_env_config saved = b->cfg;
+  if (p) b->cfg.reward_id = HS_REWARD_NONE;
+  b->cfg.autoreset = 0;
+  int rc = step_launch(b, actions, stream);
+  b->cfg = saved;
+  if (rc) return rc;
+  // 2. the program and / or the predicate, and the step's outcome rows
+  rc = outcome_launch(b, p, params, stream);
+  if (rc) return rc;
+  // 3. SB3's auto-reset of the finished envs: the masked reset, with the noise an in-kernel auto-reset draws
+  if (!saved.autoreset) return 0;
+  return launch(b, hs::MODE_RESET, nullptr, b->prog_done, b->ar_qpos_noise, b->ar_qvel_noise, 1, stream);
 }
 
 }  // namespace
@@ -1375,40 +1473,73 @@ int hs_reward_program_batch(hs_batch* b, const hs_reward_program* p, const doubl
 int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* p, const double* params, void* stream) {
   if (!actions) return fail("hs_step_program: actions must not be NULL");
   if (rp_check_batch("hs_step_program", b, p, params, true)) return -1;
+  return step_outcome_reset(b, actions, p, params, stream);
+}
+
+int hs_set_termination(hs_batch* b, const hs_reward_program* pred, const double* params, int grace_steps) {
+  if (!b) return fail("hs_set_termination: null batch");
+  if (!pred) {   // clear: the buffers stay, the next hs_set_termination starts their counters afresh
+    b->term_prog = nullptr;
+    return 0;
+  }
+  if (grace_steps < 1) return fail("hs_set_termination: grace_steps must be >= 1");
+  if (rp_check_batch("hs_set_termination", b, pred, params, true)) return -1;
   DeviceGuard g(b->device);
-  const auto* d = rp_resident(const_cast<hs_reward_program*>(p), b->device);
-  if (!d) return -1;
-  // 1. the env step without a reward and without auto-reset: the program sees the post-step state
-  const hs_env_config saved = b->cfg;
-  b->cfg.reward_id = HS_REWARD_NONE;
-  b->cfg.autoreset = 0;
-  int rc = hs_step(b, actions, stream);
-  b->cfg = saved;
-  if (rc) return rc;
-  // 2. the program, and the step's outcome rows
-  auto run = [&](auto zero) -> int {
-    using T = decltype(zero);
-    hs::RpArgs<T> a = rp_args<T>(p, d, params, b->n);
-    rp_batch_fields<T>(b, a);
-    a.outcome = 1;
-    a.reward = (T*)b->buf.reward;
-    a.total_reward = (T*)b->buf.total_reward;
-    a.terminated = b->buf.terminated;
-    a.truncated = b->buf.truncated;
-    a.obs = (const T*)b->buf.obs;
-    a.terminal_obs = (T*)b->buf.terminal_obs;
-    a.obs_dim = b->obs_dim;
-    a.step_count = b->buf.step_count;
-    a.term_step_count = b->buf.terminal_step_count;
-    a.term_total_reward = (T*)b->buf.terminal_total_reward;
-    a.done = b->prog_done;
-    return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
-  };
-  rc = b->precision == HS_FP64 ? run(0.0) : run(0.0f);
-  if (rc) return rc;
-  // 3. SB3's auto-reset of the finished envs: the masked reset, with the noise an in-kernel auto-reset draws
-  if (!saved.autoreset) return 0;
-  return launch(b, hs::MODE_RESET, nullptr, b->prog_done, b->ar_qpos_noise, b->ar_qvel_noise, 1, stream);
+  if (!rp_resident(const_cast<hs_reward_program*>(pred), b->device)) return -1;
+  const size_t N = (size_t)b->n;
+  if (!b->grace_count &&
+      (!hip_ok(hipMalloc((void**)&b->grace_count, N * sizeof(int32_t)), "hipMalloc(grace_count)") ||
+       !hip_ok(hipMalloc((void**)&b->grace_episode, N * sizeof(int32_t)), "hipMalloc(grace_episode)") ||
+       !hip_ok(hipMalloc((void**)&b->early, N), "hipMalloc(early_terminated)")))
+    return -1;
+  // no count belongs to any episode yet: the tag -1 is no episode number (they start at 0 and count up)
+  if (!hip_ok(hipDeviceSynchronize(), "hs_set_termination") ||
+      !hip_ok(hipMemset(b->grace_count, 0, N * sizeof(int32_t)), "hs_set_termination") ||
+      !hip_ok(hipMemset(b->grace_episode, 0xFF, N * sizeof(int32_t)), "hs_set_termination") ||
+      !hip_ok(hipMemset(b->early, 0, N), "hs_set_termination") ||
+      !hip_ok(hipDeviceSynchronize(), "hs_set_termination"))
+    return -1;
+  for (int k = 0; k < HS_RP_MAX_PARAMS; k++) b->term_params[k] = k < pred->n_params ? params[k] : 0.0;
+  b->grace_steps = grace_steps;
+  b->term_prog = pred;
+  return 0;
+}
+
+int hs_termination_state(const hs_batch* b, int* grace_steps, const uint8_t** early_terminated,
+                         const int32_t** grace_count, const int32_t** grace_episode) {
+  if (!b) return fail("hs_termination_state: null batch");
+  if (grace_steps) *grace_steps = b->term_prog ? b->grace_steps : 0;
+  if (early_terminated) *early_terminated = b->early;
+  if (grace_count) *grace_count = b->grace_count;
+  if (grace_episode) *grace_episode = b->grace_episode;
+  return b->term_prog ? 1 : 0;
+}
+
+int hs_apply_termination(hs_batch* b, void* stream) {
+  if (!b) return fail("hs_apply_termination: null batch");
+  if (!b->term_prog) return fail("hs_apply_termination: the batch has no termination condition (hs_set_termination)");
+  if (rp_check_batch("hs_apply_termination", b, b->term_prog, b->term_params, false)) return -1;
+  DeviceGuard g(b->device);
+  if (order_streams(b, (hipStream_t)stream)) return -1;
+  return outcome_launch(b, nullptr, nullptr, stream);
+}
+
+int hs_termination_eval_host(const hs_reward_program* pred, const double* params, int grace_steps, int n,
+                             const hs_reward_fields* f, const int32_t* episode, int32_t* count, int32_t* episode_tag,
+                             uint8_t* early) {
+  if (!pred || !f) return fail("hs_termination_eval_host: null argument");
+  if (n < 0) return fail("hs_termination_eval_host: negative n");
+  if (grace_steps < 1) return fail("hs_termination_eval_host: grace_steps must be >= 1");
+  if (n == 0) return 0;
+  if (!episode || !count || !episode_tag || !early || (pred->n_params > 0 && !params))
+    return fail("hs_termination_eval_host: null episode, count, episode_tag, early or params");
+  const double* const* fp = reinterpret_cast<const double* const*>(f);
+  for (int k = 0; k < hs::RP_NFIELDS; k++)
+    if ((pred->info.fields & (1u << k)) && !fp[k])
+      return fail(std::string("hs_termination_eval_host: the predicate reads ") + kRpFieldNames[k] + ", which is NULL");
+  hs::rp_termination_eval_host(pred->dims, pred->code.data(), (int)(pred->code.size() / 5), pred->consts.data(), params,
+                               grace_steps, n, fp, episode, count, episode_tag, early);
+  return 0;
 }
 
 int hs_pack_outputs(hs_batch* b, double* out, int ncols, int warnings, void* stream) {

@@ -12,6 +12,7 @@
 //   RP_RESULT a = the slot holding the reward; exactly one, the last instruction
 // Comparisons and the logical ops give 1 or 0; RP_WHERE and the logical ops read "not zero" as true.
 #pragma once
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -197,24 +198,67 @@ inline void rp_eval_host(const RpDims& d, const int32_t* code, int n_instr, cons
   }
 }
 
-#if defined(__HIPCC__)
-// reward_program_kernel's arguments.  field[f] is the base of field f and ld[f] its env stride in
-// values (a NULL field reads as 0: cfrc_ext / subtree_linvel without HS_FULL_STATE).  outcome = 0:
-// out[env] = the program's value.  outcome = 1 (hs_step_program, after a step without reward or
-// auto-reset): the env step's outcome rows, see the kernel.
+// -- termination conditions (include/hsim.h hs_set_termination) ----------------------------------
+// A predicate is a program whose value is read as a truth value: it holds iff the value is non-zero and
+// not NaN (a comparison with a NaN is already 0; a bare NaN value does not terminate either).
 template <typename T>
-struct RpArgs {
+RP_HD inline bool rp_truth(T v) { return v != T(0) && v == v; }
+
+// The grace counter of one env (custom_env.py:169-180 without its reward scaling): the number of consecutive
+// env steps of the CURRENT episode at which the predicate has held.  It is stored with the episode number it
+// belongs to and reads as 0 when that differs from the env's current one, so every kind of reset clears it
+// without the reset kernels knowing.  Returns the new count (saturating); *early = the episode ends now.
+RP_HD inline int32_t rp_grace_update(int32_t stored_count, int32_t stored_episode, int32_t episode, bool holds,
+                                     int32_t grace_steps, bool* early) {
+  const int32_t prev = stored_episode == episode ? stored_count : 0;
+  const int32_t count = holds ? (prev < INT32_MAX ? prev + 1 : prev) : 0;
+  *early = count >= grace_steps;
+  return count;
+}
+
+// The host path: a VALIDATED predicate and the grace update on n states in double.  count / episode_tag
+// [n] are read and updated in place, episode [n] is each env's current episode number; early [n] out.
+inline void rp_termination_eval_host(const RpDims& d, const int32_t* code, int n_instr, const double* consts,
+                                     const double* params, int grace_steps, int n, const double* const* field,
+                                     const int32_t* episode, int32_t* count, int32_t* episode_tag, uint8_t* early) {
+  for (int e = 0; e < n; e++) {
+    const double* one[RP_NFIELDS];
+    for (int f = 0; f < RP_NFIELDS; f++) one[f] = field[f] ? field[f] + (size_t)e * rp_field_len(d, f) : nullptr;
+    double v = 0;
+    rp_eval_host(d, code, n_instr, consts, params, 1, one, &v);
+    bool ends = false;
+    count[e] = rp_grace_update(count[e], episode_tag[e], episode[e], rp_truth(v), grace_steps, &ends);
+    episode_tag[e] = episode[e];
+    early[e] = ends ? 1 : 0;
+  }
+}
+
+#if defined(__HIPCC__)
+// One encoded program as the kernel sees it: code / consts on the device, the parameters by value.
+// n_instr = 0: none.
+struct RpCode {
   const int32_t* code;
   const double* consts;
-  int n_instr, n_slots, n, outcome;
+  int n_instr;
+  double params[RP_MAX_PARAMS];
+};
+
+// reward_program_kernel's arguments.  field[f] is the base of field f and ld[f] its env stride in
+// values (a NULL field reads as 0: cfrc_ext / subtree_linvel without HS_FULL_STATE).  outcome = 0:
+// out[env] = the reward program's value.  outcome = 1 (hs_step_program, hs_step with a termination set,
+// hs_apply_termination; after a step without auto-reset): the env step's outcome rows, see the kernel --
+// `prog` the reward program or none (the step kernel's reward stays), `pred` the termination predicate or none.
+template <typename T>
+struct RpArgs {
+  RpCode prog, pred;
+  int n_slots, n, outcome;          // n_slots: the larger of the two programs'
   const T* field[RP_NFIELDS];
   long long ld[RP_NFIELDS];
-  double params[RP_MAX_PARAMS];
   T* out;
   // outcome mode: the batch's rows
   T* reward;
   T* total_reward;
-  const uint8_t* terminated;
+  uint8_t* terminated;
   const uint8_t* truncated;
   const T* obs;
   T* terminal_obs;
@@ -223,6 +267,12 @@ struct RpArgs {
   int32_t* term_step_count;
   T* term_total_reward;
   uint8_t* done;
+  // with a predicate: the grace counter and its episode tag, the env's episode number, the early byte
+  const int32_t* episode;
+  int32_t* grace_count;
+  int32_t* grace_episode;
+  uint8_t* early;
+  int grace_steps;
 };
 
 template <typename T>

@@ -8,7 +8,9 @@ numpy's global legacy RNG exactly as the reference (custom_env.py:99-117), so
 ``reset(seed=s)`` reproduces the reference's initial state bit-for-bit before the physics step.
 
 Additive env_config keys: ``device`` (GPU index, default 0), ``precision`` ('fp64' default
-for this single-env surface, 'fp32'), ``max_newton``.
+for this single-env surface, 'fp32'), ``max_newton``, ``termination`` (``{"type": "fallen", "params": {...},
+"grace_steps": 1}``: the fall conditions custom_env.py:167-200 holds commented out; ``terminated`` is then true
+on an early end and ``info["early_termination"]`` says which kind it was).
 """
 from __future__ import annotations
 
@@ -155,7 +157,12 @@ class HumanoidEnv(Env):
             max_newton = env_config.get('max_newton', 100)
             # opt-in: cfrc_ext / subtree_linvel computed (reference: zeros) and obs += cfrc_ext[1:]
             full_state = bool(env_config.get('full_state_obs', False))
+            # additive: {"type": "fallen", "params": {...}, "grace_steps": 1} ends the episode on a condition of
+            # the state (custom_env.py:167-200, there commented out; grace_period_length above stays parsed
+            # and unused, as in the reference)
+            termination = env_config.get('termination')
         else:
+            termination = None
             self.model_path = env_config
             self.duration = 15
             self.framerate = 60
@@ -179,6 +186,11 @@ class HumanoidEnv(Env):
         self.init_qpos[3:7] = [1, 0, 0, 0]
         self.init_qvel = np.zeros(self.model.nv)
         self._configure(max_newton)
+        self._termination = None
+        if termination is not None:      # unknown type / parameter: ValueError here
+            from .reward_program import termination_from_config
+            rec, tparams, grace = termination_from_config(termination)
+            self._termination = self._batch.set_termination(rec.name, tparams, grace)
         obs_size = self._batch.obs_dim
         self.observation_space = Box(low=-CLIP_OBSERVATION_VALUE, high=CLIP_OBSERVATION_VALUE, shape=(obs_size,),
                                      dtype=np.float64)
@@ -228,6 +240,8 @@ class HumanoidEnv(Env):
         self.step_count += 1
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(1, -1), device=self._batch.device)
         self._batch.step(a)
+        if self._termination is not None and self._reward_dev is None:
+            self._batch.apply_termination()      # a host reward: the step ran alone, the predicate follows it
         # obs, reward, done flags and the warning counters in one copy; a bad-state reset warns as
         # mj_step's mju_warning does, a lost hand-off raises (batch.report_warnings)
         obs, cols, warn = self._batch.host_outputs(ncols=3, warnings=True)
@@ -258,6 +272,8 @@ class HumanoidEnv(Env):
             'terminated': terminated,
             'total_reward': self.total_reward,
         }
+        if self._termination is not None:     # terminated is then true on an early end too
+            info['early_termination'] = bool(self._batch.early_terminated[0].item())
         if self.render_mode == "rgb_array":   # custom_env.py:227-228
             self.render()
         return state, reward, terminated, truncated, info

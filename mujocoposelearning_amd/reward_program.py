@@ -42,6 +42,10 @@ the built-in callables is not part of the language.
 Limits (include/hsim.h HS_RP_MAX_*): 4096 instructions, 64 LIVE values (the tracer allocates value slots
 by liveness, so a long program is fine as long as few values are alive at once), 256 constants,
 32 parameters.  A program over a limit is refused at trace time with the figure in the message.
+
+Termination conditions are predicates in the same language (``register_device_termination``,
+``TERMINATION_FUNCTIONS``, the built-ins ``"fallen"`` and ``"lost_balance"``): see the section at the end of
+this module and ``env_config["termination"]``.
 """
 from __future__ import annotations
 
@@ -279,11 +283,11 @@ class _Params(dict):
         raise ValueError(f"unknown reward parameter {key!r} (the program's parameters: {sorted(self)})")
 
 
-def _merge_params(defaults, overrides, name):
+def _merge_params(defaults, overrides, name, kind="reward"):
     vals = dict(defaults)
     for k, v in (overrides or {}).items():
         if k not in defaults:
-            raise ValueError(f"unknown parameter {k!r} for reward {name!r} (its parameters: {sorted(defaults)})")
+            raise ValueError(f"unknown parameter {k!r} for {kind} {name!r} (its parameters: {sorted(defaults)})")
         vals[k] = v
     return vals
 
@@ -468,6 +472,8 @@ class DeviceReward:
     """The record of a device-capable reward: its function, parameter defaults, numeric twin, and the
     traces / native programs made of it per model."""
 
+    kind = "reward"
+
     def __init__(self, name, fn, defaults):
         self.name = name
         self.fn = fn
@@ -477,18 +483,22 @@ class DeviceReward:
         self._compiled = {}
 
         def twin(env_data, params=None):
-            vals = _merge_params(self.defaults, params, name)
+            vals = _merge_params(self.defaults, params, name, self.kind)
             p = _Params({k: Scalar(_NUMERIC, _F(v)) for k, v in vals.items()})
             with np.errstate(all="ignore"):
-                return float(_NUMERIC.lift(fn(_numeric_view(env_data), p)).v)
+                return self._twin_value(float(_NUMERIC.lift(fn(_numeric_view(env_data), p)).v))
         twin.__name__ = getattr(fn, "__name__", name)
         twin.__doc__ = fn.__doc__
         twin.device_reward = self
         self.twin = twin
 
+    @staticmethod
+    def _twin_value(v):
+        return v
+
     def params(self, overrides=None):
         """The parameter values in slot order: the defaults overlaid with ``overrides`` (unknown key: ValueError)."""
-        vals = _merge_params(self.defaults, overrides, self.name)
+        vals = _merge_params(self.defaults, overrides, self.name, self.kind)
         return np.asarray([float(vals[k]) for k in self.param_keys], dtype=np.float64)
 
     def trace(self, dims):
@@ -536,6 +546,14 @@ class CompiledProgram:
         """The program interpreted on the CPU (``hs_reward_program_eval_host``): ``fields`` maps field names to
         float64 arrays [n, ...] (``subtree_com``: [n, 3] or [n, nbody, 3], row 0 is used); returns [n] float64."""
         from . import _lib
+        f, keep, n = self._host_fields(fields)
+        out = np.zeros(n, dtype=np.float64)
+        _lib.check(_lib.lib().hs_reward_program_eval_host(self.handle, self.params(params), n, C.byref(f),
+                                                         out.ctypes.data))
+        return out
+
+    def _host_fields(self, fields):
+        from . import _lib
         keep, n = {}, None
         for name in self.fields:
             a = np.asarray(fields[name], dtype=np.float64)
@@ -546,10 +564,26 @@ class CompiledProgram:
         if n is None:
             n = len(next(iter(fields.values())))
         f = _lib.hs_reward_fields(**{_lib.REWARD_FIELD_MEMBER[k]: v.ctypes.data for k, v in keep.items()})
-        out = np.zeros(n, dtype=np.float64)
-        _lib.check(_lib.lib().hs_reward_program_eval_host(self.handle, self.params(params), n, C.byref(f),
-                                                         out.ctypes.data))
-        return out
+        return f, keep, n
+
+    def termination_eval_host(self, fields, episode, count, episode_tag, params=None, grace_steps=1):
+        """The program as a termination predicate on the CPU (``hs_termination_eval_host``): the predicate on n
+        states (``fields`` as for ``eval_host``) and one grace-counter update per state.  ``episode`` [n] int32 are
+        the envs' current episode numbers; ``count`` and ``episode_tag`` [n] int32 (contiguous) are read and
+        UPDATED IN PLACE.  Returns the [n] bool array of the envs whose episode ends."""
+        from . import _lib
+        f, keep, n = self._host_fields(fields)
+        episode = np.ascontiguousarray(episode, dtype=np.int32)
+        for a in (count, episode_tag):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous and a.shape == (n,)):
+                raise ValueError(f"count / episode_tag: contiguous int32 arrays of shape ({n},)")
+        if episode.shape != (n,):
+            raise ValueError(f"episode: shape ({n},)")
+        early = np.zeros(n, dtype=np.uint8)
+        _lib.check(_lib.lib().hs_termination_eval_host(self.handle, self.params(params), int(grace_steps), n,
+                                                      C.byref(f), episode.ctypes.data, count.ctypes.data,
+                                                      episode_tag.ctypes.data, early.ctypes.data))
+        return early != 0
 
     def close(self):
         h, self.handle = self.handle, None
@@ -587,6 +621,82 @@ def device_reward_program(name, registry=None):
     if name not in reg:
         raise ValueError(f"Unknown reward type: {name}")
     return _BY_TWIN.get(reg[name])
+
+
+# ------------------------------------------------------------------ termination conditions
+# The fall conditions the reference holds commented out (custom_env.py:167-200): a predicate written in this
+# language, evaluated on the device after every env step (hs_set_termination); when it has held for
+# ``grace_steps`` consecutive env steps of an episode, the step returns terminated = True and the env resets.
+TERMINATION_FUNCTIONS = {}
+
+
+class DeviceTermination(DeviceReward):
+    """The record of a termination condition: a ``DeviceReward`` whose value is read as a truth value --
+    terminated iff the result is non-zero and not NaN (a comparison with a NaN is false, as in Python)."""
+
+    kind = "termination"
+
+    @staticmethod
+    def _twin_value(v):
+        return bool(v != 0.0 and v == v)
+
+
+def register_device_termination(name, fn=None, defaults=None, registry=None):
+    """Register ``fn(d, p)`` as the termination condition ``name``, the counterpart of ``register_device_reward``:
+    the same ``env_data`` view ``d`` and parameter dict ``p``, the same tracer and limits.  Its numeric twin
+    ``(env_data, params=None) -> bool`` goes into ``TERMINATION_FUNCTIONS`` (or ``registry``).  Usable as a
+    decorator.  Returns ``fn``."""
+    if fn is None:
+        return lambda f: register_device_termination(name, f, defaults, registry)
+    rec = DeviceTermination(name, fn, defaults)
+    reg = TERMINATION_FUNCTIONS if registry is None else registry
+    reg[name] = rec.twin
+    _BY_TWIN[rec.twin] = rec
+    return fn
+
+
+def device_termination(name, registry=None):
+    """The ``DeviceTermination`` record of ``TERMINATION_FUNCTIONS[name]``; an unknown type raises ValueError like
+    an unknown reward type."""
+    reg = TERMINATION_FUNCTIONS if registry is None else registry
+    rec = _BY_TWIN.get(reg[name]) if name in reg else None
+    if rec is None:
+        raise ValueError(f"Unknown termination type: {name}")
+    return rec
+
+
+def termination_from_config(termination, registry=None):
+    """``env_config["termination"]`` -- ``{"type": name, "params": {...}, "grace_steps": k}`` or None -- checked:
+    returns (record, parameter overrides, grace_steps) or None.  Unknown type, unknown parameter key or a
+    grace period that is not an integer >= 1: ValueError."""
+    if termination is None:
+        return None
+    if not isinstance(termination, dict) or "type" not in termination:
+        raise ValueError('termination: expected {"type": name, "params": {...}, "grace_steps": k} or None')
+    unknown = set(termination) - {"type", "params", "grace_steps"}
+    if unknown:
+        raise ValueError(f"termination: unknown key(s) {sorted(unknown)}")
+    rec = device_termination(termination["type"], registry)
+    params = termination.get("params") or None
+    rec.params(params)
+    g = termination.get("grace_steps", 1)
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or g < 1:
+        raise ValueError(f"termination: grace_steps must be an integer >= 1, got {g!r}")
+    return rec, params, int(g)
+
+
+@register_device_termination("fallen", defaults={"min_height": 0.8})
+def fallen(d, p):
+    """custom_env.py:169 (and reward_functions.py's own ``height < 0.8``): the torso is below ``min_height``."""
+    return d.qpos[2] < p["min_height"]
+
+
+@register_device_termination("lost_balance", defaults={"min_height": 0.8, "max_roll_pitch": np.pi / 4})
+def lost_balance(d, p):
+    """custom_env.py:183-200: fallen, or rolled / pitched beyond ``max_roll_pitch`` (45 degrees).  The pitch is
+    the unclamped ``arcsin`` of ``quaternion_to_euler``: a NaN pitch compares false and does not terminate."""
+    roll, pitch, _ = quaternion_to_euler(d.qpos[3:7])
+    return (d.qpos[2] < p["min_height"]) | (abs(roll) > p["max_roll_pitch"]) | (abs(pitch) > p["max_roll_pitch"])
 
 
 # ------------------------------------------------------------------ the built-in rewards, restated

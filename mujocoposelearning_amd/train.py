@@ -35,8 +35,9 @@ def shard_envs(n_envs: int, world_size: int, rank: int):
 
 
 def env_config_from_kwargs(env_kwargs: dict, xml_path: str = DEFAULT_XML) -> dict:
-    """train_sb3.py:183-200 (duration fixed at 10.0, reward default 'walk', frame_skip default 3)."""
-    return {
+    """train_sb3.py:183-200 (duration fixed at 10.0, reward default 'walk', frame_skip default 3).
+    ``env_kwargs["termination"]`` (hsim option, absent by default) is passed through."""
+    cfg = {
         "model_path": str(xml_path),
         "render_mode": None,
         "framerate": env_kwargs.get("framerate", 60),
@@ -44,6 +45,9 @@ def env_config_from_kwargs(env_kwargs: dict, xml_path: str = DEFAULT_XML) -> dic
         "reward_config": {"type": env_kwargs.get("reward_function", "walk")},
         "frame_skip": env_kwargs.get("frame_skip", 3),
     }
+    if "termination" in env_kwargs:
+        cfg["termination"] = env_kwargs["termination"]
+    return cfg
 
 
 def _resolve_activation(ppo_kwargs: dict) -> dict:

@@ -101,6 +101,17 @@ class HumanoidVecEnv(_Base):
                              reward_id=rid if rid is not None else -1, autoreset=1 if on_device else 0,
                              max_newton=max_newton, init_height=1.282, noise_scale=0.01,
                              kneel_params=params if rid == 1 and params else None)
+        # env_config["termination"] = {"type": "fallen", "params": {...}, "grace_steps": 1}: the episode also ends
+        # when that predicate has held for grace_steps env steps (custom_env.py:167-200, there commented out),
+        # evaluated on the device after every step.  Absent or None: nothing changes.  An unknown type or
+        # parameter raises here.
+        self._termination = None
+        if cfg.get("termination") is not None:
+            from .reward_program import termination_from_config
+            rec, tparams, grace = termination_from_config(cfg["termination"])
+            if len(self.batch._groups) != 1:
+                raise NotImplementedError("a termination condition steps one stream group (groups=1)")
+            self._termination = self.batch.set_termination(rec.name, tparams, grace)
         obs_space = Box(low=-np.inf, high=np.inf, shape=(self.batch.obs_dim,), dtype=np.float64)
         act_space = Box(low=-1, high=1, shape=(self.model.nu,), dtype=np.float32)
         super().__init__(n_envs, obs_space, act_space)
@@ -136,9 +147,11 @@ class HumanoidVecEnv(_Base):
     def rollout_handle(self):
         """The hs_batch handle a fused PPO rollout (hs_rollout) may step, or None: the fp64 Newton
         engine with the device reward and on-device reset noise (graph_safe), one stream group and
-        auto-reset on."""
+        auto-reset on.  None with a termination condition: a fused launch is bounded by the shortest possible
+        episode, which a state-dependent end makes unknowable, so the trainer takes its per-step path."""
         b = self.batch
-        if (not self.graph_safe or self._program is not None or b.precision != "fp64" or not b.cfg.autoreset
+        if (not self.graph_safe or self._program is not None or self._termination is not None
+                or b.precision != "fp64" or not b.cfg.autoreset
                 or len(b._groups) != 1
                 or int(self.model.field("opt_solver")[0]) != 0):
             return None
@@ -158,8 +171,8 @@ class HumanoidVecEnv(_Base):
             return self.batch.reset()
         qn, vn = self._draw_noise(range(self.num_envs))
         obs = self.batch.reset(qpos_noise=qn, qvel_noise=vn)
-        if self._host_reward is None and self._program is None:   # device auto-reset reads the pre-drawn next noise
-            self._bind_next_noise()
+        if self._host_reward is None and self._program is None and self._termination is None:
+            self._bind_next_noise()               # device auto-reset reads the pre-drawn next noise
         return obs
 
     def step_tensors(self, actions):
@@ -168,24 +181,30 @@ class HumanoidVecEnv(_Base):
         call; ``self.batch.terminal_obs`` holds pre-reset obs of envs that just finished."""
         if self._host_reward is not None:
             return self._step_host_reward(actions)
-        if self._program is not None:
+        if self._program is not None or (self._termination is not None and self._streams is not None):
             return self._step_program(actions)
-        out = self.batch.step(actions)
+        out = self.batch.step(actions)          # (with a termination condition: step, outcome, masked reset)
         if self._streams is not None:     # host noise streams: refresh the envs that auto-reset (syncs)
             self._refresh_noise(((out[2] != 0) | (out[3] != 0)).cpu().numpy())
         return out
 
     def _step_program(self, actions):
-        """The env step with a program reward.  On-device reset noise: hs_step_program's three launches, no
-        host sync.  SB3-seeded host noise streams: the step and the program with auto-reset off, then the
-        finished envs are read back and reset with noise drawn from their streams, as on the host path."""
+        """The env step with a program reward, or with a termination condition under host noise streams.
+        On-device reset noise: hs_step_program's three launches, no host sync.  SB3-seeded host noise streams:
+        the step and the outcome launch with auto-reset off, then the finished envs are read back and reset
+        with noise drawn from their streams, as on the host path."""
         b = self.batch
-        if self._streams is None:
+
+        def step():
+            if self._program is None:
+                return b.step(actions)
             return b.step_program(actions, self._program, self._program_params)
+        if self._streams is None:
+            return step()
         import torch
         b.configure(autoreset=0)
         try:
-            out = b.step_program(actions, self._program, self._program_params)
+            out = step()
         finally:
             b.configure(autoreset=1)
         done = (out[2] != 0) | (out[3] != 0)
@@ -201,9 +220,10 @@ class HumanoidVecEnv(_Base):
         if it reads ctrl; a host callable needs both."""
         if self._host_reward is not None:
             return True, True
-        if self._program is not None:
-            return "subtree_com" in self._program.fields, "ctrl" in self._program.fields
-        return False, False
+        fields = set(self._program.fields if self._program is not None else ())
+        if self._termination is not None:         # and what the termination predicate reads
+            fields |= set(self._termination.fields)
+        return "subtree_com" in fields, "ctrl" in fields
 
     def _step_host_reward(self, actions):
         """custom_env.py:201-211 with a host reward callable: step (no auto-reset), evaluate
@@ -220,6 +240,8 @@ class HumanoidVecEnv(_Base):
                 r[i] = float(self._host_reward(views.env(i), self._host_params[i] if self._host_params else None))
         rew.copy_(torch.as_tensor(r, device=rew.device, dtype=rew.dtype))
         b.total_reward.add_(rew)
+        if self._termination is not None:   # the predicate on the same pre-reset state: terminated |= early
+            b.apply_termination()
         done = (term != 0) | (trunc != 0)
         if bool(done.any()):
             b.terminal_obs[done] = obs[done]

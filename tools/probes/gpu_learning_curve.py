@@ -1,7 +1,9 @@
 """Learning-curve sanity of the on-device PPO (SB3 is not importable, so the trainer
 is judged by the stand reward rising).  bench.py's train config: 4096 envs, n_steps 32,
 batch 32768, 4 epochs, lr 3e-4, MLP[256,256] ReLU (batch and epochs overridable).
-python tools/probes/gpu_learning_curve.py [iters] [stand|kneeling] [fp32|fp64] [seed] [batch] [epochs] [stagger] [lr] [target_kl]
+python tools/probes/gpu_learning_curve.py [iters] [stand|kneeling] [fp32|fp64] [seed] [batch] [epochs] [stagger] [lr] [target_kl] [termination]
+termination: a TERMINATION_FUNCTIONS name ("fallen", "lost_balance"; default none) with grace_steps 1: episodes then end
+at the fall, and the rollouts are collected on the graph-captured per-step path instead of the fused launches.
 target_kl > 0: SB3's KL early stop; every printed row then carries that iteration's approx_kl, clip_fraction
 and the epochs entered before the stop (n_updates grows by one per epoch entered).
 stagger = 1: spread the envs' episode clocks over the episode after the first reset (env i starts
@@ -23,9 +25,12 @@ from mujocoposelearning_amd.vec_env import HumanoidVecEnv  # noqa: E402
 XML = os.path.join(ROOT, "mujocoposelearning_amd", "assets", "humanoid.xml")
 
 
-def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epochs=4, stagger=0, lr=3e-4, target_kl=0.0):
-    env = HumanoidVecEnv({"model_path": XML, "duration": 10.0, "reward_config": {"type": reward}, "frame_skip": 3},
-                         n_envs=4096, model=HsModel(XML), seed=seed, precision=precision)
+def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epochs=4, stagger=0, lr=3e-4, target_kl=0.0,
+         termination=None):
+    cfg = {"model_path": XML, "duration": 10.0, "reward_config": {"type": reward}, "frame_skip": 3}
+    if termination:
+        cfg["termination"] = {"type": termination, "grace_steps": 1}
+    env = HumanoidVecEnv(cfg, n_envs=4096, model=HsModel(XML), seed=seed, precision=precision)
     ppo = PPO(env, n_steps=32, batch_size=batch, n_epochs=epochs, learning_rate=lr, seed=seed,
               target_kl=target_kl if target_kl > 0 else None,
               policy_kwargs={"activation_fn": "ReLU", "net_arch": {"pi": [256, 256], "vf": [256, 256]}})
@@ -62,4 +67,5 @@ if __name__ == "__main__":
          sys.argv[3] if len(sys.argv) > 3 else "fp32", int(sys.argv[4]) if len(sys.argv) > 4 else 0,
          int(sys.argv[5]) if len(sys.argv) > 5 else 32768, int(sys.argv[6]) if len(sys.argv) > 6 else 4,
          int(sys.argv[7]) if len(sys.argv) > 7 else 0, float(sys.argv[8]) if len(sys.argv) > 8 else 3e-4,
-         float(sys.argv[9]) if len(sys.argv) > 9 else 0.0)
+         float(sys.argv[9]) if len(sys.argv) > 9 else 0.0,
+         sys.argv[10] if len(sys.argv) > 10 and sys.argv[10] != "none" else None)
