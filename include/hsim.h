@@ -510,7 +510,8 @@ int hs_reward(hs_batch* b, int reward_id, const double* kneel_params, void* out,
  * int32 each, over numbered value slots, with n_consts float64 constants and n_params float64 parameter slots
  * that every call supplies (reward_config["params"] over the function's defaults, custom_env.py:263-271).  The
  * opcode table, the operand meaning and one op's arithmetic are csrc/hs_reward_prog.h; every op is one
- * correctly rounded operation or libm call of the batch precision, never contracted, comparisons with a NaN
+ * operation or libm call of the batch precision, never contracted (+ - * correctly rounded, / and sqrt in
+ * double too; the device's float / and sqrt are the fp32 engine's, <= 2.5 ulp), comparisons with a NaN
  * are false, and a select evaluates both arms.  The limits (a program is bounded by its LIVE values, the
  * slots, not by its length): */
 #define HS_RP_MAX_INSTR 4096

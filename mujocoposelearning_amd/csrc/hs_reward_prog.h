@@ -79,8 +79,25 @@ RP_HD inline int rp_arity(int op) {
   return 0;
 }
 
-// One op's arithmetic: each a single correctly rounded operation (or one libm call) of T, never
-// contracted, so a program rounds exactly as the same expression written out in reward_formula.
+// tanh of the host interpreter goes through long double where that is wider: the C library's double tanh
+// is 1.23 ulp off near |x| = 1e-3 (its documented bound is 2 ulp), and the host interpreter is the device
+// code's reference, held to 1 ulp of the exact value for every libm op (tests/test_program_ops.py).  The
+// device's tanh is its own libm's (tests/test_gpu_program_ops.py measures it).
+template <typename T>
+RP_HD inline T rp_tanh(T a) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (sizeof(T) == sizeof(double) && sizeof(long double) > sizeof(double))
+    return (T)tanhl((long double)a);
+#endif
+  return tanh(a);
+}
+
+// One op's arithmetic: each a single operation (or one libm call) of T, never contracted, so a program
+// rounds exactly as the same expression written out in reward_formula.  + - * are correctly rounded in
+// both dtypes, / and sqrt in double; the DEVICE's float / and sqrt are not: the kernel is built with the
+// fp32 engine's flags (Makefile KFLAGS, <= 2.5 ulp; measured 1.45 and 0.80 ulp), which is what makes a
+// restated built-in equal reward_formula bitwise.  The device's libm is within 1.1 ulp in double and 2.3
+// ulp in float (profiles/reward_programs.md, "Op conformance"; tests/test_gpu_program_ops.py).
 // A comparison with a NaN is false (RP_NE: true); RP_WHERE selects, both arms are always evaluated.
 template <typename T>
 RP_HD inline T rp_op(int op, T a, T b, T c) {
@@ -108,7 +125,7 @@ RP_HD inline T rp_op(int op, T a, T b, T c) {
     case RP_LOG: return log(a);
     case RP_SIN: return sin(a);
     case RP_COS: return cos(a);
-    case RP_TANH: return tanh(a);
+    case RP_TANH: return rp_tanh(a);
     case RP_ASIN: return asin(a);
     case RP_ACOS: return acos(a);
     case RP_NOT: return a != T(0) ? T(0) : T(1);
