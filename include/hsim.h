@@ -310,7 +310,8 @@ typedef struct hs_rollout_bufs {
  * next obs row, episode_start) -- on each env's wave, each env pair's step t + 1 starting when its
  * own step t is done.  Replaces the per-step loop of SB3 collect_rollouts (train_sb3.py:229 ->
  * on_policy_algorithm.py) for envs stepped by this engine; values are evaluated after the rollout.
- * n_steps <= hs_rollout_max_steps(b) (the shortest episode, at most 511 steps).  Returns 0, or 1 when an env overflowed
+ * n_steps <= hs_rollout_max_steps(b) (the shortest episode, at most 511 steps; 511 with a fused-capable termination
+ * condition, hs_set_termination_builtin).  Returns 0, or 1 when an env overflowed
  * the resident contact tier: the env state, ep_acc, episode_start and actions_clipped are restored
  * to the call's start, and the caller collects these steps step by step (hs_step).  Synchronizes. */
 int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int t_begin, int n_steps, int t_total,
@@ -603,9 +604,34 @@ int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* 
  * on the batch's current state with no reset (call it once per env step: it advances the grace counter).
  * One stream group.
  *
- * THE LIMIT: the fused launches -- hs_step_tape, hs_rollout*, hs_evaluate* -- refuse a batch with a condition
- * set (-1, the reason in hs_last_error).  The host bounds such a launch so that each env finishes at most one
- * episode in it, from the shortest possible episode; a state-dependent end makes that bound unknowable.
+ * THE LIMIT: the fused launches -- hs_step_tape, hs_rollout*, hs_evaluate* -- refuse a batch whose condition was
+ * set with hs_set_termination (-1, the reason in hs_last_error): a user-registered predicate needs the
+ * interpreter, which the step kernel has no room for.  The host bounds an ordinary fused launch so that each env
+ * finishes at most one episode in it, from the shortest possible episode; a state-dependent end makes that bound
+ * unknowable.
+ *
+ * hs_set_termination_builtin lifts the limit for the two built-in conditions (HS_TERM_FALLEN: qpos[2] <
+ * min_height; HS_TERM_LOST_BALANCE: that, or |roll| or |pitch| > max_roll_pitch with quaternion_to_euler's
+ * unclamped pitch).  It does everything hs_set_termination(b, predicate, params, grace_steps) does -- the
+ * predicate stays set, and hs_step keeps running the three launches above with the interpreter, unchanged: that
+ * path is the yardstick and the fallback of an aborted fused launch -- and also records the built-in, which makes
+ * the condition FUSED-CAPABLE.  Before recording it checks that program and built-in are the same predicate: the
+ * program may read qpos only, and it is evaluated on the host on a fixed table of probe rows (heights either
+ * side of min_height, quaternions tilted either side of max_roll_pitch in roll and in pitch, one quaternion with
+ * |2 (w y - z x)| > 1 whose NaN pitch must not terminate); any truth value that differs from the built-in's
+ * refuses the call (-1), before any launch.  hs_set_termination (new or cleared) drops the mark.
+ * With a fused-capable condition hs_step_tape, hs_rollout_act / _norm and hs_evaluate / _norm launch instead
+ * of refusing (their other preconditions stay: the fp64 Newton engine, auto-reset with the on-device reset noise,
+ * a device reward, the chunk-queue schedule): kernel instances of their own evaluate the built-in after every env
+ * step, bitwise the per-step path's results.  An env may then end several episodes in one launch, so the launch
+ * cap is 511 steps alone (hs_rollout_max_steps returns it), and THE TERMINAL ROWS' CONTRACT is: terminal_obs,
+ * terminal_step_count and terminal_total_reward are written by the launch's last step only, i.e. after a fused
+ * launch they are defined for the envs that were done on its last step (what every reader uses: a per-step
+ * output, a rollout's terminal obs rows and an evaluation's result slots have an address of their own per step
+ * or per episode).  The early_terminated byte and the grace counter / episode tag are committed by the last
+ * step with the state; an aborted launch (return 1) restores them with it.
+ * hs_termination_builtin_eval_host: the built-in predicate alone on n host rows (qpos + i * ld, ld >= 7 doubles;
+ * out [n] bytes), needing no batch and no GPU.
  *
  * hs_termination_state: returns 1 if a condition is set, else 0; *grace_steps (0 when none) and the device
  * pointers of the [N] early_terminated bytes, grace counters and their episode tags (NULL before the first
@@ -614,6 +640,12 @@ int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* 
  * hs_reward_program_eval_host (needs no GPU): episode [n] the envs' current episode numbers, count /
  * episode_tag [n] read and updated in place, early [n] written. */
 int hs_set_termination(hs_batch* b, const hs_reward_program* predicate, const double* params, int grace_steps);
+#define HS_TERM_FALLEN 1
+#define HS_TERM_LOST_BALANCE 2
+int hs_set_termination_builtin(hs_batch* b, const hs_reward_program* predicate, const double* params, int grace_steps,
+                               int kind, double min_height, double max_roll_pitch);
+int hs_termination_builtin_eval_host(int kind, double min_height, double max_roll_pitch, int n, const double* qpos,
+                                     int ld, uint8_t* out);
 int hs_apply_termination(hs_batch* b, void* stream);
 int hs_termination_state(const hs_batch* b, int* grace_steps, const uint8_t** early_terminated,
                          const int32_t** grace_count, const int32_t** grace_episode);

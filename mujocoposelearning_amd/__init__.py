@@ -43,7 +43,8 @@ def __getattr__(name):
         return getattr(render, name)
     if name in ("register_device_reward", "device_reward_program", "DeviceReward", "TracedProgram", "CompiledProgram",
                 "stand_program", "kneeling_program", "walk_program", "register_device_termination",
-                "device_termination", "DeviceTermination", "TERMINATION_FUNCTIONS"):
+                "device_termination", "DeviceTermination", "TERMINATION_FUNCTIONS",
+                "termination_fused_from_config", "builtin_termination_eval_host"):
         from . import reward_program
         return getattr(reward_program, name)
     if name == "HsBatch":

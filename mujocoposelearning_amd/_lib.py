@@ -172,6 +172,8 @@ def lib():
         "hs_reward_program_batch": (i, [vp, vp, vp, vp, vp]),
         "hs_step_program": (i, [vp, vp, vp, vp, vp]),
         "hs_set_termination": (i, [vp, vp, vp, i]),
+        "hs_set_termination_builtin": (i, [vp, vp, vp, i, i, C.c_double, C.c_double]),
+        "hs_termination_builtin_eval_host": (i, [i, C.c_double, C.c_double, i, vp, i, vp]),
         "hs_apply_termination": (i, [vp, vp]),
         "hs_termination_state": (i, [vp, vp, vp, vp, vp]),
         "hs_termination_eval_host": (i, [vp, vp, i, i, vp, vp, vp, vp, vp]),
@@ -234,7 +236,8 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_return_moments", "hs_reward_scale", "hs_kinematics_batch", "hs_render_frames",
             "hs_reward_program_create", "hs_reward_program_destroy", "hs_reward_program_info",
             "hs_reward_program_eval_host", "hs_reward_program_eval", "hs_reward_program_batch", "hs_step_program",
-            "hs_set_termination", "hs_apply_termination", "hs_termination_state", "hs_termination_eval_host")
+            "hs_set_termination", "hs_apply_termination", "hs_termination_state", "hs_termination_eval_host",
+            "hs_set_termination_builtin", "hs_termination_builtin_eval_host")
 
 
 class HsimError(RuntimeError):

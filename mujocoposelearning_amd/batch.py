@@ -381,7 +381,7 @@ class HsBatch:
         return self.t["obs"], self.t["reward"], self.t["terminated"], self.t["truncated"]
 
     # -- termination conditions (hs_set_termination) -----------------------------------------
-    def set_termination(self, condition=None, params=None, grace_steps=1, registry=None):
+    def set_termination(self, condition=None, params=None, grace_steps=1, registry=None, fused=False):
         """End episodes on a condition of the state (``hs_set_termination``).  ``condition``: the name of an entry
         of ``reward_program.TERMINATION_FUNCTIONS`` (``"fallen"``, ``"lost_balance"``, or one registered with
         ``register_device_termination``), or None to clear it; ``params``: its parameter overrides (unknown key:
@@ -392,22 +392,39 @@ class HsBatch:
         reset when auto-reset is configured -- and the fused launches are refused (``step_tape`` falls back to
         one ``step`` per tape row).  With ``reward_id`` -1 (a host reward) ``step`` stays the step alone and the
         caller runs ``apply_termination()`` after writing reward / total_reward.  The grace counter belongs to
-        the episode: every reset clears it, ``set_state`` leaves it alone.  One stream group only."""
+        the episode: every reset clears it, ``set_state`` leaves it alone.  One stream group only.
+
+        ``fused=True`` (the built-ins ``"fallen"`` / ``"lost_balance"`` only; anything else: ValueError) sets the
+        condition with ``hs_set_termination_builtin``: ``step`` stays the three launches above, and the fused
+        launches -- ``step_tape``, ``hs_rollout*``, ``hs_evaluate*`` -- run kernel instances that evaluate the
+        built-in themselves, bitwise the per-step results.  An env may end several episodes in such a launch, so
+        the terminal rows (``terminal_obs``, ``terminal_step_count``, ``terminal_total_reward``) are then written
+        by the launch's last step only: defined for the envs that were done on that step."""
         if condition is None:
             for h, _, _ in self._groups:
                 check(lib().hs_set_termination(h, None, None, 1))
             self._termination = None
+            self._termination_fused = False
             self.__dict__.pop("_early_view", None)
             return None
         if len(self._groups) != 1:
             raise NotImplementedError("set_termination: one stream group only")
-        from .reward_program import termination_from_config
-        rec, params, grace = termination_from_config(
-            {"type": condition, "params": params, "grace_steps": grace_steps}, registry)
+        from .reward_program import (builtin_termination_kind, termination_from_config,
+                                     termination_fused_from_config)
+        config = {"type": condition, "params": params, "grace_steps": grace_steps, "fused": fused}
+        rec, params, grace = termination_from_config(config, registry)
+        fused = termination_fused_from_config(config, registry)
         with _torch().cuda.device(self.device):
             prog = rec.compile(self.model)
-            check(lib().hs_set_termination(self._h, prog.handle, prog.params(params), grace))
+            if fused:
+                vals = dict(zip(rec.param_keys, rec.params(params)))
+                check(lib().hs_set_termination_builtin(
+                    self._h, prog.handle, prog.params(params), grace, builtin_termination_kind(rec),
+                    vals["min_height"], vals.get("max_roll_pitch", 0.0)))
+            else:
+                check(lib().hs_set_termination(self._h, prog.handle, prog.params(params), grace))
         self._termination = (prog, params, grace)      # the native batch does not own the predicate: keep it alive
+        self._termination_fused = fused
         self.__dict__.pop("_early_view", None)
         return prog
 
@@ -415,6 +432,11 @@ class HsBatch:
     def termination(self):
         """(compiled predicate, parameter overrides, grace_steps) of the condition set, or None."""
         return self.__dict__.get("_termination")
+
+    @property
+    def termination_fused(self):
+        """True when the condition set is fused-capable (``set_termination(..., fused=True)``)."""
+        return bool(self.__dict__.get("_termination_fused", False))
 
     def apply_termination(self):
         """The outcome launch alone on the batch's current state, no reset (``hs_apply_termination``): for a
@@ -436,14 +458,26 @@ class HsBatch:
             v = self._early_view = _torch().as_tensor(_DeviceBytes(p.value, self.n), device=self.device)
         return v
 
+    def grace_counts(self):
+        """[N] int32 device tensor (a copy): each env's effective grace count -- the consecutive env steps of
+        its current episode at which the condition has held; a stored count that belongs to another episode
+        reads as 0 (``hs_termination_state``)."""
+        if self.termination is None:
+            raise _lib.HsimError("grace_counts: the batch has no termination condition (set_termination)")
+        torch = _torch()
+        cnt, tag = C.c_void_p(), C.c_void_p()
+        check(lib().hs_termination_state(self._h, None, None, C.byref(cnt), C.byref(tag)))
+        view = lambda p: torch.as_tensor(_DeviceBytes(p.value, 4 * self.n), device=self.device).view(torch.int32)
+        return torch.where(view(tag) == self.episode.to(torch.int32), view(cnt), torch.zeros_like(view(cnt)))
+
     def step_tape(self, actions, outputs=True):
         """K consecutive ``step`` calls over an action tape [K, N, nu] (float32, on device) in one
         launch (hs_step_tape: a pair's step t + 1 starts once its own step t is committed, so the
         launch does not end every step on its slowest pair).  Bitwise the results of K ``step``
         calls.  outputs=True returns the per-step (obs [K, N, obs_dim], reward [K, N], terminated,
         truncated [K, N] uint8); the batch's own buffers hold the last step either way.  With a termination
-        condition set (``set_termination``) the tape is stepped one ``step`` at a time instead: the same
-        results, slower.  Open loop:
+        condition set (``set_termination``) without ``fused=True`` the tape is stepped one ``step`` at a time
+        instead: the same results, slower; with ``fused=True`` it is hs_step_tape as ever.  Open loop:
         benchmarks, trajectory evaluation -- a policy in the loop steps with ``step`` (or, for the PPO pi
         net, inside the launch: hs_rollout, PPO._rollout_fused).  Synchronous;
         one stream group only."""
@@ -461,8 +495,8 @@ class HsBatch:
                    torch.empty(K, self.n, dtype=torch.uint8, device=self.device),
                    torch.empty(K, self.n, dtype=torch.uint8, device=self.device))
             out = _lib.hs_tape_out(*[x.data_ptr() for x in res])
-        if self.termination is not None:
-            # a termination condition: hs_step_tape refuses (a fused launch is bounded by the shortest possible
+        if self.termination is not None and not self.termination_fused:
+            # a termination condition that is not fused-capable: hs_step_tape refuses (a fused launch is bounded by the shortest possible
             # episode), so the tape is stepped one ``step`` at a time -- the same results, slower
             for k in range(K):
                 step = self.step(a[k])

@@ -16,6 +16,7 @@
 #include "hs_kernels.h"
 #include "hs_render.h"
 #include "hs_reward_prog.h"
+#include "hs_term_builtin.h"
 #include "mjcf.h"
 
 static_assert(HS_KINDIM == hs::KINDIM, "include/hsim.h HS_KINDIM is the kernels' record size");
@@ -69,6 +70,11 @@ struct hs_batch {
   int32_t* grace_count = nullptr;
   int32_t* grace_episode = nullptr;
   uint8_t* early = nullptr;
+  // hs_set_termination_builtin: the built-in the predicate was checked against (0: none -- the condition is not
+  // fused-capable), and the grace count between an env's steps of a fused launch [n] (uncached, as mid)
+  int term_kind = 0;
+  double term_min_height = 0.0, term_max_roll_pitch = 0.0;
+  int32_t* mid_count = nullptr;
 };
 
 // a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on
@@ -233,12 +239,28 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
   auto p = params_of(b, mode, nsub);
   p.nsteps = nsteps;
   int nv = b->model->host.nv;
+  // a tape launch of a batch with a fused-capable termination condition: the TERM instances (the entry points
+  // have refused every other tape launch of a batch with a condition)
+  hs::TermArgs tm{};
+  const bool term = mode == hs::MODE_ENV_STEP && b->term_prog && b->term_kind != 0 && (nsteps > 1 || ro);
+  if (term) {
+    tm.kind = b->term_kind;
+    tm.grace_steps = b->grace_steps;
+    tm.min_height = b->term_min_height;
+    tm.max_roll_pitch = b->term_max_roll_pitch;
+    tm.grace_count = b->grace_count;
+    tm.grace_episode = b->grace_episode;
+    tm.early = b->early;
+    tm.mid_count = b->mid_count;
+  }
   if (b->precision == HS_FP64) {
     hs::TapeOut<double> to{tape ? (double*)tape->obs : nullptr, tape ? (double*)tape->reward : nullptr,
                            tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
     e = hs::launch_step<double>((const hs::DevModel<double>*)b->dmodel, nv, env_buffers<double>(b), act, mask,
-                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro, ev, nm);
+                                (const double*)nq, (const double*)nvz, p, b->n, (hipStream_t)stream, &to, ro, ev, nm,
+                                term ? &tm : nullptr);
   } else {
+    if (term) return fail("a fused launch with a termination condition runs on the fp64 Newton engine");
     hs::TapeOut<float> to{tape ? (float*)tape->obs : nullptr, tape ? (float*)tape->reward : nullptr,
                           tape ? tape->terminated : nullptr, tape ? tape->truncated : nullptr};
     e = hs::launch_step<float>((const hs::DevModel<float>*)b->dmodel, nv, env_buffers<float>(b), act, mask,
@@ -260,16 +282,29 @@ int min_episode_len(const hs_batch* b) {
   return (int)std::max(1.0, std::min((double)b->cfg.max_steps, spans));
 }
 
+int fused_step_cap(const hs_batch* b) {
+  return b->term_prog && b->term_kind != 0 ? hs::QTAG_STEPS : std::min(min_episode_len(b), hs::QTAG_STEPS);
+}
+
 struct Region { void* p; size_t bytes; };
 
 // the env state a tape launch changes (restored when it aborts on a resident-tier overflow)
 std::vector<Region> state_regions(const hs_batch* b) {
   const auto& h = b->model->host;
   const size_t N = (size_t)b->n, es = b->precision == HS_FP64 ? 8 : 4;
-  return {{b->buf.qpos, N * h.nq * es}, {b->buf.qvel, N * h.nv * es}, {b->buf.qacc_warmstart, N * h.nv * es},
-          {b->buf.ctrl, N * h.nu * es}, {b->buf.time, N * es}, {b->buf.total_reward, N * es},
-          {b->buf.step_count, N * 4}, {b->buf.episode, N * 4}, {b->buf.warning, N * HS_NWARN * 4},
-          {b->redo_total, sizeof(unsigned long long)}};
+  std::vector<Region> regs = {{b->buf.qpos, N * h.nq * es}, {b->buf.qvel, N * h.nv * es},
+                              {b->buf.qacc_warmstart, N * h.nv * es}, {b->buf.ctrl, N * h.nu * es},
+                              {b->buf.time, N * es}, {b->buf.total_reward, N * es}, {b->buf.step_count, N * 4},
+                              {b->buf.episode, N * 4}, {b->buf.warning, N * HS_NWARN * 4},
+                              {b->redo_total, sizeof(unsigned long long)}};
+  // a fused-capable termination condition: the launch's last step commits the grace counters, their episode
+  // tags and the early bytes, and the per-step replay of an aborted launch starts from the counters it found
+  if (b->term_prog && b->term_kind != 0) {
+    regs.push_back({b->grace_count, N * sizeof(int32_t)});
+    regs.push_back({b->grace_episode, N * sizeof(int32_t)});
+    regs.push_back({b->early, N});
+  }
+  return regs;
 }
 
 // Back up `regs`, run `go` (the tape launch), and read the abort word: 0 = done, 1 = aborted (the
@@ -447,6 +482,11 @@ const char kNoFusedWithTermination[] =
     ": the batch has a termination condition set (hs_set_termination), and a fused launch is bounded by the "
     "shortest possible episode, which a state-dependent end makes unknowable -- step with hs_step / "
     "hs_step_program, or clear the condition";
+// the condition keeps the fused launches out unless it is fused-capable (hs_set_termination_builtin)
+bool term_blocks_fused(const hs_batch* b) { return b->term_prog && b->term_kind == 0; }
+// the most env steps of one fused launch: each env finishes at most one episode in it (min_episode_len), unless
+// a fused-capable condition is set -- its instances write nothing once per episode (hs_env_step.h env_outcome)
+int fused_step_cap(const hs_batch* b);
 }  // namespace
 
 extern "C" {
@@ -607,6 +647,7 @@ void hs_batch_destroy(hs_batch* b) {
   if (b->grace_count) (void)hipFree(b->grace_count);
   if (b->grace_episode) (void)hipFree(b->grace_episode);
   if (b->early) (void)hipFree(b->early);
+  uc_release(b->device, (size_t)b->n * sizeof(int32_t), b->mid_count);
   if (b->mid) uc_release(b->device, (size_t)b->n * hs::MIDDIM * (b->precision == HS_FP64 ? 8 : 4), b->mid);
   if (b->qsync) uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
   if (b->eval_obs) uc_release(b->device, (size_t)b->n * b->obs_dim * sizeof(float), b->eval_obs);
@@ -695,7 +736,7 @@ int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_o
   if (n_steps < 1) return fail("hs_step_tape: n_steps must be >= 1");
   if (out && (!out->obs || !out->reward || !out->terminated || !out->truncated))
     return fail("hs_step_tape: pass all four per-step output arrays, or out = NULL");
-  if (b->term_prog) return fail(std::string("hs_step_tape") + kNoFusedWithTermination);
+  if (term_blocks_fused(b)) return fail(std::string("hs_step_tape") + kNoFusedWithTermination);
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
   const auto& h = b->model->host;
@@ -728,8 +769,16 @@ int hs_step_tape(hs_batch* b, const float* actions, int n_steps, const hs_tape_o
   // without auto-reset a finished env keeps rewriting its terminal info every step (one launch
   // must write each batch address once, see hs_env_step.h step_pair): step by step
   if (n_steps == 1 || !tape_sched || !b->cfg.autoreset || resident <= 0 || !b->mid || !b->qsync) return per_step();
+  // a fused-capable termination condition: its instances ask what the fused rollout asks
+  if (b->term_prog) {
+    if (b->precision != HS_FP64 || h.solver == 1)
+      return fail("hs_step_tape: with a termination condition the tape launch runs on the fp64 Newton engine");
+    if (b->ar_qpos_noise || b->cfg.reward_id == HS_REWARD_NONE)
+      return fail("hs_step_tape: with a termination condition the tape launch needs auto-reset with the on-device "
+                  "reset noise and a device reward");
+  }
   // one launch covers at most the shortest episode and at most QTAG_STEPS steps (its hand-off tags)
-  const int min_len = std::min(min_episode_len(b), hs::QTAG_STEPS);
+  const int min_len = fused_step_cap(b);
   if (n_steps > min_len) {
     for (int t0 = 0; t0 < n_steps; t0 += min_len) {
       const int k = std::min(min_len, n_steps - t0);
@@ -774,7 +823,7 @@ static_assert(HS_ACT_RELU == hs::ACT_RELU && HS_ACT_TANH == hs::ACT_TANH, "activ
 
 int hs_rollout_max_steps(const hs_batch* b) {
   if (!b) return fail("null batch");
-  return std::min(min_episode_len(b), hs::QTAG_STEPS);
+  return fused_step_cap(b);
 }
 
 int hs_rollout(hs_batch* b, const hs_policy* pol, const hs_rollout_bufs* rb, int t_begin, int n_steps, int t_total,
@@ -788,7 +837,7 @@ namespace {
 int fused_policy_check(const hs_batch* b, const hs_policy* pol, int act, int t_begin, int n_steps, int t_total,
                        const std::string& who, int* hidden_out) {
   const auto& h = b->model->host;
-  if (b->term_prog) return fail(who + kNoFusedWithTermination);
+  if (term_blocks_fused(b)) return fail(who + kNoFusedWithTermination);
   if (b->precision != HS_FP64 || h.solver == 1)
     return fail(who + ": the fused rollout runs on the fp64 Newton engine");
   if (!b->cfg.autoreset || b->ar_qpos_noise || b->cfg.reward_id == HS_REWARD_NONE)
@@ -805,10 +854,9 @@ int fused_policy_check(const hs_batch* b, const hs_policy* pol, int act, int t_b
                 "<= 32; two hidden layers of 64, 128 or 256 (hidden = 0: 256); ld1 >= hidden, a multiple of 4)");
   if (act != HS_ACT_RELU && act != HS_ACT_TANH)
     return fail(who + ": activation " + std::to_string(act) + " is neither HS_ACT_RELU (0) nor HS_ACT_TANH (1)");
-  if (n_steps < 1 || t_begin < 0 || t_begin + n_steps > t_total || n_steps > min_episode_len(b) ||
-      n_steps > hs::QTAG_STEPS)
+  if (n_steps < 1 || t_begin < 0 || t_begin + n_steps > t_total || n_steps > fused_step_cap(b))
     return fail(who + ": steps [t_begin, t_begin + n_steps) must lie in [0, t_total) and n_steps in [1, " +
-                std::to_string(std::min(min_episode_len(b), hs::QTAG_STEPS)) + "] (hs_rollout_max_steps)");
+                std::to_string(fused_step_cap(b)) + "] (hs_rollout_max_steps)");
   *hidden_out = hidden;
   return 0;
 }
@@ -1478,6 +1526,7 @@ int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* 
 
 int hs_set_termination(hs_batch* b, const hs_reward_program* pred, const double* params, int grace_steps) {
   if (!b) return fail("hs_set_termination: null batch");
+  b->term_kind = 0;   // (hs_set_termination_builtin marks the condition fused-capable after this call)
   if (!pred) {   // clear: the buffers stay, the next hs_set_termination starts their counters afresh
     b->term_prog = nullptr;
     return 0;
@@ -1502,6 +1551,60 @@ int hs_set_termination(hs_batch* b, const hs_reward_program* pred, const double*
   for (int k = 0; k < HS_RP_MAX_PARAMS; k++) b->term_params[k] = k < pred->n_params ? params[k] : 0.0;
   b->grace_steps = grace_steps;
   b->term_prog = pred;
+  return 0;
+}
+
+static_assert(HS_TERM_FALLEN == hs::TERM_FALLEN && HS_TERM_LOST_BALANCE == hs::TERM_LOST_BALANCE, "built-in kinds");
+
+int hs_set_termination_builtin(hs_batch* b, const hs_reward_program* pred, const double* params, int grace_steps,
+                               int kind, double min_height, double max_roll_pitch) {
+  const std::string who = "hs_set_termination_builtin";
+  if (!b || !pred) return fail(who + ": null batch or predicate");
+  if (kind != HS_TERM_FALLEN && kind != HS_TERM_LOST_BALANCE)
+    return fail(who + ": kind " + std::to_string(kind) + " is neither HS_TERM_FALLEN (1) nor HS_TERM_LOST_BALANCE (2)");
+  if (!(min_height == min_height) || !(max_roll_pitch == max_roll_pitch))
+    return fail(who + ": min_height / max_roll_pitch must not be NaN");
+  if (pred->n_params > 0 && !params) return fail(who + ": the program has parameters, params must not be NULL");
+  // program and built-in must be the same predicate: the program reads qpos only, and agrees with the built-in
+  // on the probe rows (hs_term_builtin.h) -- refused before anything is set or launched
+  if (pred->info.fields & ~(1u << hs::RP_F_QPOS)) {
+    std::string names;
+    for (int k = 0; k < hs::RP_NFIELDS; k++)
+      if (k != hs::RP_F_QPOS && (pred->info.fields & (1u << k))) names += std::string(names.empty() ? "" : ", ") + kRpFieldNames[k];
+    return fail(who + ": the predicate reads " + names + "; a built-in condition is a function of qpos alone");
+  }
+  const int bad = hs::term_probe_mismatch(pred->dims, pred->code.data(), (int)(pred->code.size() / 5), pred->consts.data(),
+                                          params, kind, min_height, max_roll_pitch);
+  if (bad >= 0)
+    return fail(who + ": the predicate and the built-in (kind " + std::to_string(kind) + ", min_height " +
+                std::to_string(min_height) + ", max_roll_pitch " + std::to_string(max_roll_pitch) +
+                ") differ on probe row " + std::to_string(bad) + ": not the same condition");
+  if (int rc = hs_set_termination(b, pred, params, grace_steps)) return rc;
+  DeviceGuard g(b->device);
+  const size_t N = (size_t)b->n;
+  if (!b->mid_count && !uc_alloc(b->device, N * sizeof(int32_t), (void**)&b->mid_count)) {
+    b->mid_count = nullptr;
+    return fail("hipExtMallocWithFlags(grace hand-off counts, uncached) failed");
+  }
+  // (a recycled uncached block holds another batch's words: a lost hand-off would read them)
+  if (!hip_ok(hipMemset(b->mid_count, 0, N * sizeof(int32_t)), "hs_set_termination_builtin") ||
+      !hip_ok(hipDeviceSynchronize(), "hs_set_termination_builtin"))
+    return -1;
+  b->term_kind = kind;
+  b->term_min_height = min_height;
+  b->term_max_roll_pitch = max_roll_pitch;
+  return 0;
+}
+
+int hs_termination_builtin_eval_host(int kind, double min_height, double max_roll_pitch, int n, const double* qpos,
+                                     int ld, uint8_t* out) {
+  if (kind != HS_TERM_FALLEN && kind != HS_TERM_LOST_BALANCE)
+    return fail("hs_termination_builtin_eval_host: kind must be HS_TERM_FALLEN (1) or HS_TERM_LOST_BALANCE (2)");
+  if (n < 0) return fail("hs_termination_builtin_eval_host: negative n");
+  if (n == 0) return 0;
+  if (!qpos || !out || ld < 7) return fail("hs_termination_builtin_eval_host: null qpos / out, or ld < 7");
+  for (int i = 0; i < n; i++)
+    out[i] = hs::term_builtin_holds<double>(kind, min_height, max_roll_pitch, qpos + (size_t)i * ld) ? 1 : 0;
   return 0;
 }
 

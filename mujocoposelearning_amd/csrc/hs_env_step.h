@@ -10,6 +10,7 @@
 #include "hs_stepper.h"
 #include "hs_reward.h"
 #include "hs_policy.h"
+#include "hs_term_builtin.h"
 
 namespace hs {
 namespace {
@@ -201,10 +202,11 @@ __device__ __forceinline__ bool resets_next(KPtr<T> k, MPtr<T> m, T time, int st
 // lane's sub-lane of its half, `env` / `env_id` the env its half steps.
 
 // load from batch: the env's state as the previous launch committed it
-template <bool EVAL, typename T, typename C>
+// TERM: also the env's effective grace count (the stored one belongs to the episode it is tagged with)
+template <bool EVAL, bool TERM = false, typename T, typename C>
 __device__ __forceinline__ void load_batch_state(KPtr<T> ka, Scratch<T, C>& s, int sl, int nq, int nv, int env_id,
                                                  bool rollout, T& time, T& xws, int& step_count, uint32_t& episode,
-                                                 T& total, double& epacc) {
+                                                 T& total, double& epacc, int32_t& grace) {
   time = ka->b.time[env_id];
   xws = (sl < nv) ? ka->b.qacc_ws[(size_t)env_id * nv + sl] : T(0);
   if (sl < nq) s.qpos[sl] = ka->b.qpos[(size_t)env_id * nq + sl];
@@ -215,6 +217,8 @@ __device__ __forceinline__ void load_batch_state(KPtr<T> ka, Scratch<T, C>& s, i
   total = ka->b.total_reward[env_id];
   if constexpr (!EVAL)
     if (rollout) epacc = ka->ro.ep_acc[env_id];
+  if constexpr (TERM)
+    grace = ka->tm.grace_episode[env_id] == (int32_t)episode ? ka->tm.grace_count[env_id] : 0;
 }
 
 // Queued schedule (launch_step sets p.queue when the pairs outnumber the resident waves): the
@@ -229,11 +233,12 @@ __device__ __forceinline__ void load_batch_state(KPtr<T> ka, Scratch<T, C>& s, i
 
 // load from hand-off row: wait for the pair's previous chunk (or tape step) to hand the state over, then
 // read the row.  false: the tape launch aborted, the caller leaves (results discarded: the host replays).
-template <bool EVAL, typename T, typename C>
+// TERM: the grace count comes beside the row (tm.mid_count).
+template <bool EVAL, bool TERM = false, typename T, typename C>
 __device__ __forceinline__ bool load_handoff_state(KPtr<T> ka, Scratch<T, C>& s, int lane, int nq, int nv, int nu,
                                                    int env_id, int pair, int wait_tag, int tstep, bool rollout,
                                                    T& time, T& xws, int& step_count, uint32_t& episode, T& total,
-                                                   int (&warn)[NWARN], T& act_row, double& epacc) {
+                                                   int (&warn)[NWARN], T& act_row, double& epacc, int32_t& grace) {
   const int sl = lane & (HL - 1);
   int* flag = ka->b.qsync + QS_FLAG + pair;
   int seen = 0, abort = 0;
@@ -267,6 +272,7 @@ __device__ __forceinline__ bool load_handoff_state(KPtr<T> ka, Scratch<T, C>& s,
     if (sl < nu) act_row = row_ld(r + MID_ACT + sl);
     if constexpr (!EVAL) epacc = (double)row_ld(r + MID_EPACC);
   }
+  if constexpr (TERM) grace = row_ld(ka->tm.mid_count + env_id);
   // never seen in practice; if it were, the state is poisoned so that the substep's mj_checkPos
   // resets the env (mj_resetData, ctrl 0 for that substep) -- counted in its own slot,
   // HS_WARN_HANDOFF, not as a bad state (the -1 cancels the HS_WARN_BADQPOS count the poisoned
@@ -280,11 +286,11 @@ __device__ __forceinline__ bool load_handoff_state(KPtr<T> ka, Scratch<T, C>& s,
 }
 
 // store hand-off row: the state and the warning counters accumulated so far, for the pair's next chunk
-// (or next tape step).  The caller publishes it (publish, below).
-template <typename T, typename C>
+// (or next tape step).  The caller publishes it (publish, below).  TERM: and the grace count beside it.
+template <bool TERM = false, typename T, typename C>
 __device__ __forceinline__ void store_handoff_state(KPtr<T> k, const Scratch<T, C>& s, int sl, int nq, int nv, int env,
                                                     T time, T xws, int step_count, uint32_t episode, T total,
-                                                    const int* warn) {
+                                                    const int* warn, int32_t grace = 0) {
   T* r = k->b.mid + (size_t)env * MIDDIM;
   if (sl < nq) row_st(r + MID_Q + sl, s.qpos[sl]);
   if (sl + HL < nq) row_st(r + MID_Q + sl + HL, s.qpos[sl + HL]);
@@ -296,6 +302,7 @@ __device__ __forceinline__ void store_handoff_state(KPtr<T> k, const Scratch<T, 
     row_st(r + MID_SC, (T)step_count);
     row_st(r + MID_EP, (T)episode);
     row_st(r + MID_TOT, total);
+    if constexpr (TERM) row_st(k->tm.mid_count + env, grace);
   }
 }
 
@@ -378,11 +385,13 @@ __device__ __forceinline__ void eval_rows(KPtr<T> k, const Stepper<T, NV, C>& st
 // env-step outcome, after the last substep (custom_env.py:163-230): the obs row, and for an env step the
 // reward, the done flags, a finished episode's info and terminal obs, the fused rollout's or evaluation's
 // rows, and whether this half resets now (do_reset) or, HINTS, some half will in its next env step
-template <bool HINTS, bool EVAL, typename T, int NV, typename C>
+// TERM: the built-in termination condition on the post-step state joins `term` (hs_term_builtin.h), and the
+// per-env terminal rows are the launch's last step's alone (an env may end several episodes in one launch)
+template <bool HINTS, bool EVAL, bool TERM = false, typename T, int NV, typename C>
 __device__ __forceinline__ void env_outcome(KPtr<T> k, Stepper<T, NV, C>& st, int lane, int nq, int nv, int nu,
                                             int env, int tstep, bool tape_final, bool rollout, bool active, T act,
                                             T time, uint32_t episode, int& step_count, T& total, double& epacc,
-                                            bool& rdone, bool& do_reset, bool& will_reset_next) {
+                                            bool& rdone, bool& do_reset, bool& will_reset_next, int32_t& grace) {
   const Scratch<T, C>& s = st.s;
   const int sl = lane & (HL - 1);
   const int obs_dim = k->p.obs_dim;
@@ -406,6 +415,20 @@ __device__ __forceinline__ void env_outcome(KPtr<T> k, Stepper<T, NV, C>& st, in
   HS_STAMP(st.clk, 25);
   total += r;
   bool term = (double)time >= k->p.duration;
+  if constexpr (TERM) {
+    // the episode also ends when the condition has held for grace_steps consecutive env steps of it
+    // (custom_env.py:167-200), whether or not the step is truncated; the count, the episode it belongs to and
+    // the early byte are committed by the launch's last step, as the state is
+    const bool holds = term_builtin_holds<T>(k->tm.kind, (T)k->tm.min_height, (T)k->tm.max_roll_pitch, s.qpos);
+    bool early = false;
+    grace = rp_grace_update(grace, (int32_t)episode, (int32_t)episode, holds, k->tm.grace_steps, &early);
+    term |= early;
+    if (tape_final && active && sl == 0) {
+      k->tm.grace_count[env] = grace;
+      k->tm.grace_episode[env] = (int32_t)episode;
+      k->tm.early[env] = early;
+    }
+  }
   if (sl == 0 && active && (k->tape.reward || tape_final)) {
     const size_t o = k->tape.reward ? (size_t)tstep * k->nenv : 0;
     (k->tape.reward ? k->tape.reward : k->b.reward)[o + env] = r;
@@ -414,7 +437,7 @@ __device__ __forceinline__ void env_outcome(KPtr<T> k, Stepper<T, NV, C>& st, in
   }
   // the final step's info of a finished episode (SubprocVecEnv returns its step_count /
   // total_reward before resetting, custom_env.py:216-224), with or without auto-reset
-  if ((term || trunc) && active && sl == 0) {
+  if ((term || trunc) && active && sl == 0 && (!TERM || tape_final)) {
     if (k->b.term_step_count) k->b.term_step_count[env] = step_count;
     if (k->b.term_total_reward) k->b.term_total_reward[env] = total;
   }
@@ -424,7 +447,7 @@ __device__ __forceinline__ void env_outcome(KPtr<T> k, Stepper<T, NV, C>& st, in
     else rollout_rows(k, st, sl, env, tstep, obs_dim, r, term, trunc, epacc);
   }
   if ((term || trunc) && k->p.autoreset && active) {
-    write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
+    if (!TERM || tape_final) write_obs(st.m, s, sl, st.qfa, k->b.terminal_obs + (size_t)env * obs_dim, obs_dim);
     do_reset = true;
   }
   // (an env that resets below restarts at time = dt, step 0: not flagged)
@@ -457,14 +480,17 @@ __device__ __forceinline__ bool defer_to_wide(KPtr<T> k, const int* warn, int sl
 // batch address would leave whichever dirty line is written back last.  For the same reason the
 // batch's obs / reward / done rows are written by the last step only when the tape has no
 // per-step outputs, and the host keeps each env to at most one finished episode per tape launch
-// (hs_step_tape), so its terminal obs / info rows are written once.
-template <typename T, int NV, typename C>
+// (hs_step_tape), so its terminal obs / info rows are written once.  A TERM instance, in which an env may
+// finish several episodes, writes those rows on the tape's last step only (env_outcome).
+template <bool TERM = false, typename T, int NV, typename C>
 __device__ __forceinline__ bool commit_or_handoff(KPtr<T> k, const Stepper<T, NV, C>& st, int sl, int nq, int nv,
                                                   int env, T time, T xws, int step_count, uint32_t episode, T total,
-                                                  const int* warn, bool tape_final, bool tape_handoff) {
+                                                  const int* warn, bool tape_final, bool tape_handoff,
+                                                  int32_t grace = 0) {
   if (defer_to_wide<T, C>(k, warn, sl, env)) return true;
   if (tape_final) commit(st.m, k, st, env, time, xws, step_count, episode, total, warn, k->p.full_state != 0);
-  if (tape_handoff) store_handoff_state(k, st.s, sl, nq, nv, env, time, xws, step_count, episode, total, warn);
+  if (tape_handoff)
+    store_handoff_state<TERM>(k, st.s, sl, nq, nv, env, time, xws, step_count, episode, total, warn, grace);
   return false;
 }
 
@@ -579,8 +605,10 @@ __device__ __forceinline__ void signal_next_step(KPtr<T> k, int lane, int pair, 
 // reads it back, the clipped action goes to the pair's next step; a finished episode writes its three
 // result slots, a traced env one trace row.
 // NORM (with ROLL): the instances of hs_rollout_norm / hs_evaluate_norm, whose policy normalises its obs.
+// TERM (tape launches of the fp64 Newton engine): the instances that evaluate a built-in termination condition
+// themselves (KArgs::tm, hs_set_termination_builtin).
 template <typename T, int NV, bool PGS, typename C, bool ROLL = false, bool HINTS = false, bool EVAL = false,
-          bool NORM = false>
+          bool NORM = false, bool TERM = false>
 __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCache<T, C>* pcache, int idx,
                                           int nidx, const int* list, int s0, int s1, int pair, bool ghost = false,
                                           int wait_tag = 0, int set_tag = 0, int tstep = 0, bool tape_launch = false,
@@ -613,12 +641,14 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
   int step_count;
   uint32_t episode;
   T total, act;
+  [[maybe_unused]] int32_t grace = 0;   // (TERM) consecutive env steps of the episode the condition has held
   if (wait_tag != 0) {   // queued: the pair's previous chunk (or tape step) hands the state over
-    if (!load_handoff_state<EVAL>(ka, s, lane, nq, nv, nu, env_id, pair, wait_tag, tstep, rollout, time, xws,
-                                  step_count, episode, total, warn, act_row, epacc))
+    if (!load_handoff_state<EVAL, TERM>(ka, s, lane, nq, nv, nu, env_id, pair, wait_tag, tstep, rollout, time, xws,
+                                        step_count, episode, total, warn, act_row, epacc, grace))
       return;
   } else {
-    load_batch_state<EVAL>(ka, s, sl, nq, nv, env_id, rollout, time, xws, step_count, episode, total, epacc);
+    load_batch_state<EVAL, TERM>(ka, s, sl, nq, nv, env_id, rollout, time, xws, step_count, episode, total, epacc,
+                                 grace);
   }
   {
     // data.ctrl is an input only to a raw physics call that keeps the current ctrl; env steps set
@@ -665,7 +695,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
     const int env = opaque_v(env_id);   // per-env addresses recomputed at each use, not kept live
     if (sub == s1 && s1 < nsub) {         // queued chunk ends before the last substep: hand over
       KPtr<T> k = opaque(ka);
-      if (active) store_handoff_state(k, s, sl, nq, nv, env, time, xws, step_count, episode, total, warn);
+      if (active) store_handoff_state<TERM>(k, s, sl, nq, nv, env, time, xws, step_count, episode, total, warn, grace);
       publish(k->b.qsync + QS_FLAG + pair, set_tag, lane);   // the row is in memory before the flag is
       HS_FLUSH();
       break;
@@ -673,11 +703,11 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
     if (sub == nsub && !in_reset) {       // after the last substep: the env step's outcome
       if (nsub > 0) {
         KPtr<T> k = opaque(ka);
-        env_outcome<HINTS, EVAL>(k, st, lane, nq, nv, nu, env, tstep, tape_final, rollout, active, act, time, episode,
-                                 step_count, total, epacc, rdone, do_reset, will_reset_next);
+        env_outcome<HINTS, EVAL, TERM>(k, st, lane, nq, nv, nu, env, tstep, tape_final, rollout, active, act, time,
+                                       episode, step_count, total, epacc, rdone, do_reset, will_reset_next, grace);
         if (active && !do_reset) {
-          if (commit_or_handoff(k, st, sl, nq, nv, env, time, xws, step_count, episode, total, warn, tape_final,
-                                tape_handoff))
+          if (commit_or_handoff<TERM>(k, st, sl, nq, nv, env, time, xws, step_count, episode, total, warn, tape_final,
+                                      tape_handoff, grace))
             deferred = true;
           active = false;   // committed (or deferred); a reset pass below is scratch work for this half
         }
@@ -686,6 +716,7 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
       in_reset = true;
       st.dbg = nullptr;
       reset_draw(opaque(ka), m, s, sl, nq, nv, nu, env, episode, time, xws);
+      if constexpr (TERM) grace = 0;   // the count belongs to the episode that ended
     } else if (sub > nsub) {              // after the reset's substep: the reset obs, the new episode's state
       if (do_reset && active) {
         KPtr<T> k = opaque(ka);
@@ -696,7 +727,8 @@ __device__ __forceinline__ void step_pair(KPtr<T> ka, Scratch<T, C>* smem, PgsCa
         if constexpr (EVAL) {
           if (rollout) write_obs<true>(st.m, s, sl, st.qfa, k->ro.obs + (size_t)env * k->ro.D, obs_dim);
         } else if (rollout) write_obs(st.m, s, sl, st.qfa, ro_next_obs(k, env, tstep), obs_dim);   // the reset obs
-        if (commit_or_handoff(k, st, sl, nq, nv, env, time, xws, 0, episode, T(0), warn, tape_final, tape_handoff))
+        if (commit_or_handoff<TERM>(k, st, sl, nq, nv, env, time, xws, 0, episode, T(0), warn, tape_final, tape_handoff,
+                                    grace))
           deferred = true;
       }
       HS_FLUSH();

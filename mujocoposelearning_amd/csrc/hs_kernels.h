@@ -198,6 +198,23 @@ struct NormArgs {
   float clip;
 };
 
+// A built-in termination condition evaluated inside a tape launch (hs_set_termination_builtin, the TERM kernel
+// instances only; hs_term_builtin.h): after every env step the predicate on the post-step qpos, the grace
+// counter, terminated |= early.  The count travels from an env's step to its next beside the hand-off row, in
+// mid_count (uncached memory, handled like b.mid); the launch's last step commits it with the state.
+// In a TERM instance an env may end several episodes in one launch, so the per-env terminal rows
+// (b.terminal_obs, term_step_count, term_total_reward) are written by the launch's last step only: they are
+// defined for the envs that were done on that step.
+struct TermArgs {
+  int kind;                 // TERM_FALLEN / TERM_LOST_BALANCE (0: none, every other instance)
+  int grace_steps;          // >= 1
+  double min_height, max_roll_pitch;
+  int32_t* grace_count;     // [N] the batch's grace counters, read by the first step and written by the last
+  int32_t* grace_episode;   // [N] the episode number each count belongs to
+  uint8_t* early;           // [N] early_terminated of the launch's last step
+  int32_t* mid_count;       // [N] the count between an env's steps (uncached, hs_batch owned)
+};
+
 // p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape` (may be null), env
 // steps of one env pair run back to back on the chunk queue with the state handed over through
 // b.mid; no wide-tier launch follows (an overflow sets qsync[QS_ABORT], the host replays the tape).
@@ -205,11 +222,17 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape = nullptr,
-                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr, const NormArgs* nm = nullptr);
+                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr, const NormArgs* nm = nullptr,
+                       const TermArgs* tm = nullptr);
 
 // The fused rollout / evaluation instance with obs normalisation (KArgs::nm set) on the chunk queue: kargs is
 // launch_step's KArgs<double>, max_grid its grid (the launch takes no more waves than the instance holds)
 hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream);
+// The same for the five instances that evaluate a built-in termination condition (KArgs::tm set; a code
+// object of their own): the tape (neither rollout nor eval), the rollout and the evaluation, the latter two
+// with or without obs normalisation
+hipError_t launch_queue_term(const void* kargs, unsigned max_grid, bool rollout, bool eval, bool norm,
+                             hipStream_t stream);
 
 // waves of the resident step-kernel instance the current device holds at once (0 if unknown)
 template <typename T>

@@ -88,7 +88,9 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && !PGS) ? 2 : 1) void step_ker
 // rows, a kernel of its own so that the rollout instance keeps its code and registers
 // NORM (with ROLL): the instances whose policy normalises its obs on load (hs_rollout_norm,
 // hs_evaluate_norm; KArgs::nm), kernels of their own so that every other instance keeps its code and registers
-template <typename T, int NV, bool PGS, bool ROLL = false, bool EVAL = false, bool NORM = false>
+// TERM: the instances that evaluate a built-in termination condition after every env step (KArgs::tm,
+// hs_set_termination_builtin): the tape, the rollout and the evaluation, kernels of their own likewise
+template <typename T, int NV, bool PGS, bool ROLL = false, bool EVAL = false, bool NORM = false, bool TERM = false>
 __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via kernarg ptr */) {
   const KPtr<T> ka = (KPtr<T>)__builtin_amdgcn_kernarg_segment_ptr();
   // this launch's epoch (its hand-off tags are qtag(epoch, ...)): the epoch only changes after every
@@ -177,8 +179,9 @@ __global__ __launch_bounds__(64, 1) void step_kernel_queue(KArgs<T> /* read via 
     const int wait_tag = tape ? (t > 0 ? qtag(epoch, t - 1, 1) : 0) : (last ? qtag(epoch, 0, 0) : 0);
     const int set_tag = tape ? (t < K - 1 ? qtag(epoch, t, 1) : 0) : (last ? 0 : qtag(epoch, 0, 0));
     int hint;   // (STEP_* bits, wave-uniform)
-    step_pair<T, NV, PGS, Resident<T>, ROLL, true, EVAL, NORM>(k, smem, pcache, env, k->nenv, nullptr, s0, s1, pair,
-                                                         single && upper, wait_tag, set_tag, t, tape, &hint);
+    step_pair<T, NV, PGS, Resident<T>, ROLL, true, EVAL, NORM, TERM>(k, smem, pcache, env, k->nenv, nullptr, s0, s1,
+                                                                     pair, single && upper, wait_tag, set_tag, t, tape,
+                                                                     &hint);
 #ifdef HS_TIMING
     // per item (indexed as step_pair's q0 stamps): its claim index within its chunk kind, and whether
     // it ran the reset pass
@@ -435,7 +438,7 @@ int resident_waves(bool pgs) {
 // a claim (step_kernel_queue), so every wave of the grid has to be running from the start.  It is
 // below resident_waves() where the queue instance's occupancy is below the direct kernel's (the fp32
 // Newton engine: 1 wave per SIMD against 2).
-template <typename T, bool PGS, bool ROLL, bool EVAL = false, bool NORM = false>
+template <typename T, bool PGS, bool ROLL, bool EVAL = false, bool NORM = false, bool TERM = false>
 int queue_waves() {
   constexpr int MAXDEV = 64;
   static int cache[MAXDEV] = {};   // 0: not yet computed
@@ -445,7 +448,7 @@ int queue_waves() {
   int per_cu = 0, v = -1;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL, NORM>, WAVE, 0) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL, NORM, TERM>, WAVE, 0) == hipSuccess &&
       per_cu > 0)
     v = per_cu * prop.multiProcessorCount;
   cache[dev] = v;
@@ -456,17 +459,23 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape,
-                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm) {
+                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm, const TermArgs* tm) {
   if (nenv <= 0) return hipSuccess;
   if (nv != 27) return hipErrorInvalidValue;
   KArgs<T> args{(MPtr<T>)dmodel, b, actions, reset_mask, noise_qpos, noise_qvel, p, nenv,
                 tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{},
-                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}};
+                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}, tm ? *tm : TermArgs{}};
   if (nm && (!ro || !nm->mean || !nm->inv_std || !(nm->clip > 0.f))) return hipErrorInvalidValue;
   // fused rollouts: the fp64 Newton engine
   if (ro && (sizeof(T) != 8 || !ro->obs || p.solver == SOLVER_PGS)) return hipErrorInvalidValue;
   // fused evaluation: a rollout launch (the policy, ro.obs = the staging rows) with result slots
   if (ev && (!ro || !ev->episode0 || ev->max_episodes < 1 || ev->n_trace < 0 || ev->n_trace > nenv))
+    return hipErrorInvalidValue;
+  // a built-in termination condition: tape launches of the fp64 Newton engine with auto-reset (an early end
+  // resets inside the launch)
+  if (tm && (sizeof(T) != 8 || p.solver == SOLVER_PGS || p.mode != MODE_ENV_STEP || !p.autoreset ||
+             (tm->kind != TERM_FALLEN && tm->kind != TERM_LOST_BALANCE) || tm->grace_steps < 1 || !tm->grace_count ||
+             !tm->grace_episode || !tm->early || !tm->mid_count || !(args.p.nsteps > 1 || ro)))
     return hipErrorInvalidValue;
   if (args.p.nsteps < 1) args.p.nsteps = 1;
   // chunk-queue schedule when the env pairs outnumber the waves the GPU holds at once (the fp64
@@ -534,6 +543,10 @@ hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b
     return hipSuccess;
   };
   hipError_t rc = hipSuccess;
+  if (tm) {
+    // the TERM instances live in an object of their own (launch_queue_term below)
+    if constexpr (sizeof(T) == 8) return launch_queue_term(&args, grid.x, ro != nullptr, ev != nullptr, nm != nullptr, stream);
+  }
   if (p.solver == SOLVER_PGS) {
     rc = launch_tiers(std::true_type{});
   } else if (ro) {
@@ -573,7 +586,9 @@ hipError_t launch_kinematics_batch(const DevModel<T>* dmodel, int nv, int n, con
 // (HS_ONLY_NORM, the fp64 flags) for the two fused instances whose policy normalises its obs
 // (hs_rollout_norm, hs_evaluate_norm): in a code object of their own they leave the engines' code objects,
 // kernel for kernel and byte for byte, what they are without them.
-#ifdef HS_ONLY_NORM
+// A fourth pass (HS_ONLY_TERM, the fp64 flags) does the same for the five instances that evaluate a built-in
+// termination condition (hs_set_termination_builtin).
+#if defined(HS_ONLY_NORM)
 hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream) {
   const KArgs<double>& args = *static_cast<const KArgs<double>*>(kargs);
   const int held = eval ? queue_waves<double, false, true, true, true>() : queue_waves<double, false, true, false, true>();
@@ -585,12 +600,32 @@ hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hi
     hipLaunchKernelGGL((step_kernel_queue<double, 27, false, true, false, true>), grid, block, 0, stream, args);
   return hipGetLastError();
 }
+#elif defined(HS_ONLY_TERM)
+hipError_t launch_queue_term(const void* kargs, unsigned max_grid, bool rollout, bool eval, bool norm,
+                             hipStream_t stream) {
+  const KArgs<double>& args = *static_cast<const KArgs<double>*>(kargs);
+  if (!rollout && (eval || norm)) return hipErrorInvalidValue;
+  // one instance: its wave count, then its launch
+  auto go = [&](auto roll, auto ev, auto nm) -> hipError_t {
+    constexpr bool R = decltype(roll)::value, E = decltype(ev)::value, N = decltype(nm)::value;
+    const int held = queue_waves<double, false, R, E, N, true>();
+    if (held <= 0) return hipErrorInvalidValue;
+    const dim3 grid(std::min(max_grid, (unsigned)held)), block(WAVE);
+    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, R, E, N, true>), grid, block, 0, stream, args);
+    return hipGetLastError();
+  };
+  using Y = std::true_type;
+  using F = std::false_type;
+  if (!rollout) return go(F{}, F{}, F{});
+  if (eval) return norm ? go(Y{}, Y{}, Y{}) : go(Y{}, Y{}, F{});
+  return norm ? go(Y{}, F{}, Y{}) : go(Y{}, F{}, F{});
+}
 #else
 #ifndef HS_ONLY_F64
 template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuffers<float>&, const float*,
                                        const uint8_t*, const float*, const float*, const StepParams&, int,
                                        hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*,
-                                       const NormArgs*);
+                                       const NormArgs*, const TermArgs*);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
 template hipError_t launch_kinematics_batch<float>(const DevModel<float>*, int, int, const float*, const float*,
@@ -602,7 +637,7 @@ template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvBuffers<double>&, const float*,
                                         const uint8_t*, const double*, const double*, const StepParams&, int,
                                         hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*,
-                                        const NormArgs*);
+                                        const NormArgs*, const TermArgs*);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
 template hipError_t launch_kinematics_batch<double>(const DevModel<double>*, int, int, const double*, const double*,
@@ -610,6 +645,6 @@ template hipError_t launch_kinematics_batch<double>(const DevModel<double>*, int
 template hipError_t launch_reward_eval<double>(const RewardEvalArgs<double>&, hipStream_t);
 template hipError_t launch_pack<double>(const PackArgs<double>&, hipStream_t);
 #endif
-#endif   // HS_ONLY_NORM
+#endif   // HS_ONLY_NORM / HS_ONLY_TERM
 
 }  // namespace hs

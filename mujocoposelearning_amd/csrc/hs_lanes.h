@@ -254,6 +254,7 @@ struct KArgs {
   RolloutArgs ro;             // fused rollout (ro.obs != null): actions from the policy, see hs_kernels.h
   EvalArgs ev;                // fused evaluation (the EVAL instance only; after ro, so every other offset stays)
   NormArgs nm;                // obs normalisation of the fused policy (the NORM instances only; last, as above)
+  TermArgs tm;                // built-in termination condition (the TERM instances only; last, as above)
 };
 template <typename T>
 using KPtr = const __attribute__((address_space(4))) KArgs<T>*;

@@ -665,17 +665,59 @@ def device_termination(name, registry=None):
     return rec
 
 
+# the built-in conditions the step kernel's fused instances evaluate themselves (include/hsim.h HS_TERM_*,
+# csrc/hs_term_builtin.h): the registered function -> its kind
+TERM_FALLEN, TERM_LOST_BALANCE = 1, 2
+
+
+def builtin_termination_kind(rec):
+    """HS_TERM_FALLEN / HS_TERM_LOST_BALANCE when ``rec`` is the record of one of the two registered built-ins
+    (the function itself, under whatever name), else None."""
+    return {fallen: TERM_FALLEN, lost_balance: TERM_LOST_BALANCE}.get(rec.fn)
+
+
+def builtin_termination_eval_host(kind, qpos, min_height=0.8, max_roll_pitch=np.pi / 4):
+    """The built-in predicate ``kind`` on the rows of ``qpos`` [n, >= 7] float64 (``hs_termination_builtin_eval_host``:
+    the function the fused kernel instances run, on the CPU, needing no batch and no GPU).  Returns [n] bool."""
+    from . import _lib
+    q = np.ascontiguousarray(qpos, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] < 7:
+        raise ValueError("builtin_termination_eval_host: qpos must be [n, >= 7]")
+    out = np.zeros(len(q), dtype=np.uint8)
+    _lib.check(_lib.lib().hs_termination_builtin_eval_host(int(kind), float(min_height), float(max_roll_pitch), len(q),
+                                                          q.ctypes.data, q.shape[1], out.ctypes.data))
+    return out != 0
+
+
+def termination_fused_from_config(termination, registry=None):
+    """The ``"fused"`` flag of ``env_config["termination"]`` (default False), checked: a non-bool, or True with a
+    condition that is not one of the two registered built-ins, raises ValueError.  None config: False."""
+    if termination is None:
+        return False
+    checked = termination_from_config(termination, registry)
+    fused = termination.get("fused", False)
+    if not isinstance(fused, (bool, np.bool_)):
+        raise ValueError(f"termination: fused must be a bool, got {fused!r}")
+    if fused and builtin_termination_kind(checked[0]) is None:
+        raise ValueError(f"termination: fused=True needs one of the built-in conditions 'fallen' / 'lost_balance': "
+                         f"{checked[0].name!r} is a user-registered predicate, which only the interpreter of the "
+                         "per-step path can evaluate")
+    return bool(fused)
+
+
 def termination_from_config(termination, registry=None):
-    """``env_config["termination"]`` -- ``{"type": name, "params": {...}, "grace_steps": k}`` or None -- checked:
-    returns (record, parameter overrides, grace_steps) or None.  Unknown type, unknown parameter key or a
-    grace period that is not an integer >= 1: ValueError."""
+    """``env_config["termination"]`` -- ``{"type": name, "params": {...}, "grace_steps": k, "fused": bool}`` or None
+    -- checked: returns (record, parameter overrides, grace_steps) or None.  Unknown type, unknown parameter key or a
+    grace period that is not an integer >= 1: ValueError.  The ``"fused"`` flag is ``termination_fused_from_config``'s."""
     if termination is None:
         return None
     if not isinstance(termination, dict) or "type" not in termination:
         raise ValueError('termination: expected {"type": name, "params": {...}, "grace_steps": k} or None')
-    unknown = set(termination) - {"type", "params", "grace_steps"}
+    unknown = set(termination) - {"type", "params", "grace_steps", "fused"}
     if unknown:
         raise ValueError(f"termination: unknown key(s) {sorted(unknown)}")
+    if not isinstance(termination.get("fused", False), (bool, np.bool_)):
+        raise ValueError(f"termination: fused must be a bool, got {termination['fused']!r}")
     rec = device_termination(termination["type"], registry)
     params = termination.get("params") or None
     rec.params(params)

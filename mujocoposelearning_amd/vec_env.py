@@ -105,13 +105,16 @@ class HumanoidVecEnv(_Base):
         # when that predicate has held for grace_steps env steps (custom_env.py:167-200, there commented out),
         # evaluated on the device after every step.  Absent or None: nothing changes.  An unknown type or
         # parameter raises here.
+        # "fused": True (the built-ins only) keeps the fused rollout / evaluation / tape launches (rollout_handle).
         self._termination = None
+        self._termination_fused = False
         if cfg.get("termination") is not None:
-            from .reward_program import termination_from_config
+            from .reward_program import termination_from_config, termination_fused_from_config
             rec, tparams, grace = termination_from_config(cfg["termination"])
+            self._termination_fused = termination_fused_from_config(cfg["termination"])
             if len(self.batch._groups) != 1:
                 raise NotImplementedError("a termination condition steps one stream group (groups=1)")
-            self._termination = self.batch.set_termination(rec.name, tparams, grace)
+            self._termination = self.batch.set_termination(rec.name, tparams, grace, fused=self._termination_fused)
         obs_space = Box(low=-np.inf, high=np.inf, shape=(self.batch.obs_dim,), dtype=np.float64)
         act_space = Box(low=-1, high=1, shape=(self.model.nu,), dtype=np.float32)
         super().__init__(n_envs, obs_space, act_space)
@@ -147,10 +150,12 @@ class HumanoidVecEnv(_Base):
     def rollout_handle(self):
         """The hs_batch handle a fused PPO rollout (hs_rollout) may step, or None: the fp64 Newton
         engine with the device reward and on-device reset noise (graph_safe), one stream group and
-        auto-reset on.  None with a termination condition: a fused launch is bounded by the shortest possible
-        episode, which a state-dependent end makes unknowable, so the trainer takes its per-step path."""
+        auto-reset on.  None with a termination condition that is not fused-capable (a user-registered predicate,
+        or a built-in without ``"fused": True``): a fused launch is bounded by the shortest possible episode, which
+        a state-dependent end makes unknowable, so the trainer takes its per-step path."""
         b = self.batch
-        if (not self.graph_safe or self._program is not None or self._termination is not None
+        if (not self.graph_safe or self._program is not None
+                or (self._termination is not None and not self._termination_fused)
                 or b.precision != "fp64" or not b.cfg.autoreset
                 or len(b._groups) != 1
                 or int(self.model.field("opt_solver")[0]) != 0):

@@ -15,7 +15,8 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KNAME = "step_kernel_queue<double, 27, false, true, false>"   # <T, NV, PGS, ROLL, EVAL>: the fused rollout
+# <T, NV, PGS, ROLL, EVAL, NORM, TERM>: the fused rollout
+KNAME = "step_kernel_queue<double, 27, false, true, false, false, false>"
 
 
 def _rows(src, sub):

@@ -14,7 +14,9 @@ STATS_STEPS = 3
 
 
 def is_step(name):
-    return "step_kernel_queue<double, 27, false, false, false>" in name   # <T, NV, PGS, ROLL, EVAL>: the per-step one
+    # <T, NV, PGS, ROLL, EVAL, NORM, TERM>: the per-step one (recordings from before NORM / TERM end after EVAL)
+    return ("step_kernel_queue<double, 27, false, false, false>" in name
+            or "step_kernel_queue<double, 27, false, false, false, false, false>" in name)
 
 
 def load(src, sub, timed):

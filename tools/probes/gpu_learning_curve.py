@@ -3,7 +3,9 @@ is judged by the stand reward rising).  bench.py's train config: 4096 envs, n_st
 batch 32768, 4 epochs, lr 3e-4, MLP[256,256] ReLU (batch and epochs overridable).
 python tools/probes/gpu_learning_curve.py [iters] [stand|kneeling] [fp32|fp64] [seed] [batch] [epochs] [stagger] [lr] [target_kl] [termination]
 termination: a TERMINATION_FUNCTIONS name ("fallen", "lost_balance"; default none) with grace_steps 1: episodes then end
-at the fall, and the rollouts are collected on the graph-captured per-step path instead of the fused launches.
+at the fall, and the rollouts are collected on the graph-captured per-step path instead of the fused launches;
+"fallen:fused" / "lost_balance:fused" sets "fused": True, which keeps the fused launches (profiles/termination_fused.md).
+The last line printed is the run's ms per iteration and env steps/s.
 target_kl > 0: SB3's KL early stop; every printed row then carries that iteration's approx_kl, clip_fraction
 and the epochs entered before the stop (n_updates grows by one per epoch entered).
 stagger = 1: spread the envs' episode clocks over the episode after the first reset (env i starts
@@ -29,7 +31,10 @@ def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epoch
          termination=None):
     cfg = {"model_path": XML, "duration": 10.0, "reward_config": {"type": reward}, "frame_skip": 3}
     if termination:
-        cfg["termination"] = {"type": termination, "grace_steps": 1}
+        name, _, opt = termination.partition(":")
+        cfg["termination"] = {"type": name, "grace_steps": 1}
+        if opt == "fused":
+            cfg["termination"]["fused"] = True
     env = HumanoidVecEnv(cfg, n_envs=4096, model=HsModel(XML), seed=seed, precision=precision)
     ppo = PPO(env, n_steps=32, batch_size=batch, n_epochs=epochs, learning_rate=lr, seed=seed,
               target_kl=target_kl if target_kl > 0 else None,
@@ -55,6 +60,9 @@ def main(iters=400, reward="stand", precision="fp32", seed=0, batch=32768, epoch
                   f"log_std {float(ppo.policy.log_std.detach().mean()):.3f}  approx_kl {st['approx_kl']:.4f}  "
                   f"clip_fraction {st['clip_fraction']:.3f}  epochs {ppo.n_updates - n_before}/{epochs}  fused {ppo._fused_rollout_args() is not None}  "
                   f"{time.perf_counter() - t0:6.1f}s", flush=True)
+    wall = time.perf_counter() - t0
+    print(f"{iters} iterations in {wall:.2f} s: {wall / iters * 1e3:.2f} ms per iteration, "
+          f"{ppo.num_timesteps / wall / 1e6:.3f} M env steps/s", flush=True)
     env.close()
     return rows
 
