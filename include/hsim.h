@@ -574,6 +574,47 @@ int hs_reward_program_batch(hs_batch* b, const hs_reward_program* prog, const do
 int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* prog, const double* params,
                     void* stream);
 
+/* Named reward components <- info['reward_components'] (custom_env.py:134-140, :217): a reward function may
+ * return a dict of name -> term (with the key "total", the reward) instead of one value.  Its program then holds
+ * one `out` instruction per entry, (RP_OUT, 0, a = slot, b = component index, 0), anywhere before the result, and
+ * is created with n_outputs = the number of entries, at most: */
+#define HS_RP_MAX_OUTPUTS 16
+/* hs_reward_program_create_components validates as hs_reward_program_create does (which means n_outputs = 0), and
+ * refuses n_outputs outside [0, 16], an `out` whose index is outside [0, n_outputs) (so any `out` of a program
+ * created with 0), a component written twice, one never written, and a source slot read before it is written.
+ * hs_reward_program_outputs: the count a program was created with.
+ *
+ * Component rows are COMPONENT-MAJOR, [n_outputs][n] -- component c of env e at c * n + e -- in the call's
+ * precision: every lane of a wave executes the same `out`, so one `out` is one store of 64 consecutive values
+ * (env-major rows would be strided by n_outputs).  With comp_out NULL (or no rows bound, below) an `out` does
+ * nothing, so the same program runs anywhere.  comp_out non-NULL with a program without outputs is refused.
+ * hs_reward_program_eval_host_components: comp_out [n_outputs][n] host doubles.
+ * hs_reward_program_batch_components: comp_out [n_outputs][N] of the batch precision (device); out as before.
+ *
+ * hs_set_reward_components binds the rows hs_step_program (and its outcome launch) fills, like the termination
+ * state a call of its own (hs_buffers is unchanged).  All four are device memory, caller-owned, and must outlive
+ * the binding: comp, comp_total, terminal_comp_total [n_outputs][N] of the batch precision, comp_episode [N]
+ * int32.  n_outputs = 0 or NULL pointers clear the binding.  Binding sets every comp_episode tag to -1 (no
+ * episode; synchronous).  With rows bound, launch 2 of hs_step_program also writes, for every env:
+ *   comp[c]                the step's value of component c, or 0 when the env is truncated, exactly as the reward is;
+ *   comp_total[c]          the episode's running sum, prev + value rounded in the batch precision, where prev reads
+ *                          as 0 when comp_episode differs from the env's episode number (the grace counter's idiom:
+ *                          every reset clears the sums without the reset kernels knowing); then comp_episode = episode;
+ *   terminal_comp_total[c] the sums of the envs that are done this step, beside terminal_total_reward.
+ * A program whose n_outputs differs from the bound count is refused (-1, both numbers in hs_last_error) BEFORE
+ * the step is launched.  With no rows bound hs_step_program is what it was.  A termination predicate has no
+ * outputs: hs_set_termination*, hs_termination_eval_host refuse a program created with n_outputs > 0.  The
+ * fused launches evaluate no program, so they fill no component rows. */
+int hs_reward_program_create_components(const hs_model* m, const int32_t* code, int n_instr, const double* consts,
+                                        int n_consts, int n_params, int n_outputs, hs_reward_program** prog);
+int hs_reward_program_outputs(const hs_reward_program* prog, int* n_outputs);
+int hs_reward_program_eval_host_components(const hs_reward_program* prog, const double* params, int n,
+                                           const hs_reward_fields* fields, double* out, double* comp_out);
+int hs_reward_program_batch_components(hs_batch* b, const hs_reward_program* prog, const double* params, void* out,
+                                       void* comp_out, void* stream);
+int hs_set_reward_components(hs_batch* b, int n_outputs, void* comp, void* comp_total, int32_t* comp_episode,
+                             void* terminal_comp_total);
+
 /* Termination conditions <- the fall conditions custom_env.py:167-200 holds commented out (`height < 0.8` held
  * for a grace period, custom_env.py:169-180 without its reward scaling; `height < 0.8` or |roll|, |pitch| > 45
  * degrees, custom_env.py:183-200) and Gymnasium Humanoid's terminate_when_unhealthy: an episode that ends on a

@@ -42,7 +42,9 @@ def __getattr__(name):
         from . import render
         return getattr(render, name)
     if name in ("register_device_reward", "device_reward_program", "DeviceReward", "TracedProgram", "CompiledProgram",
-                "stand_program", "kneeling_program", "walk_program", "register_device_termination",
+                "stand_program", "kneeling_program", "walk_program", "stand_components_program",
+                "kneeling_components_program", "walk_components_program", "components_reward",
+                "register_device_termination",
                 "device_termination", "DeviceTermination", "TERMINATION_FUNCTIONS",
                 "termination_fused_from_config", "builtin_termination_eval_host"):
         from . import reward_program

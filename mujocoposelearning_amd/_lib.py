@@ -89,6 +89,7 @@ REWARD_FIELD_MEMBER = {n: ("subtree_com0" if n == "subtree_com" else n)
                        for n in ("qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel", "subtree_com",
                                  "cfrc_ext", "subtree_linvel")}
 HS_RP_MAX_INSTR, HS_RP_MAX_SLOTS, HS_RP_MAX_CONSTS, HS_RP_MAX_PARAMS = 4096, 64, 256, 32
+HS_RP_MAX_OUTPUTS = 16
 
 
 class hs_batch_info(C.Structure):
@@ -171,6 +172,11 @@ def lib():
         "hs_reward_program_eval": (i, [vp, i, vp, i, vp, vp, vp]),
         "hs_reward_program_batch": (i, [vp, vp, vp, vp, vp]),
         "hs_step_program": (i, [vp, vp, vp, vp, vp]),
+        "hs_reward_program_create_components": (i, [vp, vp, i, vp, i, i, i, vp]),
+        "hs_reward_program_outputs": (i, [vp, vp]),
+        "hs_reward_program_eval_host_components": (i, [vp, vp, i, vp, vp, vp]),
+        "hs_reward_program_batch_components": (i, [vp, vp, vp, vp, vp, vp]),
+        "hs_set_reward_components": (i, [vp, i, vp, vp, vp, vp]),
         "hs_set_termination": (i, [vp, vp, vp, i]),
         "hs_set_termination_builtin": (i, [vp, vp, vp, i, i, C.c_double, C.c_double]),
         "hs_termination_builtin_eval_host": (i, [i, C.c_double, C.c_double, i, vp, i, vp]),
@@ -237,7 +243,10 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_reward_program_create", "hs_reward_program_destroy", "hs_reward_program_info",
             "hs_reward_program_eval_host", "hs_reward_program_eval", "hs_reward_program_batch", "hs_step_program",
             "hs_set_termination", "hs_apply_termination", "hs_termination_state", "hs_termination_eval_host",
-            "hs_set_termination_builtin", "hs_termination_builtin_eval_host")
+            "hs_set_termination_builtin", "hs_termination_builtin_eval_host",
+            "hs_reward_program_create_components", "hs_reward_program_outputs",
+            "hs_reward_program_eval_host_components", "hs_reward_program_batch_components",
+            "hs_set_reward_components")
 
 
 class HsimError(RuntimeError):

@@ -377,8 +377,65 @@ class HsBatch:
             raise NotImplementedError("step_program: one stream group only")
         a = torch.as_tensor(actions, device=self.device).to(torch.float32).contiguous()
         assert a.shape == (self.n, self.model.nu), a.shape
+        if program.outputs and self.__dict__.get("_comp") is None:
+            self.bind_reward_components(program.outputs)
         check(lib().hs_step_program(self._h, a.data_ptr(), program.handle, program.params(params), self.stream))
         return self.t["obs"], self.t["reward"], self.t["terminated"], self.t["truncated"]
+
+    # -- named reward components (hs_set_reward_components) -----------------------------------
+    def bind_reward_components(self, names):
+        """Allocate and bind the component rows of a program reward with the components ``names`` (the
+        program's ``outputs``): ``reward_components``, ``total_reward_components`` and
+        ``terminal_total_reward_components``, [C, N] tensors of the batch's dtype, component-major (one
+        component is one contiguous row: the kernel's store of a component is coalesced), and the sums' [N] int32
+        episode tag.  ``step_program`` does this once, at the first step with such a program; from then on a
+        program with another number of outputs is refused before the step.  ``names`` empty: unbind."""
+        torch = _torch()
+        if len(self._groups) != 1:
+            raise NotImplementedError("reward components: one stream group only")
+        names = tuple(names)
+        if not names:
+            check(lib().hs_set_reward_components(self._h, 0, None, None, None, None))
+            self._comp = None
+            return
+        c, n = len(names), self.n
+        z = lambda *s, dt=self.dtype: torch.zeros(*s, dtype=dt, device=self.device)  # noqa: E731
+        comp = dict(names=names, step=z(c, n), total=z(c, n), terminal=z(c, n), episode=z(n, dt=torch.int32))
+        torch.cuda.synchronize(self.device)
+        check(lib().hs_set_reward_components(self._h, c, comp["step"].data_ptr(), comp["total"].data_ptr(),
+                                             comp["episode"].data_ptr(), comp["terminal"].data_ptr()))
+        self._comp = comp
+
+    def _comp_view(self, key):
+        comp = self.__dict__.get("_comp")
+        if comp is None:
+            raise AttributeError(f"{key}: no component rows are bound (step_program with a program whose function "
+                                 "returns a dict binds them)")
+        return comp[key]
+
+    @property
+    def reward_component_names(self):
+        """The names of the bound component rows, in row order; () when none are bound."""
+        comp = self.__dict__.get("_comp")
+        return comp["names"] if comp is not None else ()
+
+    @property
+    def reward_components(self):
+        """[C, N] device tensor: the last ``step_program``'s value of every component (0 for a truncated env)."""
+        return self._comp_view("step")
+
+    @property
+    def total_reward_components(self):
+        """[C, N] device tensor: every component's running sum over the env's current episode, as of the last
+        ``step_program`` (for an env that just auto-reset: the finished episode's; read them together with the
+        episode tag's meaning in include/hsim.h -- the next step restarts them)."""
+        return self._comp_view("total")
+
+    @property
+    def terminal_total_reward_components(self):
+        """[C, N] device tensor: the episode sums of the envs that finished in the last ``step_program``, beside
+        ``terminal_total_reward`` (other envs' columns keep what an earlier end left)."""
+        return self._comp_view("terminal")
 
     # -- termination conditions (hs_set_termination) -----------------------------------------
     def set_termination(self, condition=None, params=None, grace_steps=1, registry=None, fused=False):
@@ -514,7 +571,7 @@ class HsBatch:
     _HOST_COLS = ("reward", "terminated", "truncated", "total_reward", "step_count", "terminal_step_count",
                   "terminal_total_reward")
 
-    def host_outputs(self, ncols=3, warnings=False):
+    def host_outputs(self, ncols=3, warnings=False, components=False):
         """One step's outputs on the host in ONE device-to-host copy: the obs and the first ``ncols``
         of (reward, terminated, truncated, total_reward, step_count, terminal_step_count,
         terminal_total_reward), packed on the device into one float64 buffer, copied into pinned
@@ -522,11 +579,16 @@ class HsBatch:
         float64), views of a fresh pinned block (torch's caching host allocator recycles it once
         both are dropped).  ``warnings=True`` also packs the warning counters summed over the envs
         (HS_NWARN values, cumulative since the batch was created) and returns them third, as int64.
-        One native pack launch (hs_pack_outputs) for a single-group batch."""
+        One native pack launch (hs_pack_outputs) for a single-group batch.  ``components=True`` appends one more
+        result: with component rows bound, a [2, C, N] float64 block -- ``reward_components`` and
+        ``terminal_total_reward_components`` -- that joins the same copy (two device copies behind the pack);
+        with none bound, None, and nothing more is copied."""
         torch = _torch()
         N, D = self.n, self.obs_dim
         nwr = N * _lib.HS_NWARN if warnings else 0          # per-env warning rows (summed on the host)
-        size = N * D + ncols * N + nwr
+        comp = self.__dict__.get("_comp") if components else None
+        ncomp = 2 * len(comp["names"]) * N if comp is not None else 0
+        size = N * D + ncols * N + nwr + ncomp
         dev = self.__dict__.get("_pack_dev")
         if dev is None or dev.numel() != size:
             dev = self._pack_dev = torch.empty(size, dtype=torch.float64, device=self.device)
@@ -539,15 +601,22 @@ class HsBatch:
             for k in range(ncols):
                 cols[k].copy_(self.t[self._HOST_COLS[k]])
             if nwr:
-                dev[N * D + ncols * N:].view(_lib.HS_NWARN, N).copy_(self.t["warning"].t())
+                dev[N * D + ncols * N:size - ncomp].view(_lib.HS_NWARN, N).copy_(self.t["warning"].t())
+        if ncomp:     # the component rows ride in the same copy, behind everything else
+            tail = dev[size - ncomp:].view(2, len(comp["names"]), N)
+            tail[0].copy_(comp["step"])
+            tail[1].copy_(comp["terminal"])
         host = torch.empty(size, dtype=torch.float64, pin_memory=True)
         host.copy_(dev, non_blocking=True)
         st.synchronize()
         a = host.numpy()
         obs, c = a[:N * D].reshape(N, D), a[N * D:N * D + ncols * N].reshape(ncols, N)
-        if not nwr:
-            return obs, c
-        return obs, c, a[N * D + ncols * N:].reshape(_lib.HS_NWARN, N).sum(1).astype(np.int64)
+        res = (obs, c)
+        if nwr:
+            res += (a[N * D + ncols * N:size - ncomp].reshape(_lib.HS_NWARN, N).sum(1).astype(np.int64),)
+        if components:
+            res += (a[size - ncomp:].reshape(2, -1, N) if ncomp else None,)
+        return res
 
     def tape_aborts(self):
         """Tape launches replayed step by step because an env overflowed the resident tier."""
@@ -555,12 +624,13 @@ class HsBatch:
         check(lib().hs_tape_aborts(self._groups[0][0], C.byref(v)))
         return int(v.value)
 
-    def compute_reward(self, name, params=None, registry=None):
+    def compute_reward(self, name, params=None, registry=None, components=False):
         """``REWARD_FUNCTIONS[name](data_i, params)`` for every env's current state on the device
         (``hs_reward``: the step kernel's reward code on the batch's own buffers; custom_env.py:263-271
         ``_compute_reward``; ``self.reward`` stays the last step's reward buffer).
         Needs the aux row and the data.ctrl copy (``configure(aux=True, ctrl=True)``, the default).
-        Returns an [N] tensor of the batch precision."""
+        Returns an [N] tensor of the batch precision.  ``components=True`` (a reward program only): (reward [N],
+        components [C, N]), the rows in the order of the program's ``outputs`` ([0, N] for a scalar function)."""
         from .reward_functions import device_reward_id
         torch = _torch()
         rid = device_reward_id(name, registry)
@@ -571,8 +641,16 @@ class HsBatch:
             if len(self._groups) != 1:
                 raise NotImplementedError("compute_reward with a reward program: one stream group only")
             out = torch.empty(self.n, dtype=self.dtype, device=self.device)
-            check(lib().hs_reward_program_batch(self._h, prog.handle, prog.params(params), out.data_ptr(), self.stream))
-            return out
+            if not components:
+                check(lib().hs_reward_program_batch(self._h, prog.handle, prog.params(params), out.data_ptr(),
+                                                    self.stream))
+                return out
+            comp = torch.empty(len(prog.outputs), self.n, dtype=self.dtype, device=self.device)
+            check(lib().hs_reward_program_batch_components(self._h, prog.handle, prog.params(params), out.data_ptr(),
+                                                           comp.data_ptr() if comp.numel() else None, self.stream))
+            return out, comp
+        if components:
+            raise _lib.HsimError(f"reward {name!r} is a built-in id: only a reward program has named components")
         kn = None
         if params is not None:
             p = {**dict(zip(KNEEL_KEYS, KNEEL_DEFAULTS)), **params}

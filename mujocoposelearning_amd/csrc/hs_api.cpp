@@ -22,7 +22,8 @@
 static_assert(HS_KINDIM == hs::KINDIM, "include/hsim.h HS_KINDIM is the kernels' record size");
 static_assert(HS_CAM_BODY == hs::CAM_BODY && HS_CAM_COM == hs::CAM_COM, "include/hsim.h camera modes");
 static_assert(HS_RP_MAX_INSTR == hs::RP_MAX_INSTR && HS_RP_MAX_SLOTS == hs::RP_MAX_SLOTS &&
-                  HS_RP_MAX_CONSTS == hs::RP_MAX_CONSTS && HS_RP_MAX_PARAMS == hs::RP_MAX_PARAMS,
+                  HS_RP_MAX_CONSTS == hs::RP_MAX_CONSTS && HS_RP_MAX_PARAMS == hs::RP_MAX_PARAMS &&
+                  HS_RP_MAX_OUTPUTS == hs::RP_MAX_OUTPUTS,
               "include/hsim.h reward program limits");
 static_assert(sizeof(hs_reward_fields) == hs::RP_NFIELDS * sizeof(void*), "hs_reward_fields: one pointer per field");
 
@@ -75,6 +76,13 @@ struct hs_batch {
   int term_kind = 0;
   double term_min_height = 0.0, term_max_roll_pitch = 0.0;
   int32_t* mid_count = nullptr;
+  // hs_set_reward_components: the caller's component rows [comp_n][n] (batch dtype) and the sums' episode tag [n];
+  // comp_n = 0: none bound
+  int comp_n = 0;
+  void* comp = nullptr;
+  void* comp_total = nullptr;
+  int32_t* comp_episode = nullptr;
+  void* term_comp_total = nullptr;
 };
 
 // a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on
@@ -1378,8 +1386,15 @@ int outcome_launch(hs_batch* b, const hs_reward_program* p, const double* params
     a.term_step_count = b->buf.terminal_step_count;
     a.term_total_reward = (T*)b->buf.terminal_total_reward;
     a.done = b->prog_done;
+    a.episode = (const int32_t*)b->buf.episode;
+    if (p && b->comp_n > 0) {   // (the counts agree: step_outcome_reset checks before the step)
+      a.comp = (T*)b->comp;
+      a.comp_total = (T*)b->comp_total;
+      a.comp_episode = b->comp_episode;
+      a.term_comp_total = (T*)b->term_comp_total;
+      a.n_outputs = b->comp_n;
+    }
     if (t) {
-      a.episode = (const int32_t*)b->buf.episode;
       a.grace_count = b->grace_count;
       a.grace_episode = b->grace_episode;
       a.early = b->early;
@@ -1394,6 +1409,10 @@ int step_outcome_reset(hs_batch* b, const float* actions, const hs_reward_progra
                        void* stream) {
   // the predicate's needs once more, in case the config changed after hs_set_termination: before any launch
   if (b->term_prog && rp_check_batch("hs_step", b, b->term_prog, b->term_params, true)) return -1;
+  // component rows bound: the program must write exactly that many, or a row would stay stale (or be overrun)
+  if (p && b->comp_n > 0 && p->info.n_outputs != b->comp_n)
+    return fail("hs_step_program: the program has " + std::to_string(p->info.n_outputs) + " outputs, the batch has " +
+                std::to_string(b->comp_n) + " component rows bound (hs_set_reward_components)");
   DeviceGuard g(b->device);
   if ((p && !rp_resident(const_cast<hs_reward_program*>(p), b->device))) return -1;
   // 1. the env step without auto-reset -- and, for a reward program, without a reward: the program and the
@@ -1418,12 +1437,23 @@ extern "C" {
 
 int hs_reward_program_create(const hs_model* m, const int32_t* code, int n_instr, const double* consts, int n_consts,
                              int n_params, hs_reward_program** prog) {
+  return hs_reward_program_create_components(m, code, n_instr, consts, n_consts, n_params, 0, prog);
+}
+
+int hs_reward_program_outputs(const hs_reward_program* p, int* n_outputs) {
+  if (!p || !n_outputs) return fail("hs_reward_program_outputs: null argument");
+  *n_outputs = p->info.n_outputs;
+  return 0;
+}
+
+int hs_reward_program_create_components(const hs_model* m, const int32_t* code, int n_instr, const double* consts,
+                                        int n_consts, int n_params, int n_outputs, hs_reward_program** prog) {
   if (!m || !prog) return fail("hs_reward_program_create: null argument");
   *prog = nullptr;
   const hs::HostModel& h = m->host;
   const hs::RpDims dims{h.nq, h.nv, h.nu, h.nbody};
   hs::RpInfo info;
-  const std::string why = hs::rp_validate(dims, code, n_instr, consts, n_consts, n_params, &info);
+  const std::string why = hs::rp_validate(dims, code, n_instr, consts, n_consts, n_params, n_outputs, &info);
   if (!why.empty()) return fail("hs_reward_program_create: " + why);
   auto* p = new hs_reward_program();
   p->dims = dims;
@@ -1460,15 +1490,22 @@ int hs_reward_program_info(const hs_reward_program* p, int* n_instr, int* n_slot
 
 int hs_reward_program_eval_host(const hs_reward_program* p, const double* params, int n, const hs_reward_fields* f,
                                 double* out) {
+  return hs_reward_program_eval_host_components(p, params, n, f, out, nullptr);
+}
+
+int hs_reward_program_eval_host_components(const hs_reward_program* p, const double* params, int n,
+                                           const hs_reward_fields* f, double* out, double* comp_out) {
   if (!p || !f) return fail("hs_reward_program_eval_host: null argument");
   if (n < 0) return fail("hs_reward_program_eval_host: negative n");
+  if (comp_out && p->info.n_outputs == 0)
+    return fail("hs_reward_program_eval_host_components: the program has no outputs, comp_out must be NULL");
   if (n == 0) return 0;
   if (!out || (p->n_params > 0 && !params)) return fail("hs_reward_program_eval_host: null out or params");
   const double* const* fp = reinterpret_cast<const double* const*>(f);
   for (int k = 0; k < hs::RP_NFIELDS; k++)
     if ((p->info.fields & (1u << k)) && !fp[k])
       return fail(std::string("hs_reward_program_eval_host: the program reads ") + kRpFieldNames[k] + ", which is NULL");
-  hs::rp_eval_host(p->dims, p->code.data(), (int)(p->code.size() / 5), p->consts.data(), params, n, fp, out);
+  hs::rp_eval_host(p->dims, p->code.data(), (int)(p->code.size() / 5), p->consts.data(), params, n, fp, out, comp_out);
   return 0;
 }
 
@@ -1502,8 +1539,45 @@ int hs_reward_program_eval(const hs_reward_program* p, int precision, const doub
 }
 
 int hs_reward_program_batch(hs_batch* b, const hs_reward_program* p, const double* params, void* out, void* stream) {
+  return hs_reward_program_batch_components(b, p, params, out, nullptr, stream);
+}
+
+int hs_set_reward_components(hs_batch* b, int n_outputs, void* comp, void* comp_total, int32_t* comp_episode,
+                             void* terminal_comp_total) {
+  if (!b) return fail("hs_set_reward_components: null batch");
+  if (n_outputs < 0 || n_outputs > HS_RP_MAX_OUTPUTS)
+    return fail("hs_set_reward_components: n_outputs " + std::to_string(n_outputs) + " outside [0, " +
+                std::to_string(HS_RP_MAX_OUTPUTS) + "]");
+  const bool any = comp || comp_total || comp_episode || terminal_comp_total;
+  const bool all = comp && comp_total && comp_episode && terminal_comp_total;
+  if (n_outputs > 0 && any && !all)
+    return fail("hs_set_reward_components: pass all four buffers, or none (NULL) to clear the binding");
+  if (n_outputs == 0 || !all) {   // clear
+    b->comp_n = 0;
+    b->comp = b->comp_total = b->term_comp_total = nullptr;
+    b->comp_episode = nullptr;
+    return 0;
+  }
+  // no sum belongs to any episode yet: the tag -1 is no episode number (as hs_set_termination's)
+  DeviceGuard g(b->device);
+  if (!hip_ok(hipDeviceSynchronize(), "hs_set_reward_components") ||
+      !hip_ok(hipMemset(comp_episode, 0xFF, (size_t)b->n * sizeof(int32_t)), "hs_set_reward_components") ||
+      !hip_ok(hipDeviceSynchronize(), "hs_set_reward_components"))
+    return -1;
+  b->comp_n = n_outputs;
+  b->comp = comp;
+  b->comp_total = comp_total;
+  b->comp_episode = comp_episode;
+  b->term_comp_total = terminal_comp_total;
+  return 0;
+}
+
+int hs_reward_program_batch_components(hs_batch* b, const hs_reward_program* p, const double* params, void* out,
+                                       void* comp_out, void* stream) {
   if (!out) return fail("hs_reward_program_batch: null argument");
   if (rp_check_batch("hs_reward_program_batch", b, p, params, false)) return -1;
+  if (comp_out && p->info.n_outputs == 0)
+    return fail("hs_reward_program_batch_components: the program has no outputs, comp_out must be NULL");
   DeviceGuard g(b->device);
   const auto* d = rp_resident(const_cast<hs_reward_program*>(p), b->device);
   if (!d) return -1;
@@ -1513,6 +1587,8 @@ int hs_reward_program_batch(hs_batch* b, const hs_reward_program* p, const doubl
     hs::RpArgs<T> a = rp_args<T>(p, d, params, b->n);
     rp_batch_fields<T>(b, a);
     a.out = (T*)out;
+    a.comp = (T*)comp_out;
+    a.n_outputs = p->info.n_outputs;
     return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
   };
   return b->precision == HS_FP64 ? run(0.0) : run(0.0f);
@@ -1524,7 +1600,22 @@ int hs_step_program(hs_batch* b, const float* actions, const hs_reward_program* 
   return step_outcome_reset(b, actions, p, params, stream);
 }
 
+}  // extern "C"
+
+namespace {
+// a predicate is read as one truth value: a program with named outputs is a reward, refused as a condition
+int term_refuse_outputs(const char* who, const hs_reward_program* pred) {
+  if (pred && pred->info.n_outputs > 0)
+    return fail(std::string(who) + ": the program has " + std::to_string(pred->info.n_outputs) +
+                " outputs; a termination predicate has none (it is read as one truth value)");
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
 int hs_set_termination(hs_batch* b, const hs_reward_program* pred, const double* params, int grace_steps) {
+  if (term_refuse_outputs("hs_set_termination", pred)) return -1;
   if (!b) return fail("hs_set_termination: null batch");
   b->term_kind = 0;   // (hs_set_termination_builtin marks the condition fused-capable after this call)
   if (!pred) {   // clear: the buffers stay, the next hs_set_termination starts their counters afresh
@@ -1559,6 +1650,7 @@ static_assert(HS_TERM_FALLEN == hs::TERM_FALLEN && HS_TERM_LOST_BALANCE == hs::T
 int hs_set_termination_builtin(hs_batch* b, const hs_reward_program* pred, const double* params, int grace_steps,
                                int kind, double min_height, double max_roll_pitch) {
   const std::string who = "hs_set_termination_builtin";
+  if (term_refuse_outputs("hs_set_termination_builtin", pred)) return -1;
   if (!b || !pred) return fail(who + ": null batch or predicate");
   if (kind != HS_TERM_FALLEN && kind != HS_TERM_LOST_BALANCE)
     return fail(who + ": kind " + std::to_string(kind) + " is neither HS_TERM_FALLEN (1) nor HS_TERM_LOST_BALANCE (2)");
@@ -1630,6 +1722,7 @@ int hs_apply_termination(hs_batch* b, void* stream) {
 int hs_termination_eval_host(const hs_reward_program* pred, const double* params, int grace_steps, int n,
                              const hs_reward_fields* f, const int32_t* episode, int32_t* count, int32_t* episode_tag,
                              uint8_t* early) {
+  if (term_refuse_outputs("hs_termination_eval_host", pred)) return -1;
   if (!pred || !f) return fail("hs_termination_eval_host: null argument");
   if (n < 0) return fail("hs_termination_eval_host: negative n");
   if (grace_steps < 1) return fail("hs_termination_eval_host: grace_steps must be >= 1");

@@ -10,12 +10,16 @@
  *   height / step_count / truncated / terminated / total_reward: lists (per env, Python scalars;
  *   truncated / terminated of bool)
  *   done_pos: dict env -> row of term_obs (the envs that finished), term_obs: 2-D array or None
- *   returns [dict for env in range(start, stop)], equal to the eager Python construction. */
+ *   returns [dict for env in range(start, stop)], equal to the eager Python construction.
+ * build(..., start, stop, names, comps, ep_comps): a reward with named components (a reward program whose function
+ *   returns a dict).  names: tuple of C str; comps / ep_comps: lists of C lists (per env, Python floats), the
+ *   step's components and the finished episodes' sums.  reward_components is then {name: comps[c][env]}, and a
+ *   finished env also gets episode_reward_components = {name: ep_comps[c][env]}.  Without them (or None): {}. */
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 
 static PyObject *k_height, *k_step_count, *k_truncated, *k_truncation_info, *k_terminated, *k_total_reward,
-    *k_reward_components, *k_terminal_observation, *k_timelimit, *k_reason, *v_timeout;
+    *k_reward_components, *k_episode_reward_components, *k_terminal_observation, *k_timelimit, *k_reason, *v_timeout;
 
 static int set_new(PyObject* d, PyObject* k, PyObject* v) {   /* steals v */
   if (!v) return -1;
@@ -24,9 +28,22 @@ static int set_new(PyObject* d, PyObject* k, PyObject* v) {   /* steals v */
   return rc;
 }
 
+/* {names[c]: cols[c][i]}; names NULL: {} */
+static PyObject* comp_dict(PyObject* names, PyObject* cols, Py_ssize_t i) {
+  PyObject* d = PyDict_New();
+  if (!d || !names) return d;
+  const Py_ssize_t nc = PyTuple_GET_SIZE(names);
+  for (Py_ssize_t c = 0; c < nc; c++)
+    if (PyDict_SetItem(d, PyTuple_GET_ITEM(names, c), PyList_GET_ITEM(PyList_GET_ITEM(cols, c), i)) < 0) {
+      Py_DECREF(d);
+      return NULL;
+    }
+  return d;
+}
+
 static PyObject* build_one(PyObject* h, PyObject* sc, PyObject* tr, PyObject* te, PyObject* tot, PyObject* done_pos,
-                           PyObject* tobs, Py_ssize_t i) {
-  PyObject* d = _PyDict_NewPresized(9);   /* 7 keys, 9 for a finished env: no resize on the way */
+                           PyObject* tobs, PyObject* names, PyObject* comps, PyObject* ep_comps, Py_ssize_t i) {
+  PyObject* d = _PyDict_NewPresized(10);   /* 7 keys, 9 or 10 for a finished env: no resize on the way */
   if (!d) return NULL;
   PyObject* trunc = PyList_GET_ITEM(tr, i);
   PyObject* term = PyList_GET_ITEM(te, i);
@@ -34,7 +51,7 @@ static PyObject* build_one(PyObject* h, PyObject* sc, PyObject* tr, PyObject* te
   PyObject* tinfo = PyDict_New();
   if (!tinfo) goto fail;
   if (is_trunc && PyDict_SetItem(tinfo, k_reason, v_timeout) < 0) { Py_DECREF(tinfo); goto fail; }
-  if (set_new(d, k_reward_components, PyDict_New()) < 0) { Py_DECREF(tinfo); goto fail; }
+  if (set_new(d, k_reward_components, comp_dict(names, comps, i)) < 0) { Py_DECREF(tinfo); goto fail; }
   /* keys in custom_env.py:216-224's order */
   if (PyDict_SetItem(d, k_height, PyList_GET_ITEM(h, i)) < 0 ||
       PyDict_SetItem(d, k_step_count, PyList_GET_ITEM(sc, i)) < 0 ||
@@ -53,6 +70,7 @@ static PyObject* build_one(PyObject* h, PyObject* sc, PyObject* tr, PyObject* te
       if (set_new(d, k_terminal_observation, PyObject_GetItem(tobs, row)) < 0) goto fail;
       PyObject* tl = (is_trunc && !is_term) ? Py_True : Py_False;
       if (PyDict_SetItem(d, k_timelimit, tl) < 0) goto fail;
+      if (names && set_new(d, k_episode_reward_components, comp_dict(names, ep_comps, i)) < 0) goto fail;
     }
   }
   return d;
@@ -62,13 +80,30 @@ fail:
 }
 
 static PyObject* build(PyObject* self, PyObject* args) {
-  PyObject *h, *sc, *tr, *te, *tot, *done_pos, *tobs;
+  PyObject *h, *sc, *tr, *te, *tot, *done_pos, *tobs, *names = NULL, *comps = NULL, *ep_comps = NULL;
   Py_ssize_t start, stop;
   (void)self;
-  if (!PyArg_ParseTuple(args, "O!O!O!O!O!OOnn", &PyList_Type, &h, &PyList_Type, &sc, &PyList_Type, &tr, &PyList_Type,
-                        &te, &PyList_Type, &tot, &done_pos, &tobs, &start, &stop))
+  if (!PyArg_ParseTuple(args, "O!O!O!O!O!OOnn|OOO", &PyList_Type, &h, &PyList_Type, &sc, &PyList_Type, &tr,
+                        &PyList_Type, &te, &PyList_Type, &tot, &done_pos, &tobs, &start, &stop, &names, &comps,
+                        &ep_comps))
     return NULL;
   const Py_ssize_t n = PyList_GET_SIZE(h);
+  if (names == Py_None) names = NULL;
+  if (names) {   /* the component columns: C names, two lists of C per-env lists */
+    if (!PyTuple_Check(names) || !comps || !ep_comps || !PyList_Check(comps) || !PyList_Check(ep_comps) ||
+        PyList_GET_SIZE(comps) != PyTuple_GET_SIZE(names) || PyList_GET_SIZE(ep_comps) != PyTuple_GET_SIZE(names)) {
+      PyErr_SetString(PyExc_ValueError, "_hsinfo.build: names must be a tuple, comps / ep_comps lists of as many columns");
+      return NULL;
+    }
+    for (Py_ssize_t c = 0; c < PyTuple_GET_SIZE(names); c++) {
+      PyObject *a = PyList_GET_ITEM(comps, c), *b = PyList_GET_ITEM(ep_comps, c);
+      if (!PyUnicode_Check(PyTuple_GET_ITEM(names, c)) || !PyList_Check(a) || !PyList_Check(b) ||
+          PyList_GET_SIZE(a) != n || PyList_GET_SIZE(b) != n) {
+        PyErr_SetString(PyExc_ValueError, "_hsinfo.build: component names must be str, component columns lists of one value per env");
+        return NULL;
+      }
+    }
+  }
   if (PyList_GET_SIZE(sc) != n || PyList_GET_SIZE(tr) != n || PyList_GET_SIZE(te) != n || PyList_GET_SIZE(tot) != n) {
     PyErr_SetString(PyExc_ValueError, "_hsinfo.build: column lengths differ");
     return NULL;
@@ -87,7 +122,7 @@ static PyObject* build(PyObject* self, PyObject* args) {
    * young-generation collection, which triples the cost at 4096 envs */
   const int gc_was = PyGC_Disable();
   for (Py_ssize_t i = start; i < stop; i++) {
-    PyObject* d = build_one(h, sc, tr, te, tot, done_pos, tobs, i);
+    PyObject* d = build_one(h, sc, tr, te, tot, done_pos, tobs, names, comps, ep_comps, i);
     if (!d) {
       if (gc_was) PyGC_Enable();
       Py_DECREF(out);
@@ -114,6 +149,7 @@ PyMODINIT_FUNC PyInit__hsinfo(void) {
   INTERN(k_terminated, "terminated");
   INTERN(k_total_reward, "total_reward");
   INTERN(k_reward_components, "reward_components");
+  INTERN(k_episode_reward_components, "episode_reward_components");
   INTERN(k_terminal_observation, "terminal_observation");
   INTERN(k_timelimit, "TimeLimit.truncated");
   INTERN(k_reason, "reason");

@@ -10,6 +10,9 @@
 //   RP_CONST  a = constant index      RP_PARAM  a = parameter index
 //   RP_LOAD   a = field (RP_F_*), b = the flat index within the env's row of that field
 //   RP_RESULT a = the slot holding the reward; exactly one, the last instruction
+//   RP_OUT    a = the slot holding a named component of the reward, b = the component's index; writes no
+//             slot, may stand anywhere before RP_RESULT; a program created with n_outputs components holds
+//             exactly one RP_OUT per index in [0, n_outputs)
 // Comparisons and the logical ops give 1 or 0; RP_WHERE and the logical ops read "not zero" as true.
 #pragma once
 #include <climits>
@@ -27,7 +30,7 @@
 namespace hs {
 
 // the limits (include/hsim.h HS_RP_MAX_*); a program is bounded by its LIVE values, not its length
-constexpr int RP_MAX_INSTR = 4096, RP_MAX_SLOTS = 64, RP_MAX_CONSTS = 256, RP_MAX_PARAMS = 32;
+constexpr int RP_MAX_INSTR = 4096, RP_MAX_SLOTS = 64, RP_MAX_CONSTS = 256, RP_MAX_PARAMS = 32, RP_MAX_OUTPUTS = 16;
 
 enum RpOp : int32_t {
   RP_CONST = 0, RP_PARAM, RP_LOAD,
@@ -35,6 +38,7 @@ enum RpOp : int32_t {
   RP_NEG, RP_ABS, RP_SQRT, RP_EXP, RP_LOG, RP_SIN, RP_COS, RP_TANH, RP_ASIN, RP_ACOS, RP_NOT,          // unary
   RP_WHERE,                                                                                             // ternary
   RP_RESULT,
+  RP_OUT,                                                                                               // a component
   RP_NOPS
 };
 
@@ -71,10 +75,10 @@ inline int rp_field_len(const RpDims& d, int f) {
   return 0;
 }
 
-// slots an op reads (0 for RP_CONST / RP_PARAM / RP_LOAD, whose operands are indices; RP_RESULT reads one)
+// slots an op reads (0 for RP_CONST / RP_PARAM / RP_LOAD, whose operands are indices; RP_RESULT and RP_OUT read one)
 RP_HD inline int rp_arity(int op) {
   if (op >= RP_ADD && op <= RP_OR) return 2;
-  if ((op >= RP_NEG && op <= RP_NOT) || op == RP_RESULT) return 1;
+  if ((op >= RP_NEG && op <= RP_NOT) || op == RP_RESULT || op == RP_OUT) return 1;
   if (op == RP_WHERE) return 3;
   return 0;
 }
@@ -138,12 +142,15 @@ RP_HD inline T rp_op(int op, T a, T b, T c) {
 struct RpInfo {
   int n_slots = 0;        // highest slot written + 1
   unsigned fields = 0;    // bit f set: the program reads field f
+  int n_outputs = 0;      // named components (RP_OUT); 0: the program has the reward alone
 };
 
 // Validate an encoding against the limits and a model's dimensions.  Returns "" and fills `info`, or
 // the reason a program is refused: nothing that fails here is ever uploaded or launched.
+// n_outputs: the components the program is created with -- every index in [0, n_outputs) written by exactly one
+// RP_OUT (so with 0 any RP_OUT is refused).
 inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr, const double* consts,
-                               int n_consts, int n_params, RpInfo* info) {
+                               int n_consts, int n_params, int n_outputs, RpInfo* info) {
   auto at = [](int i) { return " (instruction " + std::to_string(i) + ")"; };
   if (n_instr < 1 || n_instr > RP_MAX_INSTR)
     return "reward program: " + std::to_string(n_instr) + " instructions, the limit is " + std::to_string(RP_MAX_INSTR);
@@ -151,9 +158,13 @@ inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr
     return "reward program: " + std::to_string(n_consts) + " constants, the limit is " + std::to_string(RP_MAX_CONSTS);
   if (n_params < 0 || n_params > RP_MAX_PARAMS)
     return "reward program: " + std::to_string(n_params) + " parameters, the limit is " + std::to_string(RP_MAX_PARAMS);
+  if (n_outputs < 0 || n_outputs > RP_MAX_OUTPUTS)
+    return "reward program: " + std::to_string(n_outputs) + " outputs, the limit is " + std::to_string(RP_MAX_OUTPUTS);
   if (!code || (n_consts > 0 && !consts)) return "reward program: null code or constants";
   bool written[RP_MAX_SLOTS] = {};
+  bool out_written[RP_MAX_OUTPUTS] = {};
   RpInfo r;
+  r.n_outputs = n_outputs;
   for (int i = 0; i < n_instr; i++) {
     const int32_t* in = code + 5 * (size_t)i;
     const int op = in[0], dst = in[1];
@@ -178,20 +189,38 @@ inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr
                std::to_string(in[2]) + " has " + std::to_string(rp_field_len(d, in[2])) + " values)" + at(i);
       r.fields |= 1u << in[2];
     }
-    if (op == RP_RESULT) continue;
+    if (op == RP_OUT) {
+      const int c = in[3];
+      if (c < 0 || c >= n_outputs)
+        return "reward program: output index " + std::to_string(c) + " outside [0, " + std::to_string(n_outputs) +
+               "): the program has " + std::to_string(n_outputs) + " outputs" + at(i);
+      if (out_written[c]) return "reward program: output " + std::to_string(c) + " is written twice" + at(i);
+      out_written[c] = true;
+    }
+    if (op == RP_RESULT || op == RP_OUT) continue;
     if (dst < 0 || dst >= RP_MAX_SLOTS)
       return "reward program: slot " + std::to_string(dst) + " out of range [0, " + std::to_string(RP_MAX_SLOTS) + ")" + at(i);
     written[dst] = true;
     if (dst + 1 > r.n_slots) r.n_slots = dst + 1;
   }
+  for (int c = 0; c < n_outputs; c++)
+    if (!out_written[c]) return "reward program: output " + std::to_string(c) + " is never written (no out instruction)";
   if (info) *info = r;
   return "";
 }
 
+// a program with the reward alone (n_outputs = 0)
+inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr, const double* consts,
+                               int n_consts, int n_params, RpInfo* info) {
+  return rp_validate(d, code, n_instr, consts, n_consts, n_params, 0, info);
+}
+
 // The host interpreter: a VALIDATED program on n states in double.  field[f]: [n][rp_field_len(d, f)]
-// contiguous doubles, or NULL for a field the program does not read (checked by the caller).
+// contiguous doubles, or NULL for a field the program does not read (checked by the caller).  comp_out: the
+// component sink, component-major [n_outputs][n] (component c of state e at c * n + e), or NULL: RP_OUT is then
+// a no-op.
 inline void rp_eval_host(const RpDims& d, const int32_t* code, int n_instr, const double* consts, const double* params,
-                         int n, const double* const* field, double* out) {
+                         int n, const double* const* field, double* out, double* comp_out = nullptr) {
   int len[RP_NFIELDS];
   for (int f = 0; f < RP_NFIELDS; f++) len[f] = rp_field_len(d, f);
   for (int e = 0; e < n; e++) {
@@ -205,7 +234,10 @@ inline void rp_eval_host(const RpDims& d, const int32_t* code, int n_instr, cons
       else if (op == RP_PARAM) r = params[in[2]];
       else if (op == RP_LOAD) r = field[in[2]][(size_t)e * len[in[2]] + in[3]];
       else if (op == RP_RESULT) { res = v[in[2]]; break; }
-      else {
+      else if (op == RP_OUT) {
+        if (comp_out) comp_out[(size_t)in[3] * n + e] = v[in[2]];
+        continue;
+      } else {
         const int ar = rp_arity(op);
         r = rp_op<double>(op, v[in[2]], ar > 1 ? v[in[3]] : 0.0, ar > 2 ? v[in[4]] : 0.0);
       }
@@ -272,6 +304,15 @@ struct RpArgs {
   const T* field[RP_NFIELDS];
   long long ld[RP_NFIELDS];
   T* out;
+  // the component rows, component-major [n_outputs][n] (one RP_OUT is one coalesced store of the wave), or NULL:
+  // RP_OUT is then a no-op.  Outcome mode: the step's values (0 for a truncated env), with comp_total the
+  // episode's running sums, comp_episode [n] the episode number the sums belong to (they read as 0 when it
+  // differs from episode[env]: the grace counter's idiom) and term_comp_total the sums of the envs done this step
+  T* comp;
+  T* comp_total;
+  int32_t* comp_episode;
+  T* term_comp_total;
+  int n_outputs;
   // outcome mode: the batch's rows
   T* reward;
   T* total_reward;
@@ -284,7 +325,8 @@ struct RpArgs {
   int32_t* term_step_count;
   T* term_total_reward;
   uint8_t* done;
-  // with a predicate: the grace counter and its episode tag, the env's episode number, the early byte
+  // the env's episode number (with a predicate or component rows); with a predicate: the grace counter and its
+  // episode tag, the early byte
   const int32_t* episode;
   int32_t* grace_count;
   int32_t* grace_episode;

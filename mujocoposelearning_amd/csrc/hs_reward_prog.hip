@@ -14,6 +14,8 @@
 // values per env against the step's thousands); left as they are.
 // A reward program and a predicate run through the same interpreter (rp_run), one after the other over
 // the same slots: the LDS is sized to the larger of the two.
+// A program's named components (RP_OUT) leave through component-major rows [C][n]: each RP_OUT is one
+// coalesced store per wave (env-major rows would be strided by C).  See RpSink.
 #include <hip/hip_runtime.h>
 
 #include "hs_reward_prog.h"
@@ -22,18 +24,46 @@ namespace hs {
 namespace {
 
 constexpr int RP_BLOCK = 64;   // one wave
-
 // The interpreter loop: program `c` on env `e`'s fields, the lane's slot column at `v`.
 // One dependent chain per wave (fetch, slot reads, op or gather, slot write), and 4096 envs are 64 waves:
 // the kernel is latency-bound, mostly on the gathers.  Fetching the next instruction's words ahead by
 // hand changed nothing (profiles/reward_programs.md).
+//
+// RP_OUT goes to the lane's sink.  The rows are component-major, so one RP_OUT is one store of 64 consecutive
+// values per wave.  `comp` NULL (a kernel argument: the branch is wave-uniform) makes RP_OUT a no-op; a lane
+// past the end (`live` false) stores nothing.  In outcome mode the value is 0 for a truncated env, as the
+// reward is, and joins the episode's running sum (prev + value, rounded in T; prev reads as 0 when the sums
+// belong to another episode).
 template <typename T>
-__device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long long e, T* v) {
+struct RpSink {
+  T* comp = nullptr;       // [C][n] this evaluation's values
+  T* total = nullptr;      // [C][n] the episode's sums (outcome mode), or NULL
+  long long n = 0, env = 0;
+  bool live = false, zero = false, fresh = false;
+};
+
+template <typename T>
+__device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long long e, T* v, const RpSink<T>& s) {
   T res = T(0);
   for (int i = 0; i < c.n_instr; i++) {
     const int32_t* in = c.code + 5 * (size_t)i;
     const int op = in[0], dst = in[1], x = in[2], y = in[3], z = in[4];
     T r;
+    // (RP_OUT is tested ahead of the chain: one more scalar compare per instruction, +0.5 µs on the 167
+    // instructions of stand_program.  Folding it into one `op >= RP_RESULT` test with RP_RESULT, so that the
+    // arithmetic ops pass no more compares than before, measured 4.5 µs SLOWER: profiles/reward_programs.md)
+    if (op == RP_OUT) {
+      if (s.comp && s.live) {
+        const long long at = (long long)y * s.n + s.env;
+        const T val = s.zero ? T(0) : v[x * RP_BLOCK];
+        s.comp[at] = val;
+        if (s.total) {
+          const T prev = s.fresh ? T(0) : s.total[at];
+          s.total[at] = prev + val;
+        }
+      }
+      continue;
+    }
     if (op == RP_CONST) {
       r = (T)c.consts[x];
     } else if (op == RP_PARAM) {
@@ -64,14 +94,29 @@ __global__ __launch_bounds__(RP_BLOCK) void reward_program_kernel(RpArgs<T> a) {
   const bool ok = env < a.n;
   const long long e = ok ? env : a.n - 1;   // a lane past the end mirrors the last env and writes nothing
   const bool has_prog = a.prog.n_instr > 0, has_pred = a.pred.n_instr > 0;   // wave-uniform
+  // the reward program's component sink; a predicate has no outputs (hs_set_termination refuses them)
+  RpSink<T> sink, none;
+  int32_t ep = 0;
+  if (a.comp) {
+    sink.comp = a.comp;
+    sink.n = a.n;
+    sink.env = e;
+    sink.live = ok;
+    if (a.outcome) {
+      ep = a.episode[e];
+      sink.total = a.comp_total;
+      sink.zero = a.truncated[e] != 0;
+      sink.fresh = a.comp_episode[e] != ep;
+    }
+  }
   T res = T(0);
-  if (has_prog) res = rp_run<T>(a.prog, a, e, v);
+  if (has_prog) res = rp_run<T>(a.prog, a, e, v, sink);
   if (!a.outcome) {
     if (ok) a.out[env] = res;
     return;
   }
   T held = T(0);
-  if (has_pred) held = rp_run<T>(a.pred, a, e, v);
+  if (has_pred) held = rp_run<T>(a.pred, a, e, v, none);
   // The env step's outcome on the post-step, pre-reset state (custom_env.py:201-224), as the step kernel's
   // env_outcome writes it for a built-in reward: a truncated env is rewarded 0, the reward joins the
   // episode's total, a finished env leaves its final info and obs in the terminal rows, and its done byte
@@ -105,6 +150,16 @@ __global__ __launch_bounds__(RP_BLOCK) void reward_program_kernel(RpArgs<T> a) {
       if (a.term_step_count) a.term_step_count[env] = a.step_count[env];
       if (a.term_total_reward) a.term_total_reward[env] = total;
     }
+    // the component sums now belong to this episode; a finished env leaves them beside its total reward
+    // (the lane reads back what it stored itself at its RP_OUTs)
+    if (a.comp) {
+      a.comp_episode[env] = ep;
+      if (done)
+        for (int c = 0; c < a.n_outputs; c++) {
+          const long long at = (long long)c * a.n + env;
+          a.term_comp_total[at] = a.comp_total[at];
+        }
+    }
   }
   // terminal obs rows: the wave copies each finished env's row together (coalesced; finished envs are few)
   unsigned long long m = __ballot(done);
@@ -126,6 +181,9 @@ hipError_t launch_reward_program(const RpArgs<T>& a, hipStream_t stream) {
     return hipErrorInvalidValue;
   if (a.outcome ? (ni == 0 && np == 0) : (ni == 0 || np != 0)) return hipErrorInvalidValue;
   if (np > 0 && (!a.episode || !a.grace_count || !a.grace_episode || !a.early || a.grace_steps < 1))
+    return hipErrorInvalidValue;
+  if (a.comp && (ni == 0 || a.n_outputs < 1 || a.n_outputs > RP_MAX_OUTPUTS ||
+                 (a.outcome && (!a.comp_total || !a.comp_episode || !a.term_comp_total || !a.episode))))
     return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)(((long long)a.n + RP_BLOCK - 1) / RP_BLOCK);
   const size_t lds = (size_t)a.n_slots * RP_BLOCK * sizeof(T);   // <= 64 * 64 * 8 = 32 KB

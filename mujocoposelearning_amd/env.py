@@ -10,7 +10,11 @@ numpy's global legacy RNG exactly as the reference (custom_env.py:99-117), so
 Additive env_config keys: ``device`` (GPU index, default 0), ``precision`` ('fp64' default
 for this single-env surface, 'fp32'), ``max_newton``, ``termination`` (``{"type": "fallen", "params": {...},
 "grace_steps": 1}``: the fall conditions custom_env.py:167-200 holds commented out; ``terminated`` is then true
-on an early end and ``info["early_termination"]`` says which kind it was).
+on an early end and ``info["early_termination"]`` says which kind it was).  ``reward_config["components"] = True``
+(built-in types) or a registered program reward whose function returns a dict fills ``self.reward_components`` --
+and through custom_env.py:217's own ``getattr``, ``info["reward_components"]`` -- with the reward's named terms
+after every step (all 0.0 on the truncated step, as the reward is); the reward is then the program's numeric
+twin, evaluated on the host.
 """
 from __future__ import annotations
 
@@ -203,6 +207,16 @@ class HumanoidEnv(Env):
     def _configure(self, max_newton):
         rtype = self.reward_config.get('type', 'default')
         self._reward_dev = _rf.DEVICE_REWARD_IDS.get(_rf.REWARD_FUNCTIONS.get(rtype))
+        # named reward components (info['reward_components'], custom_env.py:217): a program reward whose function
+        # returns a dict, or a built-in with reward_config["components"] = True, which then runs as its
+        # *_components_program's numeric twin on the host instead of inside the step kernel
+        from . import reward_program as _rw
+        self._components = None
+        if self.reward_config.get('components'):
+            self._components = _rw.components_reward(rtype)
+            self._reward_dev = None
+        elif rtype in _rf.REWARD_FUNCTIONS:
+            self._components = _rw.device_reward_program(rtype)     # None for a built-in or a plain callable
         params = self.reward_config.get('params')
         kneel = params if (self._reward_dev == 1 and params) else None
         self._batch.configure(frame_skip=self.frame_skip, duration=float(self.duration), max_steps=750,
@@ -256,6 +270,12 @@ class HumanoidEnv(Env):
         if truncated:
             truncation_info['reason'] = 'timeout'
             reward = 0.0
+            if self._components is not None:      # every component is 0 on the truncated step, as the reward is
+                self.reward_components = {k: 0.0 for k in self._components.component_names}
+        elif self._components is not None:
+            # the program's numeric twin: the reward and its named terms from one evaluation
+            reward, self.reward_components = self._components.twin_with_components(
+                self.data, self.reward_config.get('params', None))
         else:
             reward = float(cols[0, 0]) if self._reward_dev is not None else self._compute_reward()
             params = self.reward_config.get('params')

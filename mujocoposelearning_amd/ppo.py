@@ -361,6 +361,14 @@ class PPO:
         self.num_timesteps = 0
         self.ep_returns = []
         self.ep_acc = torch.zeros(N, dtype=torch.float64, device=dev)
+        # a reward with named components (HumanoidVecEnv.terminal_total_reward_components, [C, N]): the finished
+        # episodes' component sums are copied per step -- one device copy, graph-capturable -- and gathered under
+        # the done mask with ep_returns.  No components: nothing is allocated, launched or logged.
+        self._comp_names = ()
+        self.ep_components = []
+        if getattr(env, "terminal_total_reward_components", None) is not None:
+            self._comp_names = tuple(env.reward_component_names)
+            self.buf["epcomp"] = torch.zeros(T, len(self._comp_names), N, dtype=torch.float64, device=dev)
         self.flat = [p for p in self.policy.parameters()]
         # device rollout: the clipped actions the env steps with, and the Philox noise stream
         self._act_clip = torch.zeros(N, A, dtype=f, device=dev)
@@ -483,7 +491,15 @@ class PPO:
         """The end of collect_rollouts on either path: finished-episode returns, the timestep count,
         the value of the last obs and GAE."""
         b = self.buf
-        self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
+        if "epcomp" not in b:
+            self.ep_returns += b["epret"][b["done"]].tolist()      # one device -> host transfer per rollout
+        else:     # the same transfer carries the finished episodes' component sums: rows of (return, components)
+            T, C, N = b["epcomp"].shape
+            idx = b["done"].view(-1).nonzero().squeeze(1)
+            rows = torch.cat([b["epret"].view(-1)[idx][:, None],
+                              b["epcomp"].permute(0, 2, 1).reshape(T * N, C)[idx]], dim=1).tolist()
+            self.ep_returns += [r[0] for r in rows]
+            self.ep_components += [r[1:] for r in rows]
         self.num_timesteps += self.n_steps * self.n_envs_global
         last_v = self.policy.value(self._obs_last_n if self._norm_obs() else self.obs)
         vn = self.vec_normalize
@@ -586,6 +602,8 @@ class PPO:
             ppo_post(rew.float(), term.to(torch.uint8), trunc.to(torch.uint8), None, gamma, obs.float(), nxt,
                      b["rew"][t], b["done"][t], self.ep_acc, b["epret"][t], self.episode_start,
                      terminal_obs=env.terminal_obs.float(), boot_obs_out=b["tobs"][t], boot_out=b["boot"][t])
+            if "epcomp" in b:
+                b["epcomp"][t].copy_(env.terminal_total_reward_components)
         self._rollout_tail()
 
     def _rollout_tail(self):
@@ -650,6 +668,8 @@ class PPO:
             b["done"][t] = done
             b["epret"][t] = self.ep_acc
             self.ep_acc.masked_fill_(done, 0.0)
+            if "epcomp" in b:
+                b["epcomp"][t].copy_(env.terminal_total_reward_components)
             self.obs = obs.float().clone()
             self.episode_start = done.float()
         return self._finish_rollout()
@@ -679,6 +699,8 @@ class PPO:
             b["done"][t] = done
             b["epret"][t] = self.ep_acc
             self.ep_acc.masked_fill_(done, 0.0)
+            if "epcomp" in b:
+                b["epcomp"][t].copy_(env.terminal_total_reward_components)
             self.obs = obs.float().clone()
             self.episode_start = done.float()
         self._normalize_rollout()
@@ -1120,6 +1142,9 @@ class PPO:
                                train_s=t2 - t1, ep_rew_mean=mean_ret, **st)
             if warn is not None:
                 self.logger["env_warnings"] = [int(x) for x in warn]
+            if self._comp_names and self.ep_components:   # the reward's named components, as ep_rew_mean is
+                means = np.mean(np.asarray(self.ep_components[-100:], dtype=np.float64), axis=0)
+                self.logger["ep_components_mean"] = {k: float(v) for k, v in zip(self._comp_names, means)}
             if self._agree_stop(callback is not None and callback(self) is False):
                 break
         return self

@@ -39,6 +39,15 @@ the whole blocks of 8, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the ta
 tracer emits that add tree itself.  Programs are pure: the ``params["previous_qpos"]`` side effect of
 the built-in callables is not part of the language.
 
+Named components: a function may return a ``dict`` of name -> scalar expression instead of one expression.  It
+must contain ``"total"``, which is the reward; every entry, ``"total"`` included, is a component, in dict order
+(at most ``MAX_OUTPUTS`` = 16, names non-empty ``str``; otherwise ValueError).  The twin in ``REWARD_FUNCTIONS``
+still returns the reward as a float; ``DeviceReward.twin_components`` gives ``{name: float}`` and the program
+carries one ``out`` instruction per component (csrc/hs_reward_prog.h RP_OUT), which the kernel stores into
+component-major ``[C, N]`` rows: ``info["reward_components"]`` of the env surfaces, ``HsBatch.reward_components``.
+A function that returns a scalar traces exactly as before.  ``stand_components_program`` and its two siblings at
+the end of this module break the built-ins down; ``reward_config={"type": "stand", "components": True}`` runs one.
+
 Limits (include/hsim.h HS_RP_MAX_*): 4096 instructions, 64 LIVE values (the tracer allocates value slots
 by liveness, so a long program is fine as long as few values are alive at once), 256 constants,
 32 parameters.  A program over a limit is refused at trace time with the figure in the message.
@@ -61,8 +70,9 @@ MAX_INSTR, MAX_SLOTS, MAX_CONSTS, MAX_PARAMS = 4096, 64, 256, 32
 _OPS = ("const", "param", "load",
         "add", "sub", "mul", "div", "arctan2", "lt", "le", "gt", "ge", "eq", "ne", "and", "or",
         "neg", "abs", "sqrt", "exp", "log", "sin", "cos", "tanh", "arcsin", "arccos", "not",
-        "where", "result")
+        "where", "result", "out")
 OP = {n: i for i, n in enumerate(_OPS)}
+MAX_OUTPUTS = 16
 _ARITY = {**{n: 2 for n in _OPS[3:16]}, **{n: 1 for n in _OPS[16:27]}, "where": 3}
 # csrc/hs_reward_prog.h RpField, and each field's row shape from (nq, nv, nu, nbody)
 FIELDS = ("qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel", "subtree_com", "cfrc_ext",
@@ -379,12 +389,29 @@ class TracedProgram:
     """A reward function traced for one model: ``code`` [n, 5] int32 (op, dst, a, b, c), ``consts`` float64,
     ``param_keys`` (the parameter slots' names, in order), ``n_slots`` and the set of ``fields`` read."""
 
-    def __init__(self, code, consts, param_keys, n_slots, fields):
+    def __init__(self, code, consts, param_keys, n_slots, fields, outputs=()):
         self.code, self.consts, self.param_keys, self.n_slots, self.fields = code, consts, param_keys, n_slots, fields
+        self.outputs = tuple(outputs)     # the component names in dict order; () for a scalar function
 
     @property
     def n_instr(self):
         return len(self.code)
+
+
+def _components(ret, lift):
+    """What a reward function returned, checked: (total, [(name, scalar), ...]).  A dict is the reward's named
+    components, ``"total"`` the reward itself; anything else is the reward alone and has no components."""
+    if not isinstance(ret, dict):
+        return lift(ret), []
+    for k in ret:
+        if not isinstance(k, str) or not k:
+            raise ValueError(f"reward components: the names must be non-empty str, got {k!r}")
+    if "total" not in ret:
+        raise ValueError(f'reward components: the dict must contain the key "total" (the reward); got {list(ret)}')
+    if len(ret) > MAX_OUTPUTS:
+        raise ValueError(f"reward components: {len(ret)} entries, the limit is {MAX_OUTPUTS}")
+    comps = [(k, lift(v)) for k, v in ret.items()]
+    return dict(comps)["total"], comps
 
 
 def trace(fn, dims, param_keys=()):
@@ -394,11 +421,16 @@ def trace(fn, dims, param_keys=()):
         raise ValueError(f"reward program: {len(param_keys)} parameters, the limit is {MAX_PARAMS}")
     tr = _Tracer(param_keys)
     p = _Params({k: tr.param(i) for i, k in enumerate(param_keys)})
-    res = tr.lift(fn(_trace_view(tr, tuple(int(x) for x in dims)), p))
+    res, comps = _components(fn(_trace_view(tr, tuple(int(x) for x in dims)), p), tr.lift)
     nodes = tr.nodes
-    # dead code out: only what the result depends on
+    # node -> the indices of the components it is (two names may be bound to one node); an ``out`` is the
+    # order entry ("out", node, index): it reads the node's slot and writes none
+    outs = {}
+    for c, (_, s) in enumerate(comps):
+        outs.setdefault(s.v, []).append(c)
+    # dead code out: only what the result and the components depend on
     need = np.zeros(len(nodes), dtype=bool)
-    stack = [res.v]
+    stack = [res.v] + list(outs)
     while stack:
         i = stack.pop()
         if need[i]:
@@ -407,22 +439,33 @@ def trace(fn, dims, param_keys=()):
         op, *args = nodes[i]
         stack.extend(args[:_ARITY.get(op, 0)])
     # order: computed nodes as the function made them; a leaf (constant, parameter, load) right before its first use
+    # a component's ``out`` right after the instruction that produces its value, so that its slot is free again
+    # as early as it can be
     order, placed = [], set()
+
+    def place(i):
+        placed.add(i)
+        order.append(i)
+        order.extend(("out", i, c) for c in outs.get(i, ()))
     for i, (op, *args) in enumerate(nodes):
         if not need[i] or op in ("const", "param", "load"):
             continue
         for a in args[:_ARITY[op]]:
             if a not in placed and nodes[a][0] in ("const", "param", "load"):
-                placed.add(a)
-                order.append(a)
-        placed.add(i)
-        order.append(i)
+                place(a)
+        place(i)
+    for i in outs:                      # a component that is a bare leaf nothing else uses
+        if i not in placed:
+            place(i)
     if res.v not in placed:
         order.append(res.v)
     if len(order) + 1 > MAX_INSTR:
         raise ValueError(f"reward program: {len(order) + 1} instructions, the limit is {MAX_INSTR}")
     last = {}
     for pos, i in enumerate(order):
+        if isinstance(i, tuple):        # an out keeps its value's slot alive until here
+            last[i[1]] = pos
+            continue
         op, *args = nodes[i]
         for a in args[:_ARITY.get(op, 0)]:
             last[a] = pos
@@ -433,6 +476,11 @@ def trace(fn, dims, param_keys=()):
     slot, free, n_slots = {}, [], 0
     code = np.zeros((len(order) + 1, 5), dtype=np.int32)
     for pos, i in enumerate(order):
+        if isinstance(i, tuple):
+            code[pos] = [OP["out"], 0, slot[i[1]], i[2], 0]
+            if last[i[1]] == pos:
+                free.append(slot.pop(i[1]))
+            continue
         op, *args = nodes[i]
         ar = _ARITY.get(op, 0)
         ops = [slot[a] for a in args[:ar]]
@@ -463,8 +511,9 @@ def trace(fn, dims, param_keys=()):
     if len(consts) > MAX_CONSTS:
         raise ValueError(f"reward program: {len(consts)} constants, the limit is {MAX_CONSTS}")
     code[len(order)] = [OP["result"], 0, slot[res.v], 0, 0]
-    fields = sorted({FIELDS[nodes[i][1]] for i in order if nodes[i][0] == "load"})
-    return TracedProgram(code, np.asarray(consts, dtype=np.float64), param_keys, max(n_slots, 1), fields)
+    fields = sorted({FIELDS[nodes[i][1]] for i in order if not isinstance(i, tuple) and nodes[i][0] == "load"})
+    return TracedProgram(code, np.asarray(consts, dtype=np.float64), param_keys, max(n_slots, 1), fields,
+                         [k for k, _ in comps])
 
 
 # ------------------------------------------------------------------ registration
@@ -473,6 +522,7 @@ class DeviceReward:
     traces / native programs made of it per model."""
 
     kind = "reward"
+    components_allowed = True      # a function may return a dict of named components (DeviceTermination: no)
 
     def __init__(self, name, fn, defaults):
         self.name = name
@@ -481,12 +531,10 @@ class DeviceReward:
         self.param_keys = list(self.defaults)
         self._traced = {}
         self._compiled = {}
+        self._names = None
 
         def twin(env_data, params=None):
-            vals = _merge_params(self.defaults, params, name, self.kind)
-            p = _Params({k: Scalar(_NUMERIC, _F(v)) for k, v in vals.items()})
-            with np.errstate(all="ignore"):
-                return self._twin_value(float(_NUMERIC.lift(fn(_numeric_view(env_data), p)).v))
+            return self._twin_value(self.twin_with_components(env_data, params)[0])
         twin.__name__ = getattr(fn, "__name__", name)
         twin.__doc__ = fn.__doc__
         twin.device_reward = self
@@ -495,6 +543,36 @@ class DeviceReward:
     @staticmethod
     def _twin_value(v):
         return v
+
+    def twin_with_components(self, env_data, params=None):
+        """The function on numbers, one evaluation: (the twin's value before ``_twin_value``, a float;
+        ``{component name: float}``, empty for a function that returns a scalar)."""
+        vals = _merge_params(self.defaults, params, self.name, self.kind)
+        p = _Params({k: Scalar(_NUMERIC, _F(v)) for k, v in vals.items()})
+        with np.errstate(all="ignore"):
+            total, comps = _components(self.fn(_numeric_view(env_data), p), _NUMERIC.lift)
+        self._note_names([k for k, _ in comps])
+        return float(total.v), {k: float(s.v) for k, s in comps}
+
+    def _note_names(self, names):
+        if names and not self.components_allowed:
+            raise ValueError(f"{self.kind} {self.name!r} returns a dict of components {list(names)}: a termination "
+                             "predicate is one truth value and has no components")
+        self._names = tuple(names)
+
+    def twin_components(self, env_data, params=None):
+        """The named components ``{name: float}`` of the reward on ``env_data``, evaluated in the numeric twin's
+        context: ``twin_components(d)["total"]`` is the twin's own return value, bit for bit.  ``{}`` for a
+        function that returns a scalar."""
+        return self.twin_with_components(env_data, params)[1]
+
+    @property
+    def component_names(self):
+        """The component names in dict order, a tuple; () for a function that returns a scalar.  Known from the
+        function's last trace or evaluation; before either, from a trace for the packaged humanoid's dimensions."""
+        if self._names is None:
+            self.trace((28, 27, 21, 17))
+        return self._names
 
     def params(self, overrides=None):
         """The parameter values in slot order: the defaults overlaid with ``overrides`` (unknown key: ValueError)."""
@@ -505,7 +583,9 @@ class DeviceReward:
         dims = tuple(int(x) for x in dims)
         t = self._traced.get(dims)
         if t is None:
-            t = self._traced[dims] = trace(self.fn, dims, self.param_keys)
+            t = trace(self.fn, dims, self.param_keys)
+            self._note_names(t.outputs)
+            self._traced[dims] = t
         return t
 
     def compile(self, model):
@@ -525,11 +605,12 @@ class CompiledProgram:
         self.model = model
         self.traced = t = reward.trace((model.nq, model.nv, model.nu, model.nbody))
         self.fields = t.fields
+        self.outputs = t.outputs            # the component names, row by row of the [C, N] component tensors
         code = np.ascontiguousarray(t.code, dtype=np.int32)
         h = C.c_void_p()
-        check(lib().hs_reward_program_create(model.handle, code.ctypes.data, len(code),
-                                             t.consts.ctypes.data if len(t.consts) else None, len(t.consts),
-                                             len(t.param_keys), C.byref(h)))
+        check(lib().hs_reward_program_create_components(model.handle, code.ctypes.data, len(code),
+                                                        t.consts.ctypes.data if len(t.consts) else None, len(t.consts),
+                                                        len(t.param_keys), len(t.outputs), C.byref(h)))
         self.handle = h
         self._pcache = {}
 
@@ -542,15 +623,21 @@ class CompiledProgram:
             a = self._pcache[key] = (C.c_double * max(len(v), 1))(*v)
         return a
 
-    def eval_host(self, fields, params=None):
+    def eval_host(self, fields, params=None, components=False):
         """The program interpreted on the CPU (``hs_reward_program_eval_host``): ``fields`` maps field names to
-        float64 arrays [n, ...] (``subtree_com``: [n, 3] or [n, nbody, 3], row 0 is used); returns [n] float64."""
+        float64 arrays [n, ...] (``subtree_com``: [n, 3] or [n, nbody, 3], row 0 is used); returns [n] float64.
+        ``components=True``: (reward [n], components [C, n]), the rows in the order of ``self.outputs``."""
         from . import _lib
         f, keep, n = self._host_fields(fields)
         out = np.zeros(n, dtype=np.float64)
-        _lib.check(_lib.lib().hs_reward_program_eval_host(self.handle, self.params(params), n, C.byref(f),
-                                                         out.ctypes.data))
-        return out
+        if not components:
+            _lib.check(_lib.lib().hs_reward_program_eval_host(self.handle, self.params(params), n, C.byref(f),
+                                                             out.ctypes.data))
+            return out
+        comp = np.zeros((len(self.outputs), n), dtype=np.float64)
+        _lib.check(_lib.lib().hs_reward_program_eval_host_components(
+            self.handle, self.params(params), n, C.byref(f), out.ctypes.data, comp.ctypes.data if comp.size else None))
+        return out, comp
 
     def _host_fields(self, fields):
         from . import _lib
@@ -635,6 +722,7 @@ class DeviceTermination(DeviceReward):
     terminated iff the result is non-zero and not NaN (a comparison with a NaN is false, as in Python)."""
 
     kind = "termination"
+    components_allowed = False     # a dict-returning predicate raises ValueError when traced or evaluated
 
     @staticmethod
     def _twin_value(v):
@@ -749,6 +837,25 @@ KNEEL_DEFAULTS = {'target_height': 1.282, 'min_height': 0.85, 'max_roll_pitch': 
 
 def kneeling_program(d, p):
     """reward_functions.py:66-154 (``robust_kneeling_reward``) in the language."""
+    return kneeling_components_program(d, p)["total"]
+
+
+def stand_program(d, p):
+    """reward_functions.py:156-211 (``stand_reward``, the 'default' and 'stand' entries) in the language."""
+    return stand_components_program(d, p)["total"]
+
+
+def walk_program(d, p):
+    """reward_functions.py:213-261 (``walk_reward``) in the language."""
+    return walk_components_program(d, p)["total"]
+
+
+# The same three with their terms named: the reference's own term names (reward_functions.py's velocity_reward,
+# posture_reward, foot_reward, torque_penalty, ... without the suffix), each the UNWEIGHTED term as the reference
+# computes it, and "total" the reward -- the very expression the *_program functions above return.  They are not
+# registry entries either; reward_config={"type": "stand", "components": True} selects one (components_reward).
+def kneeling_components_program(d, p):
+    """``kneeling_program`` with its terms: posture, com, foot, energy, alive (each before its weight), total."""
     qpos, qvel = d.qpos, d.qvel
     h = qpos[2]
     roll, pitch, _ = quaternion_to_euler(qpos[3:7])
@@ -765,11 +872,12 @@ def kneeling_program(d, p):
     alive = 1.0 - exp(-0.5 * d.time)
     total = (p['posture_weight'] * posture + p['com_weight'] * com + p['foot_weight'] * foot +
              p['energy_weight'] * energy + p['alive_weight'] * alive)
-    return where(h < p['min_height'], h ** 2, total)
+    return {"posture": posture, "com": com, "foot": foot, "energy": energy, "alive": alive,
+            "total": where(h < p['min_height'], h ** 2, total)}
 
 
-def stand_program(d, p):
-    """reward_functions.py:156-211 (``stand_reward``, the 'default' and 'stand' entries) in the language."""
+def stand_components_program(d, p):
+    """``stand_program`` with its terms: velocity, posture, foot, torque (weights 0.4, 0.3, 0.2, 0.1), total."""
     h = d.qpos[2]
     vx = d.qvel[0]
     roll, pitch, _ = quaternion_to_euler(d.qpos[3:7])
@@ -779,20 +887,43 @@ def stand_program(d, p):
     torque = exp(-0.05 * sum(square(d.ctrl)))
     foot = 1.0 - minimum(lf, rf) / (lf + rf + 1e-8)
     reward = 0.4 * vel + 0.3 * posture + 0.2 * foot + 0.1 * torque
-    return where(h < 0.8, 0.0, reward)
+    return {"velocity": vel, "posture": posture, "foot": foot, "torque": torque, "total": where(h < 0.8, 0.0, reward)}
 
 
-def walk_program(d, p):
-    """reward_functions.py:213-261 (``walk_reward``) in the language."""
+def walk_components_program(d, p):
+    """``walk_program`` with its terms: velocity, posture, torque (total = velocity + posture * torque), total."""
     h = d.qpos[2]
     vx = d.qvel[0]
     roll, pitch, _ = quaternion_to_euler(d.qpos[3:7])
     vel = exp(-0.5 * ((vx - 10.0) ** 2))
     posture = 0.5 * exp(-2.0 * ((h - 1.282) ** 2)) + 0.5 * exp(-3.0 * (roll ** 2 + pitch ** 2))
     torque = exp(-0.05 * sum(square(d.ctrl)))
-    return where(h < 0.8, 0.1 * h / 0.8, vel + posture * torque)
+    return {"velocity": vel, "posture": posture, "torque": torque,
+            "total": where(h < 0.8, 0.1 * h / 0.8, vel + posture * torque)}
 
 
-# (The three are worked examples and the feature's yardstick, not registry entries: REWARD_FUNCTIONS keeps the
-# reference's four keys, whose built-in names run inside the step kernel.  To use one as a program:
-# register_device_reward("stand_program", stand_program), and for kneeling defaults=KNEEL_DEFAULTS.)
+COMPONENT_PROGRAMS = {"default": (stand_components_program, None), "stand": (stand_components_program, None),
+                      "kneeling": (kneeling_components_program, KNEEL_DEFAULTS),
+                      "walk": (walk_components_program, None)}
+_COMPONENT_RECORDS = {}
+
+
+def components_reward(rtype):
+    """The ``DeviceReward`` record of the built-in reward ``rtype`` with its terms named -- what
+    ``reward_config={"type": rtype, "components": True}`` runs, on the program path (hs_step_program: three
+    launches per step, never a fused launch).  The records are kept here, not in ``REWARD_FUNCTIONS``, whose keys
+    stay the reference's four.  A type without a breakdown raises ValueError."""
+    if rtype not in COMPONENT_PROGRAMS:
+        raise ValueError(f'reward_config "components": True needs one of the built-in types {sorted(COMPONENT_PROGRAMS)} '
+                         f"(got {rtype!r}); a registered program reward has components when its function returns a dict")
+    rec = _COMPONENT_RECORDS.get(rtype)
+    if rec is None:
+        fn, defaults = COMPONENT_PROGRAMS[rtype]
+        rec = _COMPONENT_RECORDS[rtype] = DeviceReward(rtype, fn, defaults)
+    return rec
+
+
+# (The *_program functions are worked examples and the feature's yardstick, not registry entries: REWARD_FUNCTIONS
+# keeps the reference's four keys, whose built-in names run inside the step kernel.  To use one as a program:
+# register_device_reward("stand_program", stand_program), and for kneeling defaults=KNEEL_DEFAULTS; the breakdowns
+# are reached through reward_config["components"], or registered the same way under a name of your own.)

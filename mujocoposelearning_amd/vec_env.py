@@ -55,7 +55,12 @@ class HumanoidVecEnv(_Base):
         """``env_config``: the env_config dict (train_sb3.py:183-200), a model path, or SB3's
         ``[make_env(env_config, i) for i in range(n)]`` list of factories (train_sb3.py:203): all
         envs of one rank share one config, recovered from the first factory, and ``n_envs``
-        defaults to the list length."""
+        defaults to the list length.
+
+        ``reward_config["components"] = True`` (the built-in types only) fills ``info["reward_components"]`` with
+        the reward's named terms by running the built-in's ``reward_program.*_components_program`` on the program
+        path: rewards, obs and flags stay bitwise the built-in's, but every step is three launches and
+        ``rollout_handle()`` is None -- NOT the fused path, so a trainer collects its rollouts step by step."""
         if isinstance(env_config, (list, tuple)):
             if not env_config or not all(callable(f) for f in env_config):
                 raise TypeError("env_fns must be a non-empty list of env factories")
@@ -83,12 +88,24 @@ class HumanoidVecEnv(_Base):
         # a reward registered as a program (reward_program.register_device_reward) runs on the device:
         # hs_step_program evaluates it after the step and resets the finished envs, all as launches
         self._program = self.batch.compile_reward(rtype) if rid is None else None
+        # reward_config["components"] = True: a built-in reward with its terms named (info["reward_components"],
+        # custom_env.py:217) -- its *_components_program on the program path below, bitwise the built-in's reward.
+        # That path is three launches per step and never a fused launch (rollout_handle() is None): the flag has
+        # a price, which profiles/reward_programs.md states.  Without the flag nothing changes.
+        if self.reward_config.get("components"):
+            import torch
+            from .reward_program import components_reward
+            with torch.cuda.device(self.batch.device):
+                self._program = components_reward(rtype).compile(self.model)
+            rid = None
         self._program_params = None
         if self._program is not None:
             if len(self.batch._groups) != 1:
                 raise NotImplementedError("a reward program steps one stream group (groups=1)")
             self._program.params(params)          # an unknown key raises here, not at the first step
             self._program_params = params
+            if self._program.outputs:             # the component rows, bound once (a trainer reads them: ppo.PPO)
+                self.batch.bind_reward_components(self._program.outputs)
         # user-registered reward callables run on the host over per-env data views (slow, correct):
         # the kernel then steps without a reward and without auto-reset, so the callable sees the
         # pre-reset state; finished envs are reset by a second (masked) launch
@@ -166,6 +183,18 @@ class HumanoidVecEnv(_Base):
     def terminal_obs(self):
         """[N, obs_dim] device tensor: pre-reset obs of envs whose episode ended in the last step."""
         return self.batch.terminal_obs
+
+    @property
+    def reward_component_names(self):
+        """The names of the reward's components (a program whose function returns a dict, or a built-in with
+        ``reward_config["components"]``), in row order; () when the reward has none."""
+        return self.batch.reward_component_names
+
+    @property
+    def terminal_total_reward_components(self):
+        """[C, N] device tensor: the finished episodes' component sums of the envs that ended in the last step
+        (beside ``batch.terminal_total_reward``), or None when the reward has no components."""
+        return self.batch.terminal_total_reward_components if self.batch.reward_component_names else None
 
     def reset_tensors(self):
         """reset() on the device: returns the [N, obs_dim] device obs tensor."""
@@ -338,7 +367,8 @@ class HumanoidVecEnv(_Base):
         if not isinstance(a, torch.Tensor):
             a = torch.as_tensor(a, device=self.batch.device)
         self.step_tensors(a)
-        obs_np, cols, warn = self.batch.host_outputs(ncols=7, warnings=True)
+        # (the component rows of a reward with named components ride in the same copy; None otherwise)
+        obs_np, cols, warn, comps = self.batch.host_outputs(ncols=7, warnings=True, components=True)
         self._report_new_warnings(warn)
         rew_np = cols[0].copy()
         term_np, trunc_np = cols[1] != 0, cols[2] != 0
@@ -353,7 +383,9 @@ class HumanoidVecEnv(_Base):
             term_obs = self.batch.terminal_obs.index_select(0, rows).double().cpu().numpy()
             step_count = np.where(dones, cols[5], step_count)
             tot = np.where(dones, cols[6], tot)
-        return obs_np, rew_np, dones, StepInfos(obs_np, term_np, trunc_np, step_count, tot, idx, term_obs)
+        names = self.batch.reward_component_names if comps is not None else None
+        return obs_np, rew_np, dones, StepInfos(obs_np, term_np, trunc_np, step_count, tot, idx, term_obs,
+                                                comp_names=names, comps=comps)
 
     def _report_new_warnings(self, tot):
         """The warning counters this step added (the packed copy carries their sums): bad-state resets
@@ -454,9 +486,14 @@ class StepInfos(Sequence):
     annotate one, as SB3's VecMonitor does with ``episode``); a consumer that reads none pays
     nothing.  Building 4096 dicts in Python costs ~5 ms per step, more than the physics."""
 
-    __slots__ = ("_cols", "_idx", "_tobs", "_cache", "_n")
+    __slots__ = ("_cols", "_idx", "_tobs", "_cache", "_n", "_comp")
 
-    def __init__(self, obs, term, trunc, step_count, total, done_idx, term_obs):
+    def __init__(self, obs, term, trunc, step_count, total, done_idx, term_obs, comp_names=None, comps=None):
+        """``comp_names`` / ``comps``: a reward with named components -- the names and the [2, C, N] block of
+        ``HsBatch.host_outputs(components=True)`` (the step's components, the finished episodes' sums):
+        ``reward_components`` is then ``{name: float}`` and a finished env also carries
+        ``episode_reward_components``.  Built as lazily as everything else."""
+        self._comp = (tuple(comp_names), comps.copy()) if comp_names else None
         h = obs[:, 0].copy()
         if done_idx.size:
             h[done_idx] = term_obs[:, 0]
@@ -475,11 +512,15 @@ class StepInfos(Sequence):
             h, sc, tr, te, tot = self._cols
             pos = {int(i): k for k, i in enumerate(self._idx)}
             args = (h.tolist(), sc.astype(np.int64).tolist(), tr.tolist(), te.tolist(), tot.tolist(), pos, self._tobs)
+            extra = ()
+            if self._comp is not None:
+                names, block = self._comp
+                extra = (names, block[0].tolist(), block[1].tolist())
             try:        # the native builder (csrc/hs_infos.c, built for the interpreter of the Makefile)
                 from . import _hsinfo
-                self._cache = _hsinfo.build(*args, 0, self._n)
+                self._cache = _hsinfo.build(*args, 0, self._n, *extra)
             except ImportError:
-                self._cache = _build_infos_py(*args)
+                self._cache = _build_infos_py(*args, *extra)
         return self._cache
 
     def __getitem__(self, i):
@@ -492,17 +533,22 @@ class StepInfos(Sequence):
         return f"StepInfos({len(self)} envs)"
 
 
-def _build_infos_py(h, sc, tr, te, tot, pos, tobs):
+def _build_infos_py(h, sc, tr, te, tot, pos, tobs, names=None, comps=None, ep_comps=None):
     """The info dicts in Python (what csrc/hs_infos.c builds): custom_env.py:216-224 keys, plus
-    SB3's terminal_observation / TimeLimit.truncated for the envs that finished this step."""
+    SB3's terminal_observation / TimeLimit.truncated for the envs that finished this step.  ``names`` (a tuple)
+    with ``comps`` / ``ep_comps`` (C lists of per-env floats): the reward's named components, and the finished
+    episodes' sums as ``episode_reward_components``."""
     out = []
     for i in range(len(h)):
-        d = {"reward_components": {}, "height": h[i], "step_count": sc[i], "truncated": tr[i],
+        rc = {k: comps[c][i] for c, k in enumerate(names)} if names else {}
+        d = {"reward_components": rc, "height": h[i], "step_count": sc[i], "truncated": tr[i],
              "truncation_info": {"reason": "timeout"} if tr[i] else {}, "terminated": te[i], "total_reward": tot[i]}
         k = pos.get(i)
         if k is not None:
             d["terminal_observation"] = tobs[k]
             d["TimeLimit.truncated"] = bool(tr[i] and not te[i])
+            if names:
+                d["episode_reward_components"] = {k2: ep_comps[c][i] for c, k2 in enumerate(names)}
         out.append(d)
     return out
 
