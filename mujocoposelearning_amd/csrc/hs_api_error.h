@@ -1,4 +1,4 @@
-// Error plumbing of the C ABI, shared by its two translation units (hs_api.cpp, hs_api_ops.cpp): the
+// Error plumbing of the C ABI, shared by its translation units (hs_api*.cpp): the
 // calling thread's last error message and the helpers that set it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // hsim C ABI, stateless operators (see include/hsim.h): the PPO rollout / update operators, the policy
 // MLP forward and backward pieces, column sums and GAE -- entry points that validate their arguments and
-// launch on the caller's stream, and never touch an hs_batch (those are hs_api.cpp's).
+// launch on the caller's stream, and never touch an hs_batch (those are the batch side's: hs_api_batch.h).
 #include <hip/hip_runtime.h>
 
 #include <string>

@@ -1,4 +1,4 @@
-"""reward_program_kernel op by op and field by field on the device (csrc/hs_reward_prog.hip, hs_api.cpp
+"""reward_program_kernel op by op and field by field on the device (csrc/hs_reward_prog.hip, hs_api_reward.cpp
 rp_batch_fields): the grids, references and special cases of tests/program_op_cases.py, which
 tests/test_program_ops.py proves sound on the CPU first.
 
