@@ -397,6 +397,31 @@ int hs_evaluate_norm(hs_batch* b, const hs_policy* pol, int act, const hs_eval_b
  * SubprocVecEnv-exact mode where worker i continues its own np.random stream seeded with
  * seed + i (custom_env.py:99-110, SB3 VecEnv.seed).  The arrays stay owned by the caller. */
 int hs_set_autoreset_noise(hs_batch* b, const void* qpos_noise, const void* qvel_noise);
+/* Where an episode begins.  Bind (n_states > 0) or unbind (n_states == 0) the bank of initial states resets draw
+ * from.  qpos [K][nq], qvel [K][nv] or NULL (zeros): HOST doubles.  The library converts them to the batch
+ * precision, copies them to the device and owns the copy.  With a bank bound, every reset -- hs_reset and the
+ * auto-reset inside hs_step, hs_step_tape, hs_rollout* and hs_evaluate* alike -- starts its episode from row
+ *   j = min(K - 1, floor(u K)),
+ * u the [0, 1) value of the reset noise's counter hash at (seed, env, new episode number, slot 128), a slot no
+ * noise draw uses; the index comes from that hash whichever noise source is bound.  Then qpos = row + noise and
+ * qvel = row + noise with the noise of an unbound reset (the hs_reset arguments or the hs_set_autoreset_noise rows
+ * if given, else the counter RNG; U(+-noise_scale), the free joint's height noise x0.1, no quaternion noise);
+ * init_height and the upright quaternion are not imposed, the row supplies them.  ctrl = 0, time = 0 and the one
+ * mj_step of the reset are as ever.  The draw is uniform over the rows: repeat a row to weight it.  With no bank
+ * bound a reset is the reference's own (custom_env.py:97-130), and a bank of the one row (qpos0 with z =
+ * init_height and the upright quaternion; zero qvel) gives bitwise that reset.
+ * Refused (-1, the reason in hs_last_error): n_states < 0 or above HS_MAX_INITIAL_STATES, NULL qpos with
+ * n_states > 0, a value that is not finite, a zero free-joint quaternion.  The free joint's quaternion of every row
+ * is normalised (q / sqrt(w w + x x + y y + z z)) before it is stored.
+ * The call waits for the batch's pending launches on every stream, so the next launch sees the new bank and no
+ * earlier one does.  A launch recorded into a HIP graph keeps the bank (pointers and row count) it was recorded
+ * with: re-record it after a rebind.  The memory it points to stays the batch's until the batch is destroyed.
+ * A floor-lying row can overflow the resident contact tier during the reset's mj_step: a per-step launch re-runs
+ * the env in the wide tier, a fused launch aborts and is replayed step by step (hs_tape_aborts). */
+#define HS_MAX_INITIAL_STATES 4096
+int hs_set_initial_states(hs_batch* b, int n_states, const double* qpos, const double* qvel);
+/* *n_states = the rows bound (0: none). */
+int hs_get_initial_states(const hs_batch* b, int* n_states);
 /* One step's host-bound outputs in ONE launch, for a single device-to-host copy (the SubprocVecEnv
  * step_wait / Gym step() return values, custom_env.py:216-230, train_sb3.py:203): writes the float64
  * device buffer out = [obs N x obs_dim][ncols x N columns of reward, terminated, truncated,

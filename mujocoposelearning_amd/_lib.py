@@ -90,6 +90,7 @@ REWARD_FIELD_MEMBER = {n: ("subtree_com0" if n == "subtree_com" else n)
                                  "cfrc_ext", "subtree_linvel")}
 HS_RP_MAX_INSTR, HS_RP_MAX_SLOTS, HS_RP_MAX_CONSTS, HS_RP_MAX_PARAMS = 4096, 64, 256, 32
 HS_RP_MAX_OUTPUTS = 16
+HS_MAX_INITIAL_STATES = 4096     # most rows of a bank of initial states (hs_set_initial_states)
 
 
 class hs_batch_info(C.Structure):
@@ -149,6 +150,8 @@ def lib():
         "hs_return_moments": (i, [vp, vp, i, i, d, vp, vp, vp, vp]),
         "hs_reward_scale": (i, [vp, i, i, vp, vp, i, u64, d, d, vp, vp]),
         "hs_set_autoreset_noise": (i, [vp, vp, vp]),
+        "hs_set_initial_states": (i, [vp, i, vp, vp]),
+        "hs_get_initial_states": (i, [vp, vp]),
         "hs_physics_step": (i, [vp, vp, i, vp]),
         "hs_state_io": (i, [vp, i, vp, vp, vp, vp, vp]),
         "hs_kinematics": (i, [vp, i, vp, vp, vp, vp, vp, vp]),
@@ -246,7 +249,7 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_set_termination_builtin", "hs_termination_builtin_eval_host",
             "hs_reward_program_create_components", "hs_reward_program_outputs",
             "hs_reward_program_eval_host_components", "hs_reward_program_batch_components",
-            "hs_set_reward_components")
+            "hs_set_reward_components", "hs_set_initial_states", "hs_get_initial_states")
 
 
 class HsimError(RuntimeError):

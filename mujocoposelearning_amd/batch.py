@@ -169,10 +169,14 @@ class HsBatch:
         G = max(1, min(int(groups), self.n))
         bounds = [self.n * g // G for g in range(G + 1)]
         self._groups = []                       # (handle, lo, hi)
+        self._seed = int(seed)
+        # counts the changes of what a launch is given beyond the batch's buffers (set_initial_states): a launch
+        # recorded into a graph holds the old arguments, so whoever replays one compares this number first
+        self.launch_generation = 0
         for g in range(G):
             lo, hi = bounds[g], bounds[g + 1]
             bufs = _lib.hs_buffers(**{k: v.data_ptr() + lo * v.stride(0) * v.element_size() for k, v in self.t.items()})
-            gseed = (int(seed) + 0x9E3779B97F4A7C15 * g) & (2 ** 64 - 1)
+            gseed = self._group_seed(g)
             h = lib().hs_batch_create(model.handle, hi - lo, self.device.index, gseed, flags, C.byref(bufs))
             if not h:
                 self.close()
@@ -270,8 +274,9 @@ class HsBatch:
             check(lib().hs_set_config(h, C.byref(c)))
 
     def set_seed(self, seed):
+        self._seed = int(seed)
         for g, (h, _, _) in enumerate(self._groups):
-            check(lib().hs_set_seed(h, (int(seed) + 0x9E3779B97F4A7C15 * g) & (2 ** 64 - 1)))
+            check(lib().hs_set_seed(h, self._group_seed(g)))
 
     def _launch(self, fn, *tensors, join=True):
         """fn(handle, lo, hi, stream) per group; multi-group launches fan out to the group streams
@@ -345,6 +350,63 @@ class HsBatch:
             check(lib().hs_set_autoreset_noise(h, qn.data_ptr() + lo * qn.stride(0) * qn.element_size(),
                                                vn.data_ptr() + lo * vn.stride(0) * vn.element_size()))
         return qn, vn
+
+    # -- where episodes begin (hs_set_initial_states) ------------------------------------------
+    def set_initial_states(self, qpos=None, qvel=None):
+        """Bind the bank of initial states every reset of this batch draws its start from: ``qpos`` [K, nq] and
+        ``qvel`` [K, nv] (None: zeros) as host arrays, e.g. ``initial_state.build_bank(model, spec)``; ``qpos``
+        None unbinds, and resets are the reference's again.  Each group gets the same bank and draws with its own
+        seed.  A row's free-joint quaternion is normalised by the library.  The call waits for the batch's pending
+        launches; a trainer that replays a recorded per-step graph re-records it (``launch_generation``).
+        HsimError: rows of the wrong length, a value that is not finite, a zero quaternion, more than
+        ``HS_MAX_INITIAL_STATES`` rows."""
+        from .initial_state import normalize_quaternions
+        self.launch_generation += 1
+        if qpos is None:
+            for h, _, _ in self._groups:
+                check(lib().hs_set_initial_states(h, 0, None, None))
+            self._initial_states = None
+            return None
+        nq, nv = self.model.nq, self.model.nv
+        q = np.ascontiguousarray(np.asarray(qpos, dtype=np.float64))
+        q = q[None] if q.ndim == 1 else q
+        if q.ndim != 2 or q.shape[1] != nq or q.shape[0] < 1:
+            raise _lib.HsimError(f"set_initial_states: qpos must be [K, {nq}] with K >= 1, got {q.shape}")
+        v = None
+        if qvel is not None:
+            v = np.ascontiguousarray(np.asarray(qvel, dtype=np.float64))
+            v = v[None] if v.ndim == 1 else v
+            if v.shape != (q.shape[0], nv):
+                raise _lib.HsimError(f"set_initial_states: qvel must be [{q.shape[0]}, {nv}], got {v.shape}")
+        for h, _, _ in self._groups:
+            check(lib().hs_set_initial_states(h, q.shape[0], q.ctypes.data, None if v is None else v.ctypes.data))
+        # the rows as the library holds them (fp64; an fp32 batch rounds them once more)
+        self._initial_states = (normalize_quaternions(q), np.zeros((q.shape[0], nv)) if v is None else v.copy())
+        return self._initial_states
+
+    @property
+    def initial_states(self):
+        """(qpos [K, nq], qvel [K, nv]) float64 host arrays of the bound bank as the library holds it (quaternions
+        normalised; an fp32 batch holds them rounded to float32), or None when none is bound."""
+        return self.__dict__.get("_initial_states")
+
+    def initial_state_index(self):
+        """[N] int64 host array: the bank row each env's current episode started from, restated on the host from
+        the ``episode`` counters and the group seeds (``initial_state.draw_index``).  Meaningful for the episodes
+        that began with this bank bound; -1 for an env that was never reset, and for every env with no bank."""
+        from .initial_state import draw_index
+        out = np.full(self.n, -1, dtype=np.int64)
+        bank = self.initial_states
+        if bank is None:
+            return out
+        ep = self.t["episode"].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        for g, (_, lo, hi) in enumerate(self._groups):
+            out[lo:hi] = draw_index(self._group_seed(g), np.arange(hi - lo), ep[lo:hi], len(bank[0]))
+        out[ep == 0] = -1
+        return out
+
+    def _group_seed(self, g):
+        return (int(self._seed) + 0x9E3779B97F4A7C15 * g) & (2 ** 64 - 1)
 
     def step(self, actions, join=True):
         """custom_env.py:152-230 batched; ``actions`` [N, nu] float32 on device.  With stream

@@ -304,8 +304,9 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
     const hs_tape_out* t = x.tape;
     TapeOut<T> to{t ? (T*)t->obs : nullptr, t ? (T*)t->reward : nullptr, t ? t->terminated : nullptr,
                   t ? t->truncated : nullptr};
+    const InitArgs<T> in{(const T*)b->init_q, (const T*)b->init_v, b->init_n};   // (hs_set_initial_states)
     return launch_step<T>((const DevModel<T>*)b->dmodel, nv, env_buffers<T>(b), act, mask, (const T*)nq, (const T*)nvz,
-                          p, b->n, (hipStream_t)stream, &to, x.ro, x.ev, x.nm, term ? &tm : nullptr);
+                          p, b->n, (hipStream_t)stream, &to, x.ro, x.ev, x.nm, term ? &tm : nullptr, &in);
   });
   if (e == hipErrorInvalidValue) return fail("no kernel instance for this model's nv (compiled: nv = 27)");
   return hip_rc(e, "step kernel launch");
@@ -453,8 +454,9 @@ void hs_batch_destroy(hs_batch* b) {
     for (const BufRow& r : buffer_rows(b))
       if (*r.slot) (void)hipFree(*r.slot);
   for (void* p : {b->dmodel, b->dbg, (void*)b->redo, (void*)b->redo_total, (void*)b->prog_done, (void*)b->grace_count,
-                  (void*)b->grace_episode, (void*)b->early, b->tape_backup, (void*)b->kin_envs})
+                  (void*)b->grace_episode, (void*)b->early, b->tape_backup, (void*)b->kin_envs, b->init_q, b->init_v})
     if (p) (void)hipFree(p);
+  for (void* p : b->init_retired) (void)hipFree(p);
   hs::uc_release(b->device, (size_t)b->n * sizeof(int32_t), b->mid_count);
   if (b->mid) hs::uc_release(b->device, (size_t)b->n * hs::MIDDIM * hs::elem_size(b), b->mid);
   if (b->qsync) hs::uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);
@@ -578,6 +580,75 @@ int hs_set_autoreset_noise(hs_batch* b, const void* qpos_noise, const void* qvel
   if ((qpos_noise == nullptr) != (qvel_noise == nullptr)) return fail("bind both noise arrays or neither");
   b->ar_qpos_noise = qpos_noise;
   b->ar_qvel_noise = qvel_noise;
+  return 0;
+}
+
+int hs_set_initial_states(hs_batch* b, int n_states, const double* qpos, const double* qvel) {
+  const std::string who = "hs_set_initial_states";
+  if (!b) return fail(who + ": null batch");
+  if (n_states < 0 || n_states > HS_MAX_INITIAL_STATES)
+    return fail(who + ": n_states " + std::to_string(n_states) + " must lie in [0, HS_MAX_INITIAL_STATES = " +
+                std::to_string(HS_MAX_INITIAL_STATES) + "]");
+  if (n_states == 0) {   // unbind: the blocks stay for the next bind
+    b->init_n = 0;
+    return 0;
+  }
+  if (!qpos) return fail(who + ": qpos must not be NULL with n_states > 0");
+  const auto& h = b->model->host;
+  const size_t K = (size_t)n_states, nq = (size_t)h.nq, nv = (size_t)h.nv;
+  std::vector<double> q(qpos, qpos + K * nq), v(K * nv, 0.0);
+  if (qvel) v.assign(qvel, qvel + K * nv);
+  for (size_t i = 0; i < q.size(); i++)
+    if (!std::isfinite(q[i]))
+      return fail(who + ": qpos[" + std::to_string(i / nq) + "][" + std::to_string(i % nq) + "] is not finite");
+  for (size_t i = 0; i < v.size(); i++)
+    if (!std::isfinite(v[i]))
+      return fail(who + ": qvel[" + std::to_string(i / nv) + "][" + std::to_string(i % nv) + "] is not finite");
+  // the free joint's quaternion, normalised as mj_normalizeQuat would at the first mj_step; a zero one has no
+  // direction to keep
+  if (h.njnt > 0 && h.jnt_type[0] == hs::JNT_FREE && nq >= 7)
+    for (size_t j = 0; j < K; j++) {
+      double* r = q.data() + j * nq;
+      const double norm = std::sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5] + r[6] * r[6]);
+      if (!(norm >= 1e-15)) return fail(who + ": row " + std::to_string(j) + " has a zero free-joint quaternion");
+      for (int c = 3; c < 7; c++) r[c] /= norm;
+    }
+  DeviceGuard g(b->device);
+  // after the batch's pending launches, whatever stream they are on (they may read the rows written below)
+  if (!hip_ok(hipDeviceSynchronize(), "hs_set_initial_states")) return -1;
+  const size_t es = hs::elem_size(b);
+  if (n_states > b->init_cap) {
+    void *nq_blk = nullptr, *nv_blk = nullptr;
+    const int cap = std::min(HS_MAX_INITIAL_STATES, std::max(n_states, 2 * b->init_cap));
+    if (!hip_ok(hipMalloc(&nq_blk, (size_t)cap * nq * es), "hipMalloc(initial states)") ||
+        !hip_ok(hipMalloc(&nv_blk, (size_t)cap * nv * es), "hipMalloc(initial states)")) {
+      if (nq_blk) (void)hipFree(nq_blk);
+      return -1;
+    }
+    if (b->init_q) b->init_retired.push_back(b->init_q);
+    if (b->init_v) b->init_retired.push_back(b->init_v);
+    b->init_n = 0;
+    b->init_q = nq_blk;
+    b->init_v = nv_blk;
+    b->init_cap = cap;
+  }
+  const bool ok = by_precision(b->precision, [&](auto zero) {
+    using T = decltype(zero);
+    const std::vector<T> tq(q.begin(), q.end()), tv(v.begin(), v.end());
+    return hip_ok(hipMemcpy(b->init_q, tq.data(), tq.size() * sizeof(T), hipMemcpyHostToDevice), "initial states qpos") &&
+           hip_ok(hipMemcpy(b->init_v, tv.data(), tv.size() * sizeof(T), hipMemcpyHostToDevice), "initial states qvel");
+  });
+  if (!ok) {
+    b->init_n = 0;
+    return -1;
+  }
+  b->init_n = n_states;
+  return 0;
+}
+
+int hs_get_initial_states(const hs_batch* b, int* n_states) {
+  if (!b || !n_states) return fail("hs_get_initial_states: null argument");
+  *n_states = b->init_n;
   return 0;
 }
 

@@ -71,6 +71,14 @@ struct hs_batch {
   void* comp_total = nullptr;
   int32_t* comp_episode = nullptr;
   void* term_comp_total = nullptr;
+  // hs_set_initial_states: the bank of initial states resets draw from, in the batch precision: init_n rows bound
+  // (0: none) of the init_cap rows the two blocks hold.  A rebind that fits writes in place; one that does not
+  // allocates anew and retires the old blocks until the batch is destroyed, so a launch recorded into a graph
+  // before the rebind still reads memory of this batch.
+  void* init_q = nullptr;                    // [init_cap][nq]
+  void* init_v = nullptr;                    // [init_cap][nv]
+  int init_n = 0, init_cap = 0;
+  std::vector<void*> init_retired;
 };
 
 // a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on

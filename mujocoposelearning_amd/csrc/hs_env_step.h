@@ -497,6 +497,19 @@ __device__ __forceinline__ bool commit_or_handoff(KPtr<T> k, const Stepper<T, NV
 // reset draw: custom_env.py:97-130: mj_resetData; qpos = init (z=1.282, upright); += U(+-0.01) noise
 // with z noise x0.1 and no quaternion noise; qvel = U(+-0.01); one mj_step with ctrl = 0 (the caller's
 // next substep).
+// With a bank of initial states bound (KArgs::in, hs_set_initial_states) the episode starts from one of its
+// rows instead: row j = min(K - 1, floor(u K)), u the [0, 1) value of the counter hash at (seed, env, new
+// episode, INIT_SLOT) -- a slot no noise draw uses (qpos 0..nq-1, qvel 64..64+nv-1) -- whichever noise source
+// is bound; qpos = row + noise, qvel = row + noise, the free-joint rules on the noise alone (the row supplies
+// the height and the orientation).  One coalesced read of the row per reset: lane sl reads elements sl and
+// sl + HL.  K is wave-uniform, j the same in all lanes of a half-wave.
+constexpr int INIT_SLOT = 128;
+// the bank row of (seed, env, episode): scalar arithmetic on a half-wave's uniform values
+__device__ __forceinline__ int bank_row(uint64_t seed, int env, uint32_t ep, int K) {
+  const uint64_t h = splitmix(seed ^ splitmix(((uint64_t)env << 32) ^ ((uint64_t)ep << 8) ^ (uint64_t)INIT_SLOT));
+  const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);   // [0, 1), as uniform_pm
+  return min(K - 1, (int)(u * (double)K));
+}
 template <typename T, typename C>
 __device__ __forceinline__ void reset_draw(KPtr<T> k, MPtr<T> m, Scratch<T, C>& s, int sl, int nq, int nv, int nu,
                                            int env, uint32_t& episode, T& time, T& xws) {
@@ -505,16 +518,28 @@ __device__ __forceinline__ void reset_draw(KPtr<T> k, MPtr<T> m, Scratch<T, C>& 
   const T* nz_q = k->nz_q;
   const T* nz_v = k->nz_v;
   uint32_t ep = episode + 1;
+  // a bank bound: each half's row index from its own (env, episode), computed on the scalar unit from the halves'
+  // first lanes, so that nothing of it occupies a vector register; the rows are read relative to the uniform base
+  const int K = k->in.K;
+  uint32_t row = 0;
+  if (K > 0) {
+    const int j0 = bank_row(seed, __builtin_amdgcn_readfirstlane(env), __builtin_amdgcn_readfirstlane(ep), K);
+    const int j1 = bank_row(seed, __builtin_amdgcn_readlane(env, HL), __builtin_amdgcn_readlane(ep, HL), K);
+    row = (uint32_t)(threadIdx.x >= HL ? j1 : j0);
+  }
   for (int q = sl; q < nq; q += HL) {
-    T v = m->qpos0[q];
+    T v = K > 0 ? k->in.q[row * (uint32_t)nq + (uint32_t)q] : m->qpos0[q];
     T nzq = nz_q ? nz_q[(size_t)env * nq + q] : uniform_pm<T>(seed, env, ep, q, sc);
     if (m->jnt_type[0] == JNT_FREE) {
-      if (q == 2) { v = (T)k->p.init_height; nzq *= T(0.1); }
-      if (q >= 3 && q < 7) { v = q == 3 ? T(1) : T(0); nzq = 0; }
+      if (q == 2) { if (K <= 0) v = (T)k->p.init_height; nzq *= T(0.1); }
+      if (q >= 3 && q < 7) { if (K <= 0) v = q == 3 ? T(1) : T(0); nzq = 0; }
     }
     s.qpos[q] = v + nzq;
   }
-  if (sl < nv) s.qvel[sl] = nz_v ? nz_v[(size_t)env * nv + sl] : uniform_pm<T>(seed, env, ep, 64 + sl, sc);
+  if (sl < nv) {
+    const T nzv = nz_v ? nz_v[(size_t)env * nv + sl] : uniform_pm<T>(seed, env, ep, 64 + sl, sc);
+    s.qvel[sl] = K > 0 ? k->in.v[row * (uint32_t)nv + (uint32_t)sl] + nzv : nzv;
+  }
   if (sl < nu) s.ctrl[sl] = 0;
   xws = 0;
   time = 0;

@@ -215,6 +215,15 @@ struct TermArgs {
   int32_t* mid_count;       // [N] the count between an env's steps (uncached, hs_batch owned)
 };
 
+// The bank of initial states a reset draws its start from (hs_set_initial_states; hs_env_step.h reset_draw):
+// K rows of qpos / qvel in the batch precision, owned by the batch.  K = 0: the reference's reset.
+template <typename T>
+struct InitArgs {
+  const T* q;   // [K][nq]
+  const T* v;   // [K][nv]
+  int K;
+};
+
 // p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape` (may be null), env
 // steps of one env pair run back to back on the chunk queue with the state handed over through
 // b.mid; no wide-tier launch follows (an overflow sets qsync[QS_ABORT], the host replays the tape).
@@ -223,7 +232,7 @@ hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape = nullptr,
                        const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr, const NormArgs* nm = nullptr,
-                       const TermArgs* tm = nullptr);
+                       const TermArgs* tm = nullptr, const InitArgs<T>* in = nullptr);
 
 // The fused rollout / evaluation instance with obs normalisation (KArgs::nm set) on the chunk queue: kargs is
 // launch_step's KArgs<double>, max_grid its grid (the launch takes no more waves than the instance holds)

@@ -459,12 +459,15 @@ template <typename T>
 hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
                        const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
                        const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape,
-                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm, const TermArgs* tm) {
+                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm, const TermArgs* tm,
+                       const InitArgs<T>* in) {
   if (nenv <= 0) return hipSuccess;
   if (nv != 27) return hipErrorInvalidValue;
   KArgs<T> args{(MPtr<T>)dmodel, b, actions, reset_mask, noise_qpos, noise_qvel, p, nenv,
                 tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{},
-                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}, tm ? *tm : TermArgs{}};
+                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}, tm ? *tm : TermArgs{},
+                in ? *in : InitArgs<T>{nullptr, nullptr, 0}};
+  if (args.in.K < 0 || (args.in.K > 0 && (!args.in.q || !args.in.v))) return hipErrorInvalidValue;
   if (nm && (!ro || !nm->mean || !nm->inv_std || !(nm->clip > 0.f))) return hipErrorInvalidValue;
   // fused rollouts: the fp64 Newton engine
   if (ro && (sizeof(T) != 8 || !ro->obs || p.solver == SOLVER_PGS)) return hipErrorInvalidValue;
@@ -625,7 +628,7 @@ hipError_t launch_queue_term(const void* kargs, unsigned max_grid, bool rollout,
 template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuffers<float>&, const float*,
                                        const uint8_t*, const float*, const float*, const StepParams&, int,
                                        hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*,
-                                       const NormArgs*, const TermArgs*);
+                                       const NormArgs*, const TermArgs*, const InitArgs<float>*);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
 template hipError_t launch_kinematics_batch<float>(const DevModel<float>*, int, int, const float*, const float*,
@@ -637,7 +640,7 @@ template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvBuffers<double>&, const float*,
                                         const uint8_t*, const double*, const double*, const StepParams&, int,
                                         hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*,
-                                        const NormArgs*, const TermArgs*);
+                                        const NormArgs*, const TermArgs*, const InitArgs<double>*);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
 template hipError_t launch_kinematics_batch<double>(const DevModel<double>*, int, int, const double*, const double*,

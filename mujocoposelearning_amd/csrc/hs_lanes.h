@@ -255,6 +255,7 @@ struct KArgs {
   EvalArgs ev;                // fused evaluation (the EVAL instance only; after ro, so every other offset stays)
   NormArgs nm;                // obs normalisation of the fused policy (the NORM instances only; last, as above)
   TermArgs tm;                // built-in termination condition (the TERM instances only; last, as above)
+  InitArgs<T> in;             // bank of initial states the reset pass draws from (K = 0: none; last, as above)
 };
 template <typename T>
 using KPtr = const __attribute__((address_space(4))) KArgs<T>*;

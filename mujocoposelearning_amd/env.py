@@ -10,7 +10,10 @@ numpy's global legacy RNG exactly as the reference (custom_env.py:99-117), so
 Additive env_config keys: ``device`` (GPU index, default 0), ``precision`` ('fp64' default
 for this single-env surface, 'fp32'), ``max_newton``, ``termination`` (``{"type": "fallen", "params": {...},
 "grace_steps": 1}``: the fall conditions custom_env.py:167-200 holds commented out; ``terminated`` is then true
-on an early end and ``info["early_termination"]`` says which kind it was).  ``reward_config["components"] = True``
+on an early end and ``info["early_termination"]`` says which kind it was), ``initial_state`` (``{"keyframe":
+"squat"}``, ``{"trajectory": path}``, ...: every reset starts from a row of that bank of states instead of the
+standing pose, ``initial_state.build_bank``; its ``"noise_scale"`` scales the reset noise).
+``reward_config["components"] = True``
 (built-in types) or a registered program reward whose function returns a dict fills ``self.reward_components`` --
 and through custom_env.py:217's own ``getattr``, ``info["reward_components"]`` -- with the reward's named terms
 after every step (all 0.0 on the truncated step, as the reward is); the reward is then the program's numeric
@@ -165,8 +168,11 @@ class HumanoidEnv(Env):
             # the state (custom_env.py:167-200, there commented out; grace_period_length above stays parsed
             # and unused, as in the reference)
             termination = env_config.get('termination')
+            # additive: where episodes begin (initial_state.build_bank): {"keyframe": "squat"}, {"trajectory": path}
+            initial_state = env_config.get('initial_state')
         else:
             termination = None
+            initial_state = None
             self.model_path = env_config
             self.duration = 15
             self.framerate = 60
@@ -189,7 +195,13 @@ class HumanoidEnv(Env):
         self.init_qpos[2] = 1.282
         self.init_qpos[3:7] = [1, 0, 0, 0]
         self.init_qvel = np.zeros(self.model.nv)
+        self._noise_scale = 0.01      # custom_env.py:109-110
         self._configure(max_newton)
+        if initial_state is not None:    # unknown key / keyframe name, wrong lengths: ValueError here
+            from .initial_state import build_bank, noise_scale_of
+            self._batch.set_initial_states(*build_bank(self.model, initial_state))
+            self._noise_scale = noise_scale_of(initial_state, self._noise_scale)
+            self._batch.configure(noise_scale=self._noise_scale)
         self._termination = None
         if termination is not None:      # unknown type / parameter: ValueError here
             from .reward_program import termination_from_config
@@ -228,9 +240,11 @@ class HumanoidEnv(Env):
         """custom_env.py:97-150."""
         if seed is not None:
             np.random.seed(seed)
-        pos_noise = np.random.uniform(low=-0.01, high=0.01, size=self.model.nq)
-        vel_noise = np.random.uniform(low=-0.01, high=0.01, size=self.model.nv)
-        # the kernel applies pos_noise[2] *= 0.1, pos_noise[3:7] = 0 and the init pose (custom_env.py:105-117)
+        ns = self._noise_scale
+        pos_noise = np.random.uniform(low=-ns, high=ns, size=self.model.nq)
+        vel_noise = np.random.uniform(low=-ns, high=ns, size=self.model.nv)
+        # the kernel applies pos_noise[2] *= 0.1, pos_noise[3:7] = 0 and the init pose (custom_env.py:105-117), or,
+        # with env_config["initial_state"], the row of the bank it draws for this episode
         self._batch.reset(qpos_noise=pos_noise[None], qvel_noise=vel_noise[None])
         self.frames = []          # custom_env.py:123-127
         if self.renderer:

@@ -377,6 +377,7 @@ class PPO:
         self._noise_seed = (int(seed) + 7919 * rank) * 0x9E3779B97F4A7C15 % 2 ** 64
         self._noise_ctr = torch.zeros(1, dtype=torch.int64, device=dev)    # Philox step counter (device)
         self._rollout_graph = None
+        self._rollout_graph_gen = 0             # the env batch's launch_generation the graph was recorded at
         if self.vec_normalize is not None:      # normalised copies: one step's obs, the rollout's last obs
             self._obs_step = torch.zeros(N, D, dtype=f, device=dev)
             self._obs_last_n = torch.zeros(N, D, dtype=f, device=dev)
@@ -443,7 +444,13 @@ class PPO:
         if self._fused_rollout_args() is not None:
             self._rollout_fused()
         else:
+            # a recorded env launch holds the launch arguments of its time: a bank of initial states bound since
+            # (HsBatch.set_initial_states) is not in it, so the graph is dropped and recorded again
+            gen = getattr(getattr(env, "batch", None), "launch_generation", 0)
+            if self._rollout_graph is not None and gen != self._rollout_graph_gen:
+                self._rollout_graph = None
             if self.graphs and self._rollout_graph is None and getattr(env, "graph_safe", False):
+                self._rollout_graph_gen = gen
                 self._capture_rollout()                   # on failure: graphs off, eager body below
             if self._rollout_graph is not None:
                 self._rollout_graph.replay()

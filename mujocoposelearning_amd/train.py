@@ -36,7 +36,8 @@ def shard_envs(n_envs: int, world_size: int, rank: int):
 
 def env_config_from_kwargs(env_kwargs: dict, xml_path: str = DEFAULT_XML) -> dict:
     """train_sb3.py:183-200 (duration fixed at 10.0, reward default 'walk', frame_skip default 3).
-    ``env_kwargs["termination"]`` (hsim option, absent by default) is passed through."""
+    ``env_kwargs["termination"]`` and ``env_kwargs["initial_state"]`` (hsim options, absent by default) are passed
+    through."""
     cfg = {
         "model_path": str(xml_path),
         "render_mode": None,
@@ -47,6 +48,8 @@ def env_config_from_kwargs(env_kwargs: dict, xml_path: str = DEFAULT_XML) -> dic
     }
     if "termination" in env_kwargs:
         cfg["termination"] = env_kwargs["termination"]
+    if "initial_state" in env_kwargs:
+        cfg["initial_state"] = env_kwargs["initial_state"]
     return cfg
 
 

@@ -132,6 +132,16 @@ class HumanoidVecEnv(_Base):
             if len(self.batch._groups) != 1:
                 raise NotImplementedError("a termination condition steps one stream group (groups=1)")
             self._termination = self.batch.set_termination(rec.name, tparams, grace, fused=self._termination_fused)
+        # env_config["initial_state"] = {"keyframe": "squat"} / {"keyframes": [...]} / {"trajectory": path} /
+        # {"states": (qpos, qvel)} (initial_state.build_bank): every reset, the auto-resets inside fused launches
+        # included, starts from a row of that bank, drawn per episode on the device.  Absent or None: nothing
+        # changes.  An unknown key or keyframe name raises here.
+        self._noise_scale = 0.01
+        if cfg.get("initial_state") is not None:
+            from .initial_state import build_bank, noise_scale_of
+            self.batch.set_initial_states(*build_bank(self.model, cfg["initial_state"]))
+            self._noise_scale = noise_scale_of(cfg["initial_state"], self._noise_scale)
+            self.batch.configure(noise_scale=self._noise_scale)
         obs_space = Box(low=-np.inf, high=np.inf, shape=(self.batch.obs_dim,), dtype=np.float64)
         act_space = Box(low=-1, high=1, shape=(self.model.nu,), dtype=np.float32)
         super().__init__(n_envs, obs_space, act_space)
@@ -323,8 +333,8 @@ class HumanoidVecEnv(_Base):
         qn, vn = np.zeros((self.num_envs, m.nq)), np.zeros((self.num_envs, m.nv))
         for i in envs:
             r = self._streams[i]
-            qn[i] = r.uniform(low=-0.01, high=0.01, size=m.nq)
-            vn[i] = r.uniform(low=-0.01, high=0.01, size=m.nv)
+            qn[i] = r.uniform(low=-self._noise_scale, high=self._noise_scale, size=m.nq)
+            vn[i] = r.uniform(low=-self._noise_scale, high=self._noise_scale, size=m.nv)
         return qn, vn
 
     def _bind_next_noise(self):
