@@ -319,6 +319,8 @@ struct Compiler {
     for (int k = 0; k < 5; k++) m.geom_solimp.push_back(si[k]);
     m.geom_margin.push_back(getv(a, "margin", {0})[0]);
     m.geom_gap.push_back(getv(a, "gap", {0})[0]);
+    // MuJoCo leaves contacts with dist >= margin - gap out of the constraint rows; the step kernels do not
+    if (m.geom_gap.back() != 0) { err = "nonzero geom gap not supported"; return false; }
     m.geom_solmix.push_back(getv(a, "solmix", {1})[0]);
     double r = size.empty() ? 0 : size[0];
     m.geom_rbound.push_back(type == GEOM_PLANE ? 0 : type == GEOM_SPHERE ? r : r + size[1]);
@@ -1220,8 +1222,7 @@ bool build_dev_model(const HostModel& m, DevModel<T>& d, std::string& err) {
     d.pair_size[p][2] = (T)m.geom_size[3 * g2]; d.pair_size[p][3] = (T)m.geom_size[3 * g2 + 1];
     d.pair_mu[p] = (T)mu;
     d.pair_margin[p] = (T)(std::max(m.geom_margin[g1], m.geom_margin[g2]) - std::max(m.geom_gap[g1], m.geom_gap[g2]));
-    if (std::max(m.geom_margin[g1], m.geom_margin[g2]) != 0) { err = "nonzero geom margin not supported"; return false; }
-    for (int k = 0; k < 2; k++) d.pair_solref[p][k] = (T)sr[k];
+    if (std::max(m.geom_margin[g1], m.geom_margin[g2]) != 0) { err = "nonzero geom margin not supported"; return false; }    for (int k = 0; k < 2; k++) d.pair_solref[p][k] = (T)sr[k];
     fill_solimp(d.pair_solimp[p], si);
   }
   for (int t = 0; t < m.ntendon; t++) {

@@ -378,6 +378,9 @@ def compile_mjcf(path):
         M["geom_" + k] = np.array([g[k] for g in geoms])
     for k in ("margin", "gap", "solmix"):
         M["geom_" + k] = np.array([g[k] for g in geoms])
+    if np.any(M["geom_gap"] != 0):
+        # MuJoCo leaves contacts with dist >= margin - gap out of the constraint rows; the oracle does not
+        raise ValueError("nonzero geom gap not supported")
     rb = []
     for g in geoms:
         rb.append(0.0 if g["type"] == GEOM_PLANE else (g["size"][0] if g["type"] == GEOM_SPHERE else g["size"][0] + g["size"][1]))

@@ -37,20 +37,25 @@ def _qmul(a, b):
     return np.r_[a[0] * b[0] - a[1:] @ b[1:], a[0] * b[1:] + b[0] * a[1:] + np.cross(a[1:], b[1:])]
 
 
-def lying_states(o, n, seed, overflow=True, cap=(32, 128)):
-    """Prone / supine / on-the-side humanoids pressed into the floor; with overflow=True only
-    states whose contacts or rows exceed the resident tier ``cap`` (ncon, nefc) are kept."""
-    M = o.M
+def lying_poses(M, seed, draws=20000):
+    """The pose generator of lying_states: ``draws`` random lying poses of model M."""
     rng = np.random.default_rng(seed)
     lo, hi = M["jnt_range"][1:, 0], M["jnt_range"][1:, 1]
-    out = []
-    for _ in range(20000):
+    for _ in range(draws):
         q = M["qpos0"].copy()
         q[3:7] = _qmul(_qaxis([0, 0, 1], rng.uniform(-np.pi, np.pi)),
                        _qmul(_qaxis([0, 1, 0], np.pi / 2 * rng.choice([-1, 1])),
                              _qaxis([1, 0, 0], rng.uniform(-np.pi, np.pi))))
         q[7:] = np.clip(rng.uniform(0, 0.3) * rng.normal(size=21), lo, hi)
         q[2] = rng.uniform(0.0, 0.2)
+        yield q
+
+
+def lying_states(o, n, seed, overflow=True, cap=(32, 128)):
+    """Prone / supine / on-the-side humanoids pressed into the floor; with overflow=True only
+    states whose contacts or rows exceed the resident tier ``cap`` (ncon, nefc) are kept."""
+    out = []
+    for q in lying_poses(o.M, seed):
         o.reset_data()
         o.qpos[:] = q
         o.qvel[:] = 0
