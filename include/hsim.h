@@ -719,6 +719,72 @@ int hs_termination_eval_host(const hs_reward_program* predicate, const double* p
                              const hs_reward_fields* fields, const int32_t* episode, int32_t* count,
                              int32_t* episode_tag, uint8_t* early);
 
+/* Reference-motion targets <- the recording an episode started from (hs_set_initial_states binds it as a start
+ * distribution), visible to rewards and termination conditions: "be where the recording is NOW", "hold the
+ * keyframe you started from", "end the episode once you have drifted off the recording".  A batch may hold one
+ * REFERENCE MOTION: n_rows = K >= 1 rows qpos [K][nq] / qvel [K][nv] (HOST doubles; qvel NULL: zeros), key_dt > 0
+ * seconds between consecutive rows (required with K > 1, ignored with K == 1; the `time` attributes of recorded
+ * <key> elements are not trusted), an end mode and a start mode:
+ *   HS_REF_HOLD | HS_REF_LOOP              past the last row: stay on it | start over at row 0
+ *   HS_REF_START_ZERO | HS_REF_START_DRAWN  the episode's first row j0: 0 | the row its initial state drew,
+ *                                           min(K - 1, floor(u K)) of hs_set_initial_states (0 for episode 0)
+ * Programs read it as two more fields, ref_qpos [nq] and ref_qvel [nv] (field ids 16 and 17, a block of their own after
+ * subtree_linvel -- the ids 10 .. 15 stay unknown fields, left for state fields to come; hs_reward_program_info's
+ * mask reports them as bits 16 and 17), with the ordinary load instruction.  They are NOT
+ * members of hs_reward_fields, whose layout is unchanged: a sample is no array of the caller's but a pure
+ * function of (seed, env, episode[env], time[env]) and the rows, so nothing is carried between steps:
+ *   x  = (double)j0 + (double)time / key_dt        in double also for an fp32 batch; NaN or negative: 0
+ *   hold:  x = min(x, K - 1); i = floor(x); i1 = min(i + 1, K - 1)
+ *   loop:  x = min(x, 2^52);  i = floor(x) mod K; i1 = (i + 1) mod K
+ *   w  = (T)(x - floor(x));   ref[k] = a + w (b - a),  a = row_i[k], b = row_i1[k]
+ * each operation rounded in the batch precision T, never contracted; i and i1 lie in [0, K - 1] for every input.
+ * The free joint's quaternion of every row is normalised when bound (as hs_set_initial_states does), but the
+ * interpolated components are NOT renormalised: a program divides by the norm where it matters.
+ *
+ * hs_set_reference_motion: n_rows = 0 clears the binding.  The library converts the rows to the batch precision
+ * and owns the copy, by the rules of hs_set_initial_states: the call waits for the batch's pending launches,
+ * writes in place when the rows fit the blocks, otherwise allocates anew and keeps the old blocks until the batch
+ * is destroyed; a launch recorded into a HIP graph keeps the reference it was recorded with: re-record it after a
+ * rebind.  Refused (-1): n_rows outside [0, HS_MAX_REFERENCE_ROWS], NULL qpos, key_dt not finite or <= 0 with
+ * K > 1, unknown flag bits, a value that is not finite, a zero free-joint quaternion.
+ * A program that reads a reference field is refused BEFORE ANY LAUNCH by hs_reward_program_batch*, hs_step_program,
+ * hs_step / hs_apply_termination (the predicate) and hs_set_termination when the batch has no reference bound, and
+ * when the reference has HS_REF_START_DRAWN but no bank of initial states of the same n_rows is bound.  The
+ * entry points that take hs_reward_fields alone (hs_reward_program_eval, hs_reward_program_eval_host*,
+ * hs_termination_eval_host) refuse such a program and name the batch entry points.  A batch with a reference
+ * bound whose programs do not read it runs exactly the launches it ran before, fused ones included.
+ * hs_get_reference_motion: the rows bound (0: none), key_dt and the flags; any pointer may be NULL.
+ *
+ * hs_reward_program_eval_host_reference / hs_termination_eval_host_reference: the host interpreter with a
+ * reference (ref NULL: hs_reward_program_eval_host_components / hs_termination_eval_host).  The rows are used as
+ * given (not normalised); precision HS_FP32 computes the sample in float, as an fp32 batch does, and widens it.
+ * fields->time is required.  episode / seed [n]: each state's episode number and its batch's (group's) seed,
+ * required with HS_REF_START_DRAWN only; env [n]: each state's env index within that batch, NULL: 0 .. n-1. */
+#define HS_REF_HOLD 0
+#define HS_REF_LOOP 1
+#define HS_REF_START_ZERO 0
+#define HS_REF_START_DRAWN 2
+#define HS_MAX_REFERENCE_ROWS 4096
+typedef struct {
+  int n_rows;
+  const double* qpos;
+  const double* qvel;
+  double key_dt;
+  int flags;
+  int precision;
+  const int32_t* episode;
+  const uint64_t* seed;
+  const int32_t* env;
+} hs_reference_host;
+int hs_set_reference_motion(hs_batch* b, int n_rows, const double* qpos, const double* qvel, double key_dt, int flags);
+int hs_get_reference_motion(const hs_batch* b, int* n_rows, double* key_dt, int* flags);
+int hs_reward_program_eval_host_reference(const hs_reward_program* prog, const double* params, int n,
+                                          const hs_reward_fields* fields, const hs_reference_host* ref, double* out,
+                                          double* comp_out);
+int hs_termination_eval_host_reference(const hs_reward_program* predicate, const double* params, int grace_steps, int n,
+                                       const hs_reward_fields* fields, const hs_reference_host* ref,
+                                       const int32_t* episode, int32_t* count, int32_t* episode_tag, uint8_t* early);
+
 /* GAE(gamma, lambda) reverse scan over a device rollout buffer, SB3 semantics: [T][N] float32
  * rewards, values, episode_starts; [N] last_values, last_dones; writes [T][N] advantages and
  * returns (= advantages + values).  All pointers are device memory on the current device;

@@ -49,6 +49,9 @@ def __getattr__(name):
                 "termination_fused_from_config", "builtin_termination_eval_host"):
         from . import reward_program
         return getattr(reward_program, name)
+    if name in ("Reference", "build_reference"):
+        from . import reference_motion
+        return getattr(reference_motion, name)
     if name == "HsBatch":
         from .batch import HsBatch
         return HsBatch

@@ -91,6 +91,14 @@ REWARD_FIELD_MEMBER = {n: ("subtree_com0" if n == "subtree_com" else n)
 HS_RP_MAX_INSTR, HS_RP_MAX_SLOTS, HS_RP_MAX_CONSTS, HS_RP_MAX_PARAMS = 4096, 64, 256, 32
 HS_RP_MAX_OUTPUTS = 16
 HS_MAX_INITIAL_STATES = 4096     # most rows of a bank of initial states (hs_set_initial_states)
+HS_REF_HOLD, HS_REF_LOOP, HS_REF_START_ZERO, HS_REF_START_DRAWN = 0, 1, 0, 2   # hs_set_reference_motion flags
+HS_MAX_REFERENCE_ROWS = 4096
+
+
+class hs_reference_host(C.Structure):
+    _fields_ = [("n_rows", C.c_int), ("qpos", C.c_void_p), ("qvel", C.c_void_p), ("key_dt", C.c_double),
+                ("flags", C.c_int), ("precision", C.c_int), ("episode", C.c_void_p), ("seed", C.c_void_p),
+                ("env", C.c_void_p)]
 
 
 class hs_batch_info(C.Structure):
@@ -152,6 +160,10 @@ def lib():
         "hs_set_autoreset_noise": (i, [vp, vp, vp]),
         "hs_set_initial_states": (i, [vp, i, vp, vp]),
         "hs_get_initial_states": (i, [vp, vp]),
+        "hs_set_reference_motion": (i, [vp, i, vp, vp, d, i]),
+        "hs_get_reference_motion": (i, [vp, vp, vp, vp]),
+        "hs_reward_program_eval_host_reference": (i, [vp, vp, i, vp, vp, vp, vp]),
+        "hs_termination_eval_host_reference": (i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp]),
         "hs_physics_step": (i, [vp, vp, i, vp]),
         "hs_state_io": (i, [vp, i, vp, vp, vp, vp, vp]),
         "hs_kinematics": (i, [vp, i, vp, vp, vp, vp, vp, vp]),
@@ -249,7 +261,9 @@ EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_t
             "hs_set_termination_builtin", "hs_termination_builtin_eval_host",
             "hs_reward_program_create_components", "hs_reward_program_outputs",
             "hs_reward_program_eval_host_components", "hs_reward_program_batch_components",
-            "hs_set_reward_components", "hs_set_initial_states", "hs_get_initial_states")
+            "hs_set_reward_components", "hs_set_initial_states", "hs_get_initial_states",
+            "hs_set_reference_motion", "hs_get_reference_motion", "hs_reward_program_eval_host_reference",
+            "hs_termination_eval_host_reference")
 
 
 class HsimError(RuntimeError):

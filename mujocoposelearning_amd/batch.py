@@ -405,6 +405,78 @@ class HsBatch:
         out[ep == 0] = -1
         return out
 
+    # -- what rewards and termination conditions compare against (hs_set_reference_motion) ------
+    def set_reference_motion(self, qpos=None, qvel=None, key_dt=None, end="hold", start="zero"):
+        """Bind the reference motion that reward and termination programs read as ``d.ref_qpos`` / ``d.ref_qvel``
+        (``reference_motion.py``): ``qpos`` [K, nq] and ``qvel`` [K, nv] (None: zeros) as host arrays, ``key_dt``
+        seconds between rows (required with K > 1), ``end`` ``"hold"`` | ``"loop"``, ``start`` ``"zero"`` |
+        ``"drawn"`` -- or one ``reference_motion.Reference`` as the first argument.  ``qpos`` None unbinds.  Each
+        group gets the same rows and draws with its own seed.  ``start="drawn"`` needs a bank of initial states of
+        the same K bound by the time a program that reads the reference is launched (checked then, before the
+        launch).  The call waits for the batch's pending launches; a trainer that replays a recorded per-step graph
+        re-records it (``launch_generation``).  A batch whose programs do not read the reference runs exactly the
+        launches it ran before.  ValueError / HsimError: rows of the wrong length, a value that is not finite, a zero
+        quaternion, more than ``HS_MAX_REFERENCE_ROWS`` rows, a missing ``key_dt``, an unknown mode."""
+        from .reference_motion import Reference
+        if qpos is None:
+            self.launch_generation += 1
+            for h, _, _ in self._groups:
+                check(lib().hs_set_reference_motion(h, 0, None, None, 0.0, 0))
+            self._reference_motion = None
+            return None
+        nq, nv = self.model.nq, self.model.nv
+        ref = qpos if isinstance(qpos, Reference) else Reference(qpos, qvel, key_dt, end, start, nv=nv)
+        if ref.qpos.shape[1] != nq or ref.qvel.shape[1] != nv:
+            raise _lib.HsimError(f"set_reference_motion: rows must be [K, {nq}] / [K, {nv}], got "
+                                 f"{ref.qpos.shape} / {ref.qvel.shape}")
+        self.launch_generation += 1
+        q, v = np.ascontiguousarray(ref.qpos), np.ascontiguousarray(ref.qvel)
+        for h, _, _ in self._groups:
+            check(lib().hs_set_reference_motion(h, ref.K, q.ctypes.data, v.ctypes.data,
+                                                1.0 if ref.key_dt is None else ref.key_dt, ref.flags))
+        # the rows as the library holds them: it normalises the quaternions of what it is given once more, by the
+        # expression of initial_state.normalize_quaternions, which moves an already normalised one by an ulp at most
+        self._reference_motion = Reference(ref.qpos, ref.qvel, ref.key_dt, ref.end, ref.start)
+        return self._reference_motion
+
+    @property
+    def reference_motion(self):
+        """The bound ``reference_motion.Reference``, or None: the float64 rows as the library holds them (it
+        normalises the quaternions once more when it binds them, so they may differ from the rows given in the last
+        bit; an fp32 batch holds them rounded to float32).  ``reference_motion.sample`` of THIS object is bitwise
+        what the device reads."""
+        return self.__dict__.get("_reference_motion")
+
+    def _group_seeds_env(self):
+        """Per env: its group's seed (a list of ints) and its index within the group ([N] int64)."""
+        seeds, env = [0] * self.n, np.zeros(self.n, dtype=np.int64)
+        for g, (_, lo, hi) in enumerate(self._groups):
+            seeds[lo:hi] = [self._group_seed(g)] * (hi - lo)
+            env[lo:hi] = np.arange(hi - lo)
+        return seeds, env
+
+    def reference_phase(self):
+        """[N] float64 host array: each env's phase x on the bound reference at its current ``episode`` and ``time``
+        -- start row + time / key_dt after its clamps, the value whose floor indexes the rows
+        (``reference_motion.phase``, the host restatement of what the kernel computes).  HsimError with none bound."""
+        from .reference_motion import phase
+        ref = self.reference_motion
+        if ref is None:
+            raise _lib.HsimError("reference_phase: the batch has no reference motion bound (set_reference_motion)")
+        seeds, env = self._group_seeds_env()
+        return phase(ref, self.t["time"].cpu().numpy(), self.t["episode"].cpu().numpy(), seeds, env)[0]
+
+    def reference_sample(self):
+        """(ref_qpos [N, nq], ref_qvel [N, nv]) host arrays of the batch dtype: what a program launched now would read
+        (``reference_motion.sample`` at the envs' current ``episode`` and ``time``)."""
+        from .reference_motion import sample
+        ref = self.reference_motion
+        if ref is None:
+            raise _lib.HsimError("reference_sample: the batch has no reference motion bound (set_reference_motion)")
+        seeds, env = self._group_seeds_env()
+        return sample(ref, self.t["time"].cpu().numpy(), self.t["episode"].cpu().numpy(), seeds, env,
+                      dtype=np.float64 if self.precision == "fp64" else np.float32)
+
     def _group_seed(self, g):
         return (int(self._seed) + 0x9E3779B97F4A7C15 * g) & (2 ** 64 - 1)
 

@@ -454,9 +454,11 @@ void hs_batch_destroy(hs_batch* b) {
     for (const BufRow& r : buffer_rows(b))
       if (*r.slot) (void)hipFree(*r.slot);
   for (void* p : {b->dmodel, b->dbg, (void*)b->redo, (void*)b->redo_total, (void*)b->prog_done, (void*)b->grace_count,
-                  (void*)b->grace_episode, (void*)b->early, b->tape_backup, (void*)b->kin_envs, b->init_q, b->init_v})
+                  (void*)b->grace_episode, (void*)b->early, b->tape_backup, (void*)b->kin_envs, b->init_q, b->init_v,
+                  b->ref_q, b->ref_v})
     if (p) (void)hipFree(p);
   for (void* p : b->init_retired) (void)hipFree(p);
+  for (void* p : b->ref_retired) (void)hipFree(p);
   hs::uc_release(b->device, (size_t)b->n * sizeof(int32_t), b->mid_count);
   if (b->mid) hs::uc_release(b->device, (size_t)b->n * hs::MIDDIM * hs::elem_size(b), b->mid);
   if (b->qsync) hs::uc_release(b->device, hs::qsync_words(b->n) * sizeof(int), b->qsync);

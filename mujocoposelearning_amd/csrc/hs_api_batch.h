@@ -79,6 +79,14 @@ struct hs_batch {
   void* init_v = nullptr;                    // [init_cap][nv]
   int init_n = 0, init_cap = 0;
   std::vector<void*> init_retired;
+  // hs_set_reference_motion: the reference motion reward and termination programs sample (ref_qpos / ref_qvel), in
+  // the batch precision: ref_n rows bound (0: none) of the ref_cap the two blocks hold, key_dt seconds apart, the
+  // HS_REF_* flags.  Bound and rebound by the rules of the initial-state bank above.
+  void* ref_q = nullptr;                     // [ref_cap][nq]
+  void* ref_v = nullptr;                     // [ref_cap][nv]
+  int ref_n = 0, ref_cap = 0, ref_flags = 0;
+  double ref_key_dt = 0.0;
+  std::vector<void*> ref_retired;
 };
 
 // a validated reward program (hs_reward_prog.h) and its copies in device memory, one per device it ran on

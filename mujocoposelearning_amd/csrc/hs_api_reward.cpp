@@ -9,6 +9,10 @@ static_assert(HS_RP_MAX_INSTR == hs::RP_MAX_INSTR && HS_RP_MAX_SLOTS == hs::RP_M
                   HS_RP_MAX_OUTPUTS == hs::RP_MAX_OUTPUTS,
               "include/hsim.h reward program limits");
 static_assert(sizeof(hs_reward_fields) == hs::RP_NFIELDS * sizeof(void*), "hs_reward_fields: one pointer per field");
+static_assert(HS_REF_HOLD == hs::RP_REF_HOLD && HS_REF_LOOP == hs::RP_REF_LOOP &&
+                  HS_REF_START_ZERO == hs::RP_REF_START_ZERO && HS_REF_START_DRAWN == hs::RP_REF_START_DRAWN &&
+                  HS_MAX_REFERENCE_ROWS == hs::RP_REF_MAX_ROWS,
+              "include/hsim.h reference motion flags");
 static_assert(HS_TERM_FALLEN == hs::TERM_FALLEN && HS_TERM_LOST_BALANCE == hs::TERM_LOST_BALANCE, "built-in kinds");
 
 namespace {
@@ -35,12 +39,29 @@ hs::RewardEvalArgs<T> reward_eval_args(const hs::HostModel& h, int reward_id, in
 }
 
 // -- reward programs (hs_reward_prog.h) --------------------------------------------------------
-const char* const kRpFieldNames[hs::RP_NFIELDS] = {"qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel",
-                                                   "subtree_com[0]", "cfrc_ext", "subtree_linvel"};
+const char* const kRpFieldNames[hs::RP_NFIELDS_ALL] = {
+    "qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel", "subtree_com[0]", "cfrc_ext", "subtree_linvel",
+    "", "", "", "", "", "",   // (ids 10 .. 15: no field)
+    "ref_qpos", "ref_qvel"};
+static_assert(hs::RP_F_REF_QPOS == 16 && hs::RP_NFIELDS_ALL == 18, "kRpFieldNames follows RpField");
 
-// every field the program (`noun`: "program" / "predicate") reads must be given; `who`: the entry point's name
-int rp_check_fields(const char* who, const char* noun, const hs_reward_program* p, const hs_reward_fields* f) {
+// the reference field a program reads, by name ("" when it reads none)
+std::string rp_ref_field_read(const hs_reward_program* p) {
+  for (int k = hs::RP_F_REF_QPOS; k < hs::RP_NFIELDS_ALL; k++)
+    if (p->info.fields & (1u << k)) return kRpFieldNames[k];
+  return "";
+}
+
+// every field the program (`noun`: "program" / "predicate") reads must be given; `who`: the entry point's name.
+// A reference field has no member of hs_reward_fields: with_ref tells whether the entry point was given a reference
+int rp_check_fields(const char* who, const char* noun, const hs_reward_program* p, const hs_reward_fields* f,
+                    bool with_ref = false) {
   const void* const* fp = reinterpret_cast<const void* const*>(f);
+  if (!with_ref && (p->info.fields & hs::RP_REF_FIELDS))
+    return fail(std::string(who) + ": the " + noun + " reads " + rp_ref_field_read(p) +
+                ", a sample of a reference motion, which hs_reward_fields does not carry: evaluate it on a batch with "
+                "one bound (hs_set_reference_motion; hs_reward_program_batch, hs_step_program) or on the host with "
+                "hs_reward_program_eval_host_reference");
   for (int k = 0; k < hs::RP_NFIELDS; k++)
     if ((p->info.fields & (1u << k)) && !fp[k])
       return fail(std::string(who) + ": the " + noun + " reads " + kRpFieldNames[k] + ", which is NULL");
@@ -109,6 +130,23 @@ void rp_batch_fields(const hs_batch* b, hs::RpArgs<T>& a) {
   set(hs::RP_F_LINVEL, b->full_state ? b->buf.subtree_linvel : nullptr, 3 * h.nbody);
 }
 
+// the batch's reference motion for a launch whose programs read `fields`: set only when one of them reads a
+// reference field (rp_check_batch has checked that it is bound), so that any other launch is what it was
+template <typename T>
+void rp_batch_ref(const hs_batch* b, unsigned fields, hs::RpArgs<T>& a) {
+  if (!(fields & hs::RP_REF_FIELDS)) return;
+  a.ref.q = (const T*)b->ref_q;
+  a.ref.v = (const T*)b->ref_v;
+  a.ref.K = b->ref_n;
+  a.ref.flags = b->ref_flags;
+  a.ref.nq = b->model->host.nq;
+  a.ref.nv = b->model->host.nv;
+  a.ref.key_dt = b->ref_key_dt;
+  a.ref.seed = b->seed;
+  a.ref.time = (const T*)b->buf.time;
+  a.ref.episode = (const int32_t*)b->buf.episode;
+}
+
 // what a program needs of a batch before anything is launched; `stepped`: the check runs ahead of the
 // step that will write the outputs (hs_step_program), so a stale data.ctrl does not matter
 int rp_check_batch(const char* who, const hs_batch* b, const hs_reward_program* p, const double* params, bool stepped) {
@@ -126,6 +164,15 @@ int rp_check_batch(const char* who, const hs_batch* b, const hs_reward_program* 
   if (b->full_state && (f & ((1u << hs::RP_F_CFRC) | (1u << hs::RP_F_LINVEL))) &&
       (!b->buf.cfrc_ext || !b->buf.subtree_linvel))
     return fail(w + ": the batch has no cfrc_ext / subtree_linvel buffers");
+  if (f & hs::RP_REF_FIELDS) {
+    if (b->ref_n <= 0)
+      return fail(w + ": the program reads " + rp_ref_field_read(p) +
+                  ", but the batch has no reference motion bound (hs_set_reference_motion)");
+    if ((b->ref_flags & HS_REF_START_DRAWN) && b->init_n != b->ref_n)
+      return fail(w + ": the reference motion starts at the drawn row (HS_REF_START_DRAWN), which needs a bank of "
+                  "initial states of the same " + std::to_string(b->ref_n) + " rows bound (hs_set_initial_states); " +
+                  (b->init_n > 0 ? "the bank bound has " + std::to_string(b->init_n) : std::string("none is bound")));
+  }
   return 0;
 }
 
@@ -145,6 +192,7 @@ int outcome_launch(hs_batch* b, const hs_reward_program* p, const double* params
     a.n_slots = std::max(p ? p->info.n_slots : 1, t ? t->info.n_slots : 1);
     a.n = b->n;
     rp_batch_fields<T>(b, a);
+    rp_batch_ref<T>(b, (p ? p->info.fields : 0u) | (t ? t->info.fields : 0u), a);
     a.outcome = 1;
     a.reward = (T*)b->buf.reward;
     a.total_reward = (T*)b->buf.total_reward;
@@ -173,6 +221,56 @@ int outcome_launch(hs_batch* b, const hs_reward_program* p, const double* params
     }
     return hip_rc(hs::launch_reward_program<T>(a, (hipStream_t)stream), "reward_program_kernel");
   });
+}
+
+// A reference row's free-joint quaternion divided by its norm; false for a zero one.  Never contracted: the
+// expression numpy evaluates (initial_state.normalize_quaternions), bit for bit, so that the host can state the
+// rows the device holds (HsBatch.reference_motion) and a sample of them exactly.
+bool ref_normalize_quat(double* r) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double ww = r[3] * r[3], xx = r[4] * r[4], yy = r[5] * r[5], zz = r[6] * r[6];
+  const double norm = std::sqrt(((ww + xx) + yy) + zz);
+  if (!(norm >= 1e-15)) return false;
+  for (int c = 3; c < 7; c++) r[c] = r[c] / norm;
+  return true;
+}
+
+// The flags of a reference motion, checked (`who`: the entry point's name).
+int ref_check_flags(const std::string& who, int flags) {
+  if (flags & ~(HS_REF_LOOP | HS_REF_START_DRAWN))
+    return fail(who + ": flags " + std::to_string(flags) + " hold a bit that is neither HS_REF_LOOP (1) nor "
+                "HS_REF_START_DRAWN (2)");
+  return 0;
+}
+
+// a host caller's reference for a program that reads one, checked and turned into the interpreter's RpRefHost
+int ref_host(const char* who_c, const hs_reward_program* p, const hs_reward_fields* f, const hs_reference_host* ref,
+             hs::RpRefHost* r) {
+  const std::string who(who_c);
+  if (ref->n_rows < 1 || ref->n_rows > HS_MAX_REFERENCE_ROWS)
+    return fail(who + ": the program reads " + rp_ref_field_read(p) + ", the reference needs n_rows in [1, " +
+                std::to_string(HS_MAX_REFERENCE_ROWS) + "], got " + std::to_string(ref->n_rows));
+  if (!ref->qpos) return fail(who + ": the reference's qpos must not be NULL");
+  if (ref->n_rows > 1 && !(ref->key_dt > 0.0 && std::isfinite(ref->key_dt)))
+    return fail(who + ": key_dt must be finite and > 0 with more than one row");
+  if (ref_check_flags(who, ref->flags)) return -1;
+  const int prec = ref->precision & 0xFF;
+  if (prec != HS_FP32 && prec != HS_FP64) return fail(who + ": the reference's precision must be HS_FP32 or HS_FP64");
+  if (!f->time) return fail(who + ": a reference is sampled at the state's time, which is NULL");
+  if ((ref->flags & HS_REF_START_DRAWN) && (!ref->episode || !ref->seed))
+    return fail(who + ": HS_REF_START_DRAWN needs the per-state episode and seed arrays");
+  r->K = ref->n_rows;
+  r->qpos = ref->qpos;
+  r->qvel = ref->qvel;
+  r->key_dt = ref->key_dt;
+  r->flags = ref->flags;
+  r->fp32 = prec == HS_FP32;
+  r->episode = ref->episode;
+  r->seed = ref->seed;
+  r->env = ref->env;
+  return 0;
 }
 
 // a predicate is read as one truth value: a program with named outputs is a reward, refused as a condition
@@ -335,15 +433,25 @@ int hs_reward_program_info(const hs_reward_program* p, int* n_instr, int* n_slot
 
 int hs_reward_program_eval_host_components(const hs_reward_program* p, const double* params, int n,
                                            const hs_reward_fields* f, double* out, double* comp_out) {
-  if (!p || !f) return fail("hs_reward_program_eval_host: null argument");
-  if (n < 0) return fail("hs_reward_program_eval_host: negative n");
+  return hs_reward_program_eval_host_reference(p, params, n, f, nullptr, out, comp_out);
+}
+
+int hs_reward_program_eval_host_reference(const hs_reward_program* p, const double* params, int n,
+                                          const hs_reward_fields* f, const hs_reference_host* ref, double* out,
+                                          double* comp_out) {
+  const char* who = ref ? "hs_reward_program_eval_host_reference" : "hs_reward_program_eval_host";
+  if (!p || !f) return fail(std::string(who) + ": null argument");
+  if (n < 0) return fail(std::string(who) + ": negative n");
   if (comp_out && p->info.n_outputs == 0)
     return fail("hs_reward_program_eval_host_components: the program has no outputs, comp_out must be NULL");
+  hs::RpRefHost r;
+  const bool reads_ref = (p->info.fields & hs::RP_REF_FIELDS) != 0;
+  if (ref && reads_ref && ref_host(who, p, f, ref, &r)) return -1;
   if (n == 0) return 0;
-  if (!out || (p->n_params > 0 && !params)) return fail("hs_reward_program_eval_host: null out or params");
-  if (rp_check_fields("hs_reward_program_eval_host", "program", p, f)) return -1;
+  if (!out || (p->n_params > 0 && !params)) return fail(std::string(who) + ": null out or params");
+  if (rp_check_fields(who, "program", p, f, ref != nullptr)) return -1;
   hs::rp_eval_host(p->dims, p->code.data(), (int)(p->code.size() / 5), p->consts.data(), params, n,
-                   reinterpret_cast<const double* const*>(f), out, comp_out);
+                   reinterpret_cast<const double* const*>(f), out, comp_out, ref && reads_ref ? &r : nullptr);
   return 0;
 }
 
@@ -421,6 +529,7 @@ int hs_reward_program_batch_components(hs_batch* b, const hs_reward_program* p, 
     using T = decltype(zero);
     hs::RpArgs<T> a = rp_args<T>(p, d, params, b->n);
     rp_batch_fields<T>(b, a);
+    rp_batch_ref<T>(b, p->info.fields, a);
     a.out = (T*)out;
     a.comp = (T*)comp_out;
     a.n_outputs = p->info.n_outputs;
@@ -483,7 +592,7 @@ int hs_set_termination_builtin(hs_batch* b, const hs_reward_program* pred, const
   // on the probe rows (hs_term_builtin.h) -- refused before anything is set or launched
   if (pred->info.fields & ~(1u << hs::RP_F_QPOS)) {
     std::string names;
-    for (int k = 0; k < hs::RP_NFIELDS; k++)
+    for (int k = 0; k < hs::RP_NFIELDS_ALL; k++)
       if (k != hs::RP_F_QPOS && (pred->info.fields & (1u << k))) names += std::string(names.empty() ? "" : ", ") + kRpFieldNames[k];
     return fail(who + ": the predicate reads " + names + "; a built-in condition is a function of qpos alone");
   }
@@ -542,17 +651,98 @@ int hs_apply_termination(hs_batch* b, void* stream) {
 int hs_termination_eval_host(const hs_reward_program* pred, const double* params, int grace_steps, int n,
                              const hs_reward_fields* f, const int32_t* episode, int32_t* count, int32_t* episode_tag,
                              uint8_t* early) {
+  return hs_termination_eval_host_reference(pred, params, grace_steps, n, f, nullptr, episode, count, episode_tag, early);
+}
+
+int hs_termination_eval_host_reference(const hs_reward_program* pred, const double* params, int grace_steps, int n,
+                                       const hs_reward_fields* f, const hs_reference_host* ref, const int32_t* episode,
+                                       int32_t* count, int32_t* episode_tag, uint8_t* early) {
   if (term_refuse_outputs("hs_termination_eval_host", pred)) return -1;
   if (!pred || !f) return fail("hs_termination_eval_host: null argument");
+  hs::RpRefHost r;
+  const bool reads_ref = (pred->info.fields & hs::RP_REF_FIELDS) != 0;
+  if (ref && reads_ref && ref_host("hs_termination_eval_host_reference", pred, f, ref, &r)) return -1;
   if (n < 0) return fail("hs_termination_eval_host: negative n");
   if (grace_steps < 1) return fail("hs_termination_eval_host: grace_steps must be >= 1");
   if (n == 0) return 0;
   if (!episode || !count || !episode_tag || !early || (pred->n_params > 0 && !params))
     return fail("hs_termination_eval_host: null episode, count, episode_tag, early or params");
-  if (rp_check_fields("hs_termination_eval_host", "predicate", pred, f)) return -1;
+  if (rp_check_fields("hs_termination_eval_host", "predicate", pred, f, ref != nullptr)) return -1;
   hs::rp_termination_eval_host(pred->dims, pred->code.data(), (int)(pred->code.size() / 5), pred->consts.data(), params,
                                grace_steps, n, reinterpret_cast<const double* const*>(f), episode, count, episode_tag,
-                               early);
+                               early, ref && reads_ref ? &r : nullptr);
+  return 0;
+}
+
+int hs_set_reference_motion(hs_batch* b, int n_rows, const double* qpos, const double* qvel, double key_dt, int flags) {
+  const std::string who = "hs_set_reference_motion";
+  if (!b) return fail(who + ": null batch");
+  if (n_rows < 0 || n_rows > HS_MAX_REFERENCE_ROWS)
+    return fail(who + ": n_rows " + std::to_string(n_rows) + " must lie in [0, HS_MAX_REFERENCE_ROWS = " +
+                std::to_string(HS_MAX_REFERENCE_ROWS) + "]");
+  if (n_rows == 0) {   // unbind: the blocks stay for the next bind
+    b->ref_n = 0;
+    return 0;
+  }
+  if (!qpos) return fail(who + ": qpos must not be NULL with n_rows > 0");
+  if (n_rows > 1 && !(key_dt > 0.0 && std::isfinite(key_dt)))
+    return fail(who + ": key_dt must be finite and > 0 with more than one row (the seconds between consecutive rows)");
+  if (ref_check_flags(who, flags)) return -1;
+  const auto& h = b->model->host;
+  const size_t K = (size_t)n_rows, nq = (size_t)h.nq, nv = (size_t)h.nv;
+  std::vector<double> q(qpos, qpos + K * nq), v(K * nv, 0.0);
+  if (qvel) v.assign(qvel, qvel + K * nv);
+  for (size_t i = 0; i < q.size(); i++)
+    if (!std::isfinite(q[i]))
+      return fail(who + ": qpos[" + std::to_string(i / nq) + "][" + std::to_string(i % nq) + "] is not finite");
+  for (size_t i = 0; i < v.size(); i++)
+    if (!std::isfinite(v[i]))
+      return fail(who + ": qvel[" + std::to_string(i / nv) + "][" + std::to_string(i % nv) + "] is not finite");
+  // the free joint's quaternion, normalised as hs_set_initial_states normalises a bank's
+  if (h.njnt > 0 && h.jnt_type[0] == hs::JNT_FREE && nq >= 7)
+    for (size_t j = 0; j < K; j++)
+      if (!ref_normalize_quat(q.data() + j * nq))
+        return fail(who + ": row " + std::to_string(j) + " has a zero free-joint quaternion");
+  DeviceGuard g(b->device);
+  // after the batch's pending launches, whatever stream they are on (they may read the rows written below)
+  if (!hip_ok(hipDeviceSynchronize(), "hs_set_reference_motion")) return -1;
+  const size_t es = hs::elem_size(b);
+  if (n_rows > b->ref_cap) {
+    void *q_blk = nullptr, *v_blk = nullptr;
+    const int cap = std::min(HS_MAX_REFERENCE_ROWS, std::max(n_rows, 2 * b->ref_cap));
+    if (!hip_ok(hipMalloc(&q_blk, (size_t)cap * nq * es), "hipMalloc(reference motion)") ||
+        !hip_ok(hipMalloc(&v_blk, (size_t)cap * nv * es), "hipMalloc(reference motion)")) {
+      if (q_blk) (void)hipFree(q_blk);
+      return -1;
+    }
+    if (b->ref_q) b->ref_retired.push_back(b->ref_q);
+    if (b->ref_v) b->ref_retired.push_back(b->ref_v);
+    b->ref_n = 0;
+    b->ref_q = q_blk;
+    b->ref_v = v_blk;
+    b->ref_cap = cap;
+  }
+  const bool ok = by_precision(b->precision, [&](auto zero) {
+    using T = decltype(zero);
+    const std::vector<T> tq(q.begin(), q.end()), tv(v.begin(), v.end());
+    return hip_ok(hipMemcpy(b->ref_q, tq.data(), tq.size() * sizeof(T), hipMemcpyHostToDevice), "reference qpos") &&
+           hip_ok(hipMemcpy(b->ref_v, tv.data(), tv.size() * sizeof(T), hipMemcpyHostToDevice), "reference qvel");
+  });
+  if (!ok) {
+    b->ref_n = 0;
+    return -1;
+  }
+  b->ref_n = n_rows;
+  b->ref_key_dt = n_rows > 1 ? key_dt : 1.0;
+  b->ref_flags = flags;
+  return 0;
+}
+
+int hs_get_reference_motion(const hs_batch* b, int* n_rows, double* key_dt, int* flags) {
+  if (!b) return fail("hs_get_reference_motion: null batch");
+  if (n_rows) *n_rows = b->ref_n;
+  if (key_dt) *key_dt = b->ref_n > 0 ? b->ref_key_dt : 0.0;
+  if (flags) *flags = b->ref_n > 0 ? b->ref_flags : 0;
   return 0;
 }
 

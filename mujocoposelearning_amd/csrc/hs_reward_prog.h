@@ -54,8 +54,16 @@ enum RpField : int32_t {
   RP_F_COM,        // subtree_com[0] [3] (the root's row: what the aux row holds)
   RP_F_CFRC,       // cfrc_ext [nbody][6]
   RP_F_LINVEL,     // subtree_linvel [nbody][3]
-  RP_NFIELDS
+  RP_NFIELDS,      // the fields a caller supplies as arrays: the members of hs_reward_fields
+  // the reference motion's sample at the env's own (episode, time) -- see "reference motion" below: no array of
+  // the caller's, computed from the bound rows; read with RP_LOAD like any field.  A block of its own at 16: the
+  // ids from RP_NFIELDS to 15 stay unknown fields, left for state fields to come
+  RP_F_REF_QPOS = 16,   // [nq]
+  RP_F_REF_QVEL,        // [nv]
+  RP_NFIELDS_ALL
 };
+inline bool rp_field_known(int f) { return (f >= 0 && f < RP_NFIELDS) || f == RP_F_REF_QPOS || f == RP_F_REF_QVEL; }
+constexpr unsigned RP_REF_FIELDS = (1u << RP_F_REF_QPOS) | (1u << RP_F_REF_QVEL);
 
 struct RpDims { int nq, nv, nu, nbody; };
 
@@ -71,6 +79,8 @@ inline int rp_field_len(const RpDims& d, int f) {
     case RP_F_COM: return 3;
     case RP_F_CFRC: return 6 * d.nbody;
     case RP_F_LINVEL: return 3 * d.nbody;
+    case RP_F_REF_QPOS: return d.nq;
+    case RP_F_REF_QVEL: return d.nv;
   }
   return 0;
 }
@@ -103,8 +113,10 @@ RP_HD inline T rp_tanh(T a) {
 // restated built-in equal reward_formula bitwise.  The device's libm is within 1.1 ulp in double and 2.3
 // ulp in float (profiles/reward_programs.md, "Op conformance"; tests/test_gpu_program_ops.py).
 // A comparison with a NaN is false (RP_NE: true); RP_WHERE selects, both arms are always evaluated.
+// (always inlined: the kernel's two instances, with and without reference fields, would otherwise share one
+// out-of-line copy, a call per instruction)
 template <typename T>
-RP_HD inline T rp_op(int op, T a, T b, T c) {
+RP_HD inline __attribute__((always_inline)) T rp_op(int op, T a, T b, T c) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -183,7 +195,7 @@ inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr
     if (op == RP_PARAM && (in[2] < 0 || in[2] >= n_params))
       return "reward program: parameter index " + std::to_string(in[2]) + " out of range" + at(i);
     if (op == RP_LOAD) {
-      if (in[2] < 0 || in[2] >= RP_NFIELDS) return "reward program: unknown field " + std::to_string(in[2]) + at(i);
+      if (!rp_field_known(in[2])) return "reward program: unknown field " + std::to_string(in[2]) + at(i);
       if (in[3] < 0 || in[3] >= rp_field_len(d, in[2]))
         return "reward program: field index " + std::to_string(in[3]) + " outside the model's dimensions (field " +
                std::to_string(in[2]) + " has " + std::to_string(rp_field_len(d, in[2])) + " values)" + at(i);
@@ -215,23 +227,131 @@ inline std::string rp_validate(const RpDims& d, const int32_t* code, int n_instr
   return rp_validate(d, code, n_instr, consts, n_consts, n_params, 0, info);
 }
 
+// -- reference motion (include/hsim.h hs_set_reference_motion) ------------------------------------
+// K rows qpos [K][nq] / qvel [K][nv], key_dt seconds apart.  ref_qpos / ref_qvel of an env are the rows'
+// linear interpolation at the env's phase x = j0 + time / key_dt: a pure function of (seed, env, episode, time)
+// and the bound table, so nothing is carried between steps.  The one definition, shared by the kernel and the
+// host interpreter and restated in numpy (reference_motion.sample).
+constexpr int RP_REF_HOLD = 0, RP_REF_LOOP = 1;              // past the last row: stay on it / start over
+constexpr int RP_REF_START_ZERO = 0, RP_REF_START_DRAWN = 2; // j0 = 0 / the row the episode's initial state drew
+constexpr int RP_REF_MAX_ROWS = 4096;
+constexpr int RP_REF_INIT_SLOT = 128;                        // hs_env_step.h INIT_SLOT
+
+// the step kernels' counter hash (hs_env_step.h splitmix / bank_row), restated so that this unit does not
+// include theirs: the bank row the reset of (seed, env, episode) drew, min(K - 1, floor(u K))
+RP_HD inline uint64_t rp_splitmix(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+RP_HD inline int rp_bank_row(uint64_t seed, int env, uint32_t ep, int K) {
+  const uint64_t h =
+      rp_splitmix(seed ^ rp_splitmix(((uint64_t)env << 32) ^ ((uint64_t)ep << 8) ^ (uint64_t)RP_REF_INIT_SLOT));
+  const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);   // [0, 1)
+  const int j = (int)(u * (double)K);
+  return j < K - 1 ? j : K - 1;
+}
+
+// The start row: 0, or with RP_REF_START_DRAWN the initial-state draw's own row (episode 0 was never reset: 0).
+RP_HD inline int rp_ref_start(int flags, uint64_t seed, int env, int32_t episode, int K) {
+  if (!(flags & RP_REF_START_DRAWN) || episode == 0) return 0;
+  return rp_bank_row(seed, env, (uint32_t)episode, K);
+}
+
+// The phase of one env: the two rows *i, *i1 in [0, K - 1] for EVERY input (NaN, +-inf, 1e300) and the weight
+// of the second in [0, 1).  Always in double, also for a float batch: the float build's divide is not correctly
+// rounded (Makefile KFLAGS) and the row index must not depend on that.  K == 1: the row itself, key_dt ignored.
+RP_HD inline double rp_ref_phase(int K, int flags, int j0, double time, double key_dt, int* i, int* i1) {
+  if (K <= 1) {
+    *i = *i1 = 0;
+    return 0.0;
+  }
+  double x = (double)j0 + time / key_dt;
+  if (!(x >= 0.0)) x = 0.0;                         // NaN or negative
+  if (flags & RP_REF_LOOP) {
+    if (!(x < 4503599627370496.0)) x = 4503599627370496.0;   // 2^52: beyond it a double has no fraction to index by
+    const double f = floor(x);
+    const int r = (int)((int64_t)f % (int64_t)K);
+    *i = r;
+    *i1 = r + 1 < K ? r + 1 : 0;
+    return x - f;
+  }
+  if (!(x < (double)(K - 1))) x = (double)(K - 1);
+  const double f = floor(x);
+  const int r = (int)f;
+  *i = r;
+  *i1 = r + 1 < K ? r + 1 : K - 1;
+  return x - f;
+}
+
+// The value: a + w (b - a), each operation rounded in T, never contracted; w == 0 gives a.  Quaternion components
+// are interpolated like any other coordinate and NOT renormalised: a program divides by the norm where it matters.
+template <typename T>
+RP_HD inline T rp_ref_value(T a, T b, T w) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const T d = b - a;
+  const T s = w * d;
+  return a + s;
+}
+
+// What the host interpreter samples a reference from: the rows as doubles (of a float batch: float values),
+// per-state episode numbers and seeds, the env index of state e (env ? env[e] : env_base + e); `fp32`: the
+// sample is computed in float, as a float batch's kernel does, and widened.  The time is the state's own time field.
+struct RpRefHost {
+  int K = 0;
+  const double* qpos = nullptr;   // [K][nq]
+  const double* qvel = nullptr;   // [K][nv], or NULL: zeros
+  double key_dt = 0;
+  int flags = 0;
+  bool fp32 = false;
+  const int32_t* episode = nullptr;
+  const uint64_t* seed = nullptr;
+  const int32_t* env = nullptr;
+  int env_base = 0;
+};
+
+inline double rp_ref_load_host(const RpDims& d, const RpRefHost& ref, int field, int index, int i, int i1, double w) {
+  const bool pos = field == RP_F_REF_QPOS;
+  const double* rows = pos ? ref.qpos : ref.qvel;
+  if (!rows) return 0.0;
+  const size_t ld = (size_t)(pos ? d.nq : d.nv);
+  const double a = rows[(size_t)i * ld + index], b = rows[(size_t)i1 * ld + index];
+  if (ref.fp32) return (double)rp_ref_value<float>((float)a, (float)b, (float)w);
+  return rp_ref_value<double>(a, b, w);
+}
+
 // The host interpreter: a VALIDATED program on n states in double.  field[f]: [n][rp_field_len(d, f)]
 // contiguous doubles, or NULL for a field the program does not read (checked by the caller).  comp_out: the
 // component sink, component-major [n_outputs][n] (component c of state e at c * n + e), or NULL: RP_OUT is then
-// a no-op.
+// a no-op.  ref: the reference motion, for a program that reads ref_qpos / ref_qvel (the caller has checked that
+// it is there, with the time field, episode and seed).
 inline void rp_eval_host(const RpDims& d, const int32_t* code, int n_instr, const double* consts, const double* params,
-                         int n, const double* const* field, double* out, double* comp_out = nullptr) {
+                         int n, const double* const* field, double* out, double* comp_out = nullptr,
+                         const RpRefHost* ref = nullptr) {
   int len[RP_NFIELDS];
   for (int f = 0; f < RP_NFIELDS; f++) len[f] = rp_field_len(d, f);
   for (int e = 0; e < n; e++) {
     double v[RP_MAX_SLOTS];
     double res = 0;
+    int ri = 0, ri1 = 0;
+    double rw = 0;
+    if (ref) {
+      int j0 = 0;   // (episode and seed are needed, and read, for a drawn start only)
+      if (ref->flags & RP_REF_START_DRAWN)
+        j0 = rp_ref_start(ref->flags, ref->seed[e], ref->env ? ref->env[e] : ref->env_base + e, ref->episode[e], ref->K);
+      rw = rp_ref_phase(ref->K, ref->flags, j0, field[RP_F_TIME][e], ref->key_dt, &ri, &ri1);
+      if (ref->fp32) rw = (double)(float)rw;
+    }
     for (int i = 0; i < n_instr; i++) {
       const int32_t* in = code + 5 * (size_t)i;
       const int op = in[0];
       double r;
       if (op == RP_CONST) r = consts[in[2]];
       else if (op == RP_PARAM) r = params[in[2]];
+      else if (op == RP_LOAD && in[2] >= RP_NFIELDS) r = ref ? rp_ref_load_host(d, *ref, in[2], in[3], ri, ri1, rw) : 0.0;
       else if (op == RP_LOAD) r = field[in[2]][(size_t)e * len[in[2]] + in[3]];
       else if (op == RP_RESULT) { res = v[in[2]]; break; }
       else if (op == RP_OUT) {
@@ -269,12 +389,21 @@ RP_HD inline int32_t rp_grace_update(int32_t stored_count, int32_t stored_episod
 // [n] are read and updated in place, episode [n] is each env's current episode number; early [n] out.
 inline void rp_termination_eval_host(const RpDims& d, const int32_t* code, int n_instr, const double* consts,
                                      const double* params, int grace_steps, int n, const double* const* field,
-                                     const int32_t* episode, int32_t* count, int32_t* episode_tag, uint8_t* early) {
+                                     const int32_t* episode, int32_t* count, int32_t* episode_tag, uint8_t* early,
+                                     const RpRefHost* ref = nullptr) {
   for (int e = 0; e < n; e++) {
     const double* one[RP_NFIELDS];
     for (int f = 0; f < RP_NFIELDS; f++) one[f] = field[f] ? field[f] + (size_t)e * rp_field_len(d, f) : nullptr;
     double v = 0;
-    rp_eval_host(d, code, n_instr, consts, params, 1, one, &v);
+    RpRefHost r1;   // state e's slice of the reference's per-state arrays
+    if (ref) {
+      r1 = *ref;
+      if (ref->episode) r1.episode = ref->episode + e;
+      if (ref->seed) r1.seed = ref->seed + e;
+      if (ref->env) r1.env = ref->env + e;
+      r1.env_base = ref->env_base + e;
+    }
+    rp_eval_host(d, code, n_instr, consts, params, 1, one, &v, nullptr, ref ? &r1 : nullptr);
     bool ends = false;
     count[e] = rp_grace_update(count[e], episode_tag[e], episode[e], rp_truth(v), grace_steps, &ends);
     episode_tag[e] = episode[e];
@@ -297,6 +426,20 @@ struct RpCode {
 // out[env] = the reward program's value.  outcome = 1 (hs_step_program, hs_step with a termination set,
 // hs_apply_termination; after a step without auto-reset): the env step's outcome rows, see the kernel --
 // `prog` the reward program or none (the step kernel's reward stays), `pred` the termination predicate or none.
+// The reference motion as the kernel sees it (the batch's, hs_set_reference_motion).  K = 0: the launch's programs
+// read no reference field -- the host sets K only from their field masks, and launch_reward_program then runs the
+// kernel instance that has no phase prologue and no reference load: the code a launch ran before the feature.
+template <typename T>
+struct RpRef {
+  const T* q;                 // [K][nq]
+  const T* v;                 // [K][nv]
+  int K, flags, nq, nv;
+  double key_dt;
+  uint64_t seed;
+  const T* time;              // [n]
+  const int32_t* episode;     // [n]
+};
+
 template <typename T>
 struct RpArgs {
   RpCode prog, pred;
@@ -332,6 +475,8 @@ struct RpArgs {
   int32_t* grace_episode;
   uint8_t* early;
   int grace_steps;
+  // the reference motion, for programs that read ref_qpos / ref_qvel (last: every other member keeps its offset)
+  RpRef<T> ref;
 };
 
 template <typename T>

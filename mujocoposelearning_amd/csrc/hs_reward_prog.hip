@@ -16,6 +16,13 @@
 // the same slots: the LDS is sized to the larger of the two.
 // A program's named components (RP_OUT) leave through component-major rows [C][n]: each RP_OUT is one
 // coalesced store per wave (env-major rows would be strided by C).  See RpSink.
+// Reference fields (ref_qpos / ref_qvel, hs_reward_prog.h "reference motion"): when the launch's programs read
+// one (RpRef::K > 0, set by the host from their field masks) the REF instance of the kernel runs: the lane
+// computes its two rows and the weight ONCE, ahead of rp_run, and keeps them in registers (RpLanePhase); a load
+// of such a field is then the two row gathers, issued together, and the interpolation -- no second pass over the
+// program.  The rows are a few KB that every lane of the launch reads: they stay in L2.  Every other launch runs
+// the instance without REF, which compiles to the code it was before: a first version that tested K in one
+// kernel cost the stand program's launch 3.5 us of 64 (profiles/reference_motion.md).
 #include <hip/hip_runtime.h>
 
 #include "hs_reward_prog.h"
@@ -42,8 +49,29 @@ struct RpSink {
   bool live = false, zero = false, fresh = false;
 };
 
+// the lane's phase on the reference motion: the two rows, packed into one register (i | i1 << 16; both are below
+// RP_REF_MAX_ROWS = 2^12), and the second row's weight
 template <typename T>
-__device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long long e, T* v, const RpSink<T>& s) {
+struct RpLanePhase {
+  uint32_t rows = 0;
+  T w = T(0);
+};
+static_assert(RP_REF_MAX_ROWS <= 1 << 16, "RpLanePhase packs two row indices into 32 bits");
+
+template <typename T>
+__device__ __forceinline__ RpLanePhase<T> rp_lane_phase(const RpRef<T>& r, long long e) {
+  RpLanePhase<T> ph;
+  const int32_t ep = r.episode[e];
+  const int j0 = rp_ref_start(r.flags, r.seed, (int)e, ep, r.K);
+  int i = 0, i1 = 0;
+  ph.w = (T)rp_ref_phase(r.K, r.flags, j0, (double)r.time[e], r.key_dt, &i, &i1);
+  ph.rows = (uint32_t)i | ((uint32_t)i1 << 16);
+  return ph;
+}
+
+template <typename T, bool REF>
+__device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long long e, T* v, const RpSink<T>& s,
+                                    const RpLanePhase<T>& ph) {
   T res = T(0);
   for (int i = 0; i < c.n_instr; i++) {
     const int32_t* in = c.code + 5 * (size_t)i;
@@ -69,8 +97,17 @@ __device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long lo
     } else if (op == RP_PARAM) {
       r = (T)c.params[x];
     } else if (op == RP_LOAD) {
-      const T* f = a.field[x];
-      r = f ? f[e * a.ld[x] + y] : T(0);
+      if (!REF || x < RP_NFIELDS) {
+        const T* f = a.field[x];
+        r = f ? f[e * a.ld[x] + y] : T(0);
+      } else {   // a reference field (x is wave-uniform): the two rows' values, then a + w (b - a)
+        const bool pos = x == RP_F_REF_QPOS;
+        const T* f = pos ? a.ref.q : a.ref.v;
+        const size_t ld = (size_t)(pos ? a.ref.nq : a.ref.nv);
+        const T lo = f[(size_t)(ph.rows & 0xFFFFu) * ld + (size_t)y];
+        const T hi = f[(size_t)(ph.rows >> 16) * ld + (size_t)y];
+        r = rp_ref_value<T>(lo, hi, ph.w);
+      }
     } else if (op == RP_RESULT) {
       res = v[x * RP_BLOCK];
       break;
@@ -86,7 +123,7 @@ __device__ __forceinline__ T rp_run(const RpCode& c, const RpArgs<T>& a, long lo
   return res;
 }
 
-template <typename T>
+template <typename T, bool REF>
 __global__ __launch_bounds__(RP_BLOCK) void reward_program_kernel(RpArgs<T> a) {
   extern __shared__ double rp_lds[];
   T* v = reinterpret_cast<T*>(rp_lds) + threadIdx.x;
@@ -109,14 +146,16 @@ __global__ __launch_bounds__(RP_BLOCK) void reward_program_kernel(RpArgs<T> a) {
       sink.fresh = a.comp_episode[e] != ep;
     }
   }
+  RpLanePhase<T> ph;
+  if constexpr (REF) ph = rp_lane_phase<T>(a.ref, e);
   T res = T(0);
-  if (has_prog) res = rp_run<T>(a.prog, a, e, v, sink);
+  if (has_prog) res = rp_run<T, REF>(a.prog, a, e, v, sink, ph);
   if (!a.outcome) {
     if (ok) a.out[env] = res;
     return;
   }
   T held = T(0);
-  if (has_pred) held = rp_run<T>(a.pred, a, e, v, none);
+  if (has_pred) held = rp_run<T, REF>(a.pred, a, e, v, none, ph);
   // The env step's outcome on the post-step, pre-reset state (custom_env.py:201-224), as the step kernel's
   // env_outcome writes it for a built-in reward: a truncated env is rewarded 0, the reward joins the
   // episode's total, a finished env leaves its final info and obs in the terminal rows, and its done byte
@@ -185,9 +224,16 @@ hipError_t launch_reward_program(const RpArgs<T>& a, hipStream_t stream) {
   if (a.comp && (ni == 0 || a.n_outputs < 1 || a.n_outputs > RP_MAX_OUTPUTS ||
                  (a.outcome && (!a.comp_total || !a.comp_episode || !a.term_comp_total || !a.episode))))
     return hipErrorInvalidValue;
+  if (a.ref.K < 0 || a.ref.K > RP_REF_MAX_ROWS ||
+      (a.ref.K > 0 && (!a.ref.q || !a.ref.v || !a.ref.time || !a.ref.episode || a.ref.nq < 1 || a.ref.nv < 1 ||
+                       (a.ref.K > 1 && !(a.ref.key_dt > 0)))))
+    return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)(((long long)a.n + RP_BLOCK - 1) / RP_BLOCK);
   const size_t lds = (size_t)a.n_slots * RP_BLOCK * sizeof(T);   // <= 64 * 64 * 8 = 32 KB
-  hipLaunchKernelGGL((reward_program_kernel<T>), dim3(blocks), dim3(RP_BLOCK), lds, stream, a);
+  if (a.ref.K > 0)
+    hipLaunchKernelGGL((reward_program_kernel<T, true>), dim3(blocks), dim3(RP_BLOCK), lds, stream, a);
+  else
+    hipLaunchKernelGGL((reward_program_kernel<T, false>), dim3(blocks), dim3(RP_BLOCK), lds, stream, a);
   return hipGetLastError();
 }
 

@@ -12,7 +12,10 @@ for this single-env surface, 'fp32'), ``max_newton``, ``termination`` (``{"type"
 "grace_steps": 1}``: the fall conditions custom_env.py:167-200 holds commented out; ``terminated`` is then true
 on an early end and ``info["early_termination"]`` says which kind it was), ``initial_state`` (``{"keyframe":
 "squat"}``, ``{"trajectory": path}``, ...: every reset starts from a row of that bank of states instead of the
-standing pose, ``initial_state.build_bank``; its ``"noise_scale"`` scales the reset noise).
+standing pose, ``initial_state.build_bank``; its ``"noise_scale"`` scales the reset noise), ``reference_motion``
+(``{"trajectory": path, "key_dt": 0.05}``, ``{"from_initial_state": True, "key_dt": ...}``, ...: the recording
+that the reward ``"track"``, the termination ``"off_track"`` and user programs read as ``data.ref_qpos`` /
+``data.ref_qvel``, ``reference_motion.build_reference``).
 ``reward_config["components"] = True``
 (built-in types) or a registered program reward whose function returns a dict fills ``self.reward_components`` --
 and through custom_env.py:217's own ``getattr``, ``info["reward_components"]`` -- with the reward's named terms
@@ -85,6 +88,17 @@ class HsData:
     @property
     def time(self):
         return float(self._b().time[self._env._idx].item())
+
+    @property
+    def ref_qpos(self):
+        """The bound reference motion's qpos at this env's episode and time (``reference_motion.sample``: what a
+        program on the device reads as ``d.ref_qpos``); needs ``env_config["reference_motion"]``."""
+        return self._b().reference_sample()[0][self._env._idx].astype(np.float64)
+
+    @property
+    def ref_qvel(self):
+        """The bound reference motion's qvel at this env's episode and time."""
+        return self._b().reference_sample()[1][self._env._idx].astype(np.float64)
 
     @property
     def qacc_warmstart(self):
@@ -170,6 +184,9 @@ class HumanoidEnv(Env):
             termination = env_config.get('termination')
             # additive: where episodes begin (initial_state.build_bank): {"keyframe": "squat"}, {"trajectory": path}
             initial_state = env_config.get('initial_state')
+            # additive, read below: env_config['reference_motion'] = {"trajectory": path, "key_dt": 0.05} or
+            # {"from_initial_state": True, "key_dt": ...} (reference_motion.build_reference) -- what "track" /
+            # "off_track" and user programs read as d.ref_qpos / d.ref_qvel
         else:
             termination = None
             initial_state = None
@@ -184,6 +201,9 @@ class HumanoidEnv(Env):
             self.total_reward = 0.0
             device, precision, max_newton, full_state = 0, 'fp64', 100, False
         self.model = HsModel(self.model_path)
+        # (checked before the batch exists: unknown key, missing key_dt, a reward that reads the reference without one)
+        from .reference_motion import reference_from_config
+        reference = reference_from_config(self.model, env_config if isinstance(env_config, dict) else {})
         self._body_parent = self.model.field("body_parentid").astype(int)
         self._batch = HsBatch(self.model, 1, device=device, precision=precision, full_state=full_state)
         self._idx = 0
@@ -202,6 +222,8 @@ class HumanoidEnv(Env):
             self._batch.set_initial_states(*build_bank(self.model, initial_state))
             self._noise_scale = noise_scale_of(initial_state, self._noise_scale)
             self._batch.configure(noise_scale=self._noise_scale)
+        if reference is not None:
+            self._batch.set_reference_motion(reference)
         self._termination = None
         if termination is not None:      # unknown type / parameter: ValueError here
             from .reward_program import termination_from_config
@@ -227,7 +249,7 @@ class HumanoidEnv(Env):
         if self.reward_config.get('components'):
             self._components = _rw.components_reward(rtype)
             self._reward_dev = None
-        elif rtype in _rf.REWARD_FUNCTIONS:
+        elif rtype in _rf.REWARD_FUNCTIONS or rtype in _rf.PROGRAM_REWARDS:
             self._components = _rw.device_reward_program(rtype)     # None for a built-in or a plain callable
         params = self.reward_config.get('params')
         kneel = params if (self._reward_dev == 1 and params) else None

@@ -86,10 +86,17 @@ REWARD_FUNCTIONS = {
 DEVICE_REWARD_IDS = {stand_reward: 0, robust_kneeling_reward: 1, walk_reward: 2}
 
 
+# The package's own program rewards by name (reward_program.py registers "track" here): consulted after
+# REWARD_FUNCTIONS, whose keys stay the reference's four until a user registers something.
+PROGRAM_REWARDS = {}
+
+
 def device_reward_id(name, registry=None):
-    """Kernel id for REWARD_FUNCTIONS[name], or None when it is a user callable (host path).
-    Unknown names raise ValueError exactly like custom_env.py:268-269."""
+    """Kernel id for REWARD_FUNCTIONS[name], or None when it is a user callable (host path) or one of the
+    package's program rewards (PROGRAM_REWARDS).  Unknown names raise ValueError exactly like custom_env.py:268-269."""
     reg = REWARD_FUNCTIONS if registry is None else registry
     if name not in reg:
+        if registry is None and name in PROGRAM_REWARDS:
+            return None
         raise ValueError(f"Unknown reward type: {name}")
     return DEVICE_REWARD_IDS.get(reg[name])

@@ -20,7 +20,8 @@ is the device code's reference in the tests.
 Fields: ``qpos``, ``qvel``, ``ctrl``, ``time``, ``qfrc_actuator[nv]``, ``cinert[nbody][10]``,
 ``cvel[nbody][6]``, ``subtree_com[0]`` (only the root's row: the batch keeps that one, in its aux row),
 ``cfrc_ext[nbody][6]`` and ``subtree_linvel[nbody][3]`` (zeros unless ``full_state``, as the built-in
-rewards see them).  Indexing and slicing give object arrays of scalars, so a vector expression unrolls
+rewards see them); and ``ref_qpos[nq]`` / ``ref_qvel[nv]``, the batch's reference motion sampled at the env's own
+episode and time (``reference_motion.py``; the batch must have one bound).  Indexing and slicing give object arrays of scalars, so a vector expression unrolls
 into scalar instructions; negative and slice indices are resolved against the model at trace time.
 
 Operators: ``+ - * /``, unary minus, ``abs``, ``**`` with a constant exponent 2, 3 or 4 (repeated
@@ -77,12 +78,20 @@ _ARITY = {**{n: 2 for n in _OPS[3:16]}, **{n: 1 for n in _OPS[16:27]}, "where": 
 # csrc/hs_reward_prog.h RpField, and each field's row shape from (nq, nv, nu, nbody)
 FIELDS = ("qpos", "qvel", "ctrl", "time", "qfrc_actuator", "cinert", "cvel", "subtree_com", "cfrc_ext",
           "subtree_linvel")
-FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
+# ``FIELDS`` are the state fields, which a caller supplies as arrays (the members of hs_reward_fields, one each).
+# The two REFERENCE_FIELDS come after them in the id space, in a block of their own (RP_F_REF_QPOS = 16,
+# RP_F_REF_QVEL = 17; the ids 10 .. 15 stay unknown): the sample of the batch's reference motion at the env's own
+# phase (reference_motion.py), which no caller supplies as an array.
+REFERENCE_FIELDS = ("ref_qpos", "ref_qvel")
+ALL_FIELDS = FIELDS + REFERENCE_FIELDS
+FIELD_ID = {**{n: i for i, n in enumerate(FIELDS)}, "ref_qpos": 16, "ref_qvel": 17}
+_FIELD_NAME = {i: n for n, i in FIELD_ID.items()}
 
 
 def _field_shape(name, nq, nv, nu, nbody):
     return {"qpos": (nq,), "qvel": (nv,), "ctrl": (nu,), "time": (), "qfrc_actuator": (nv,), "cinert": (nbody, 10),
-            "cvel": (nbody, 6), "subtree_com": (3,), "cfrc_ext": (nbody, 6), "subtree_linvel": (nbody, 3)}[name]
+            "cvel": (nbody, 6), "subtree_com": (3,), "cfrc_ext": (nbody, 6), "subtree_linvel": (nbody, 3),
+            "ref_qpos": (nq,), "ref_qvel": (nv,)}[name]
 
 
 # ------------------------------------------------------------------ scalars
@@ -251,7 +260,7 @@ class _View:
     def __getattr__(self, name):
         if name not in FIELD_ID:
             raise AttributeError(f"env_data.{name} is not a field a reward program can read (available: "
-                                 + ", ".join(FIELDS) + ")")
+                                 + ", ".join(ALL_FIELDS) + ")")
         v = self._make(name)
         self.__dict__[name] = v
         return v
@@ -277,6 +286,10 @@ def _trace_view(tr, dims):
 
 def _numeric_view(env_data):
     def make(name):
+        if name in REFERENCE_FIELDS and not hasattr(env_data, name):
+            raise AttributeError(f"env_data.{name}: this env_data carries no reference sample (HumanoidEnv's data view "
+                                 "does with env_config['reference_motion']; elsewhere set ref_qpos / ref_qvel from "
+                                 "reference_motion.sample)")
         x = getattr(env_data, name)
         if name == "time":
             return Scalar(_NUMERIC, _F(x))
@@ -511,7 +524,7 @@ def trace(fn, dims, param_keys=()):
     if len(consts) > MAX_CONSTS:
         raise ValueError(f"reward program: {len(consts)} constants, the limit is {MAX_CONSTS}")
     code[len(order)] = [OP["result"], 0, slot[res.v], 0, 0]
-    fields = sorted({FIELDS[nodes[i][1]] for i in order if not isinstance(i, tuple) and nodes[i][0] == "load"})
+    fields = sorted({_FIELD_NAME[nodes[i][1]] for i in order if not isinstance(i, tuple) and nodes[i][0] == "load"})
     return TracedProgram(code, np.asarray(consts, dtype=np.float64), param_keys, max(n_slots, 1), fields,
                          [k for k, _ in comps])
 
@@ -623,13 +636,24 @@ class CompiledProgram:
             a = self._pcache[key] = (C.c_double * max(len(v), 1))(*v)
         return a
 
-    def eval_host(self, fields, params=None, components=False):
+    def eval_host(self, fields, params=None, components=False, reference=None):
         """The program interpreted on the CPU (``hs_reward_program_eval_host``): ``fields`` maps field names to
         float64 arrays [n, ...] (``subtree_com``: [n, 3] or [n, nbody, 3], row 0 is used); returns [n] float64.
-        ``components=True``: (reward [n], components [C, n]), the rows in the order of ``self.outputs``."""
+        ``components=True``: (reward [n], components [C, n]), the rows in the order of ``self.outputs``.
+        ``reference``: for a program that reads ``ref_qpos`` / ``ref_qvel``, a dict ``{"motion":
+        reference_motion.Reference, "episode": [n] (start "drawn" only), "seed": int or [n], "env": [n] or None,
+        "dtype": np.float64 | np.float32}`` -- the sample is taken at ``fields["time"]``
+        (``hs_reward_program_eval_host_reference``); without it such a program is refused."""
         from . import _lib
-        f, keep, n = self._host_fields(fields)
+        f, keep, n = self._host_fields(fields, with_time=reference is not None)
         out = np.zeros(n, dtype=np.float64)
+        if reference is not None:
+            ref, keep_ref = self._host_reference(reference, n)
+            comp = np.zeros((len(self.outputs), n), dtype=np.float64)
+            _lib.check(_lib.lib().hs_reward_program_eval_host_reference(
+                self.handle, self.params(params), n, C.byref(f), C.byref(ref), out.ctypes.data,
+                comp.ctypes.data if components and comp.size else None))
+            return (out, comp) if components else out
         if not components:
             _lib.check(_lib.lib().hs_reward_program_eval_host(self.handle, self.params(params), n, C.byref(f),
                                                              out.ctypes.data))
@@ -639,10 +663,48 @@ class CompiledProgram:
             self.handle, self.params(params), n, C.byref(f), out.ctypes.data, comp.ctypes.data if comp.size else None))
         return out, comp
 
-    def _host_fields(self, fields):
+    @staticmethod
+    def _host_reference(reference, n):
+        """The ``hs_reference_host`` of ``eval_host``'s ``reference`` dict, and the arrays it points into."""
+        from . import _lib
+        unknown = sorted(set(reference) - {"motion", "episode", "seed", "env", "dtype"})
+        if unknown or "motion" not in reference:
+            raise ValueError(f"reference: a dict with 'motion' and optionally 'episode', 'seed', 'env', 'dtype'; "
+                             f"got {sorted(reference)}")
+        m = reference["motion"]
+        dt = np.dtype(reference.get("dtype", np.float64))
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError(f"reference: dtype must be float64 or float32, got {dt}")
+        # the rows as a batch of that dtype holds them
+        keep = [np.ascontiguousarray(m.qpos.astype(dt).astype(np.float64)),
+                np.ascontiguousarray(m.qvel.astype(dt).astype(np.float64))]
+        ep = seed = env = None
+        if reference.get("episode") is not None:
+            ep = np.ascontiguousarray(np.broadcast_to(np.asarray(reference["episode"], dtype=np.int64), (n,)),
+                                      dtype=np.int32)
+        if m.start == "drawn":
+            if ep is None:
+                raise ValueError("reference: start='drawn' needs 'episode'")
+            s = np.broadcast_to(np.asarray(reference.get("seed", 0), dtype=object), (n,))
+            seed = np.array([int(x) & (2 ** 64 - 1) for x in s], dtype=np.uint64)
+        if reference.get("env") is not None:
+            env = np.ascontiguousarray(np.broadcast_to(np.asarray(reference["env"], dtype=np.int64), (n,)),
+                                       dtype=np.int32)
+        keep += [ep, seed, env]
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ref = _lib.hs_reference_host(n_rows=m.K, qpos=ptr(keep[0]), qvel=ptr(keep[1]),
+                                     key_dt=1.0 if m.key_dt is None else m.key_dt, flags=m.flags,
+                                     precision=_lib.HS_FP32 if dt == np.dtype(np.float32) else _lib.HS_FP64,
+                                     episode=ptr(ep), seed=ptr(seed), env=ptr(env))
+        return ref, keep
+
+    def _host_fields(self, fields, with_time=False):
         from . import _lib
         keep, n = {}, None
-        for name in self.fields:
+        names = [k for k in self.fields if k not in REFERENCE_FIELDS]
+        if with_time and "time" not in names:     # a reference is sampled at the state's time
+            names.append("time")
+        for name in names:
             a = np.asarray(fields[name], dtype=np.float64)
             if name == "subtree_com" and a.ndim == 3:
                 a = a[:, 0]
@@ -653,13 +715,14 @@ class CompiledProgram:
         f = _lib.hs_reward_fields(**{_lib.REWARD_FIELD_MEMBER[k]: v.ctypes.data for k, v in keep.items()})
         return f, keep, n
 
-    def termination_eval_host(self, fields, episode, count, episode_tag, params=None, grace_steps=1):
+    def termination_eval_host(self, fields, episode, count, episode_tag, params=None, grace_steps=1, reference=None):
         """The program as a termination predicate on the CPU (``hs_termination_eval_host``): the predicate on n
         states (``fields`` as for ``eval_host``) and one grace-counter update per state.  ``episode`` [n] int32 are
         the envs' current episode numbers; ``count`` and ``episode_tag`` [n] int32 (contiguous) are read and
-        UPDATED IN PLACE.  Returns the [n] bool array of the envs whose episode ends."""
+        UPDATED IN PLACE.  Returns the [n] bool array of the envs whose episode ends.  ``reference``: as for
+        ``eval_host`` (``hs_termination_eval_host_reference``)."""
         from . import _lib
-        f, keep, n = self._host_fields(fields)
+        f, keep, n = self._host_fields(fields, with_time=reference is not None)
         episode = np.ascontiguousarray(episode, dtype=np.int32)
         for a in (count, episode_tag):
             if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous and a.shape == (n,)):
@@ -667,6 +730,12 @@ class CompiledProgram:
         if episode.shape != (n,):
             raise ValueError(f"episode: shape ({n},)")
         early = np.zeros(n, dtype=np.uint8)
+        if reference is not None:
+            ref, keep_ref = self._host_reference(reference, n)
+            _lib.check(_lib.lib().hs_termination_eval_host_reference(
+                self.handle, self.params(params), int(grace_steps), n, C.byref(f), C.byref(ref), episode.ctypes.data,
+                count.ctypes.data, episode_tag.ctypes.data, early.ctypes.data))
+            return early != 0
         _lib.check(_lib.lib().hs_termination_eval_host(self.handle, self.params(params), int(grace_steps), n,
                                                       C.byref(f), episode.ctypes.data, count.ctypes.data,
                                                       episode_tag.ctypes.data, early.ctypes.data))
@@ -706,6 +775,8 @@ def device_reward_program(name, registry=None):
     host callable.  Unknown names raise ValueError like custom_env.py:268-269."""
     reg = _rf.REWARD_FUNCTIONS if registry is None else registry
     if name not in reg:
+        if registry is None and name in _rf.PROGRAM_REWARDS:      # the package's own program rewards ("track")
+            return _BY_TWIN.get(_rf.PROGRAM_REWARDS[name])
         raise ValueError(f"Unknown reward type: {name}")
     return _BY_TWIN.get(reg[name])
 
@@ -827,6 +898,43 @@ def lost_balance(d, p):
     the unclamped ``arcsin`` of ``quaternion_to_euler``: a NaN pitch compares false and does not terminate."""
     roll, pitch, _ = quaternion_to_euler(d.qpos[3:7])
     return (d.qpos[2] < p["min_height"]) | (abs(roll) > p["max_roll_pitch"]) | (abs(pitch) > p["max_roll_pitch"])
+
+
+# ------------------------------------------------------------------ reference-motion targets
+# Written over d.ref_qpos / d.ref_qvel (reference_motion.py): they need a reference motion bound to the batch
+# (env_config["reference_motion"], HsBatch.set_reference_motion) and run on the program path -- three launches per
+# step, rollout_handle() None -- like any user program.  "track" is registered in reward_functions.PROGRAM_REWARDS,
+# which every lookup by name consults after REWARD_FUNCTIONS (that one keeps the reference's four keys).
+TRACK_DEFAULTS = {"k_pose": 2.0, "k_vel": 0.1, "k_root": 5.0, "w_pose": 0.5, "w_vel": 0.1, "w_root": 0.4}
+
+
+@register_device_reward("track", defaults=TRACK_DEFAULTS, registry=_rf.PROGRAM_REWARDS)
+def track(d, p):
+    """Follow the reference motion (DeepMimic-style exponentials of squared errors), components ``pose``,
+    ``velocity``, ``root``, ``total``:
+
+        pose     = exp(-k_pose sum((qpos[7:] - ref_qpos[7:])^2))          the joint angles
+        velocity = exp(-k_vel  sum((qvel[6:] - ref_qvel[6:])^2))          the joint velocities
+        root     = exp(-k_root (sum((qpos[:3] - ref_qpos[:3])^2) + 1 - (q . q_ref)^2 / sum(q_ref^2)))
+        total    = w_pose pose + w_vel velocity + w_root root
+
+    ``q`` is the root quaternion (unit: the step normalises it); the interpolated ``q_ref`` is not renormalised, so
+    its squared norm divides.  Every constant is a parameter.  The defaults are a starting point, not a tuned
+    claim: nothing has been trained with them."""
+    pose = exp(-p["k_pose"] * sum(square(d.qpos[7:] - d.ref_qpos[7:])))
+    velocity = exp(-p["k_vel"] * sum(square(d.qvel[6:] - d.ref_qvel[6:])))
+    q, qr = d.qpos[3:7], d.ref_qpos[3:7]
+    dot = sum(q * qr)
+    root = exp(-p["k_root"] * (sum(square(d.qpos[:3] - d.ref_qpos[:3])) + 1.0 - dot * dot / sum(square(qr))))
+    return {"pose": pose, "velocity": velocity, "root": root,
+            "total": p["w_pose"] * pose + p["w_vel"] * velocity + p["w_root"] * root}
+
+
+@register_device_termination("off_track", defaults={"max_root_dist": 0.5})
+def off_track(d, p):
+    """The root has drifted more than ``max_root_dist`` from the reference's: sum((qpos[:3] - ref_qpos[:3])^2) >
+    max_root_dist^2.  With ``grace_steps`` the drift must last that many env steps."""
+    return sum(square(d.qpos[:3] - d.ref_qpos[:3])) > p["max_root_dist"] ** 2
 
 
 # ------------------------------------------------------------------ the built-in rewards, restated

@@ -75,6 +75,13 @@ class HumanoidVecEnv(_Base):
         cfg = env_config if isinstance(env_config, dict) else {"model_path": env_config}
         self.env_config = dict(cfg)
         self.model = model if model is not None else HsModel(cfg["model_path"])
+        # env_config["reference_motion"] = {"trajectory": path, "key_dt": 0.05, "end": "hold", "start": "zero"} or
+        # {"from_initial_state": True, "key_dt": ...} (reference_motion.build_reference): what reward and termination
+        # programs read as d.ref_qpos / d.ref_qvel -- the reward "track", the condition "off_track".  Checked here,
+        # before the batch exists: an unknown key, a missing key_dt, or a program that reads the reference with
+        # none configured raises ValueError.  Absent or None: nothing changes.
+        from .reference_motion import reference_from_config
+        self._reference = reference_from_config(self.model, cfg)
         if groups == "auto":      # one launch per step (stream groups only pay off when run free, see HsBatch)
             groups = 1
         self.batch = HsBatch(self.model, n_envs, device=device, precision=precision, seed=seed,
@@ -118,6 +125,20 @@ class HumanoidVecEnv(_Base):
                              reward_id=rid if rid is not None else -1, autoreset=1 if on_device else 0,
                              max_newton=max_newton, init_height=1.282, noise_scale=0.01,
                              kneel_params=params if rid == 1 and params else None)
+        # env_config["initial_state"] = {"keyframe": "squat"} / {"keyframes": [...]} / {"trajectory": path} /
+        # {"states": (qpos, qvel)} (initial_state.build_bank): every reset, the auto-resets inside fused launches
+        # included, starts from a row of that bank, drawn per episode on the device.  Absent or None: nothing
+        # changes.  An unknown key or keyframe name raises here.
+        self._noise_scale = 0.01
+        if cfg.get("initial_state") is not None:
+            from .initial_state import build_bank, noise_scale_of
+            self.batch.set_initial_states(*build_bank(self.model, cfg["initial_state"]))
+            self._noise_scale = noise_scale_of(cfg["initial_state"], self._noise_scale)
+            self.batch.configure(noise_scale=self._noise_scale)
+        # the reference motion (checked above), bound before the termination condition, which is checked against the
+        # batch when it is set; bound but unread, the batch runs the launches it ran before
+        if self._reference is not None:
+            self.batch.set_reference_motion(self._reference)
         # env_config["termination"] = {"type": "fallen", "params": {...}, "grace_steps": 1}: the episode also ends
         # when that predicate has held for grace_steps env steps (custom_env.py:167-200, there commented out),
         # evaluated on the device after every step.  Absent or None: nothing changes.  An unknown type or
@@ -132,16 +153,6 @@ class HumanoidVecEnv(_Base):
             if len(self.batch._groups) != 1:
                 raise NotImplementedError("a termination condition steps one stream group (groups=1)")
             self._termination = self.batch.set_termination(rec.name, tparams, grace, fused=self._termination_fused)
-        # env_config["initial_state"] = {"keyframe": "squat"} / {"keyframes": [...]} / {"trajectory": path} /
-        # {"states": (qpos, qvel)} (initial_state.build_bank): every reset, the auto-resets inside fused launches
-        # included, starts from a row of that bank, drawn per episode on the device.  Absent or None: nothing
-        # changes.  An unknown key or keyframe name raises here.
-        self._noise_scale = 0.01
-        if cfg.get("initial_state") is not None:
-            from .initial_state import build_bank, noise_scale_of
-            self.batch.set_initial_states(*build_bank(self.model, cfg["initial_state"]))
-            self._noise_scale = noise_scale_of(cfg["initial_state"], self._noise_scale)
-            self.batch.configure(noise_scale=self._noise_scale)
         obs_space = Box(low=-np.inf, high=np.inf, shape=(self.batch.obs_dim,), dtype=np.float64)
         act_space = Box(low=-1, high=1, shape=(self.model.nu,), dtype=np.float32)
         super().__init__(n_envs, obs_space, act_space)

@@ -9,6 +9,8 @@ warm-up, then timed steps between synchronisations), for
             out, one Python call per env, rewards copied back).  It steps 4096 Python calls per env step, so
             it is timed over --host-steps steps only and takes its preconditioned state from the program env
             (qpos, qvel, warm start, clocks, step counts) instead of running an episode itself.
+  track     (only when named in --legs) the registered "track" reward over a three-keyframe looping reference
+            motion (profiles/reference_motion.md): a program that reads ref_qpos / ref_qvel, two row gathers each.
 
 Prints one JSON line per leg.  Under `rocprofv3 --kernel-trace --stats -- python ... --legs program` the trace
 holds the program launch's and the masked reset's kernel times.
@@ -52,9 +54,9 @@ def main():
     g = torch.Generator(device=dev).manual_seed(1)
     tape = (torch.rand(1024, n, model.nu, device=dev, generator=g) * 2 - 1).contiguous()
 
-    def make(rtype):
+    def make(rtype, **extra):
         e = HumanoidVecEnv({"model_path": XML, "duration": DURATION, "frame_skip": FRAME_SKIP,
-                            "reward_config": {"type": rtype}}, n_envs=n, precision="fp64", seed=0, model=model)
+                            "reward_config": {"type": rtype}, **extra}, n_envs=n, precision="fp64", seed=0, model=model)
         aux, ctrl = e.required_outputs()
         e.batch.configure(aux=aux, ctrl=ctrl)        # what a trainer keeps (train.py)
         e.reset_tensors()
@@ -88,6 +90,17 @@ def main():
                 print(json.dumps({"leg": leg, "envs": n, "steps": args.steps, "env_steps_per_s": n * args.steps / el,
                                   "ms_per_step": 1e3 * el / args.steps,
                                   "reward_mean": float(e.batch.reward.mean())}), flush=True)
+    if "track" in legs:
+        e = make("track", reference_motion={"keyframes": ["default", "squat", "stand_on_left_leg"], "key_dt": 1.0,
+                                            "end": "loop"})
+        precondition(e)
+        el = timed(e, args.steps, args.warmup)
+        t = e._program.traced
+        loads = t.code[t.code[:, 0] == rw.OP["load"]]
+        print(json.dumps({"leg": "track", "envs": n, "steps": args.steps, "env_steps_per_s": n * args.steps / el,
+                          "ms_per_step": 1e3 * el / args.steps, "reward_mean": float(e.batch.reward.mean()),
+                          "instructions": int(t.n_instr), "state_loads": int((loads[:, 2] < 10).sum()),
+                          "reference_loads": int((loads[:, 2] >= 10).sum())}), flush=True)
     if "host" in legs:
         src = envs["program"]
         e = make("stand_callable")
