@@ -187,7 +187,7 @@ __device__ __forceinline__ void map_vx(Scratch<T, C>& s, int sl, int nb, uint32_
     T v[6] = {0, 0, 0, 0, 0, 0};
     // the chain's dofs only, ascending: the same sum as over all dofs (the skipped terms are exact
     // zeros), ~half the fp64 FMAs (fp64 0.866 -> 0.812 ms per launch)
-    for_bits<T>(ch, [&](int j) { ValsX<T, 6> r; r.x = s.vx[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
+    HS_FOR_BITS(C, G_VX, T)(ch, [&](int j) { ValsX<T, 6> r; r.x = s.vx[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
                 [&](int, const ValsX<T, 6>& r) {
 #pragma unroll
                   for (int k = 0; k < 6; k++) v[k] = fma(r.v[k], r.x, v[k]);

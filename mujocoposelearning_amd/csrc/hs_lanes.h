@@ -10,6 +10,7 @@
 
 #include "hs_kernels.h"
 #include "hs_model.h"
+#include "hs_bits.h"
 
 namespace hs {
 namespace {
@@ -32,6 +33,9 @@ struct Cap {
   // the lane table (the list lies over con_F, where their kinematics tail ends, and store_contact_near
   // reads the table), and another parameter would rename every fp32 function that carries its Cap.
   static constexpr bool NEAR = LT;
+  // the chain / subtree sums read their operands a group of bits at a time (for_bits_g below): the same
+  // instances again, and a constant of its own for the same reason
+  static constexpr bool GROUPS = LT;
   static_assert((NCON % HL == 0 || HL % NCON == 0) && NEFC % HL == 0, "capacity in whole half-waves");
 };
 // resident tier per precision (hs_model.h).  The fp64 instances keep the lane table in LDS: at one wave
@@ -135,9 +139,11 @@ __device__ __forceinline__ uint32_t hballot(bool p, bool upper) {
 }
 // f(j, ld(j)) for each set bit j of mk, ascending (the chain / subtree sums).  AHEAD: the loads of the
 // next bit's operands are issued before the current bit's arithmetic, so one LDS round trip overlaps
-// the FMAs (the same operations in the same order) -- the contact loops take it; for the chain /
+// the FMAs (the same operations in the same order) -- the contact loops take it.  For the chain /
 // subtree sums it measured slower in both engines (fp64 0.697 vs 0.691 ms, fp32 0.411 vs 0.408 ms
-// per configs[1] launch).
+// per configs[1] launch): it keeps one round trip per bit, hides it behind ~10 adds only
+// and pays 14-20 register copies per bit for that.  Those sums take for_bits_g below instead, which
+// reads a group of bits per round trip (profiles/chain_sums.md).
 template <typename T, bool AHEAD = false, typename LD, typename F>
 __device__ __forceinline__ void for_bits(uint32_t mk, LD&& ld, F&& f) {
   if constexpr (AHEAD) {
@@ -160,6 +166,29 @@ __device__ __forceinline__ void for_bits(uint32_t mk, LD&& ld, F&& f) {
     }
   }
 }
+// The chain / subtree sums' walk: G bits per round (for_bit_groups, hs_bits.h) in the instances with
+// Cap::GROUPS, the bit-by-bit walk in every other.  At one wave per SIMD nothing hides an LDS round trip,
+// and the bit-by-bit walk pays one per set bit of the wave's longest mask (15 dofs for a foot's chain,
+// 16 bodies for the root's subtree on humanoid.xml); the fp32 engine runs two waves per SIMD and has no
+// registers for a second set of operands.  Group sizes per call site: profiles/chain_sums.md.
+template <typename C, int G, typename T, typename LD, typename F>
+__device__ __forceinline__ void for_bits_g(uint32_t mk, LD&& ld, F&& f) {
+  if constexpr (C::GROUPS && G > 1) for_bit_groups<G>(mk, ld, f, [] { SCHED_FENCE(); });
+  else for_bits<T>(mk, ld, f);
+}
+// The phases spell the call HS_FOR_BITS(C, G, T)(mask, ld, f); in the fp32 pass it is the for_bits call it
+// replaces (as HS_LT below: the fp32 code object stays byte for byte what it is without the groups).
+#ifdef HS_ONLY_F32
+#define HS_FOR_BITS(C, G, T) for_bits<T>
+#else
+#define HS_FOR_BITS(C, G, T) for_bits_g<C, G, T>
+#endif
+// Bits per round.  A/B among {2, 3, 4} on the configs[1] launch (profiles/chain_sums.md): the 10-value subtree sum of
+// mass_matrix (20 VGPRs per bit in flight) takes 2; the four sums of velocity_forces were measured together, not one
+// by one, and share 3 (14 VGPRs per bit, 12 for the cfrc subtree sum); map_vx takes 3.  4 everywhere measured no
+// faster than the bit-by-bit walk.  post_constraint runs only with full_state, which that launch does not set: its 3
+// follows the other 6-value sums and was not measured on its own.
+constexpr int G_CRB = 2, G_VEL = 3, G_VX = 3, G_POST = 3;
 template <typename T, int N>
 struct Vals { T v[N]; };
 template <typename T, int N>

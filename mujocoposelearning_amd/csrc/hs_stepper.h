@@ -350,7 +350,7 @@ struct Stepper {
     if (sl > 0 && sl < nb) {
       const uint32_t dm = HS_LT(C, m).body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
       T a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for_bits<T>(dm, [&](int c) { Vals<T, 10> r; for (int k = 0; k < 10; k++) r.v[k] = s.cinert[c][k]; return r; },
+      HS_FOR_BITS(C, G_CRB, T)(dm, [&](int c) { Vals<T, 10> r; for (int k = 0; k < 10; k++) r.v[k] = s.cinert[c][k]; return r; },
                   [&](int, const Vals<T, 10>& r) { for (int k = 0; k < 10; k++) a[k] += r.v[k]; });   // the subtree's bodies, ascending
       for (int k = 0; k < 10; k++) s.u.c.crb[sl][k] = a[k];
     }
@@ -398,7 +398,7 @@ struct Stepper {
       T v[6] = {0, 0, 0, 0, 0, 0};
       if (sl > 0) {
         const uint32_t ch = HS_LT(C, m).body_chainmask[sl];
-        for_bits<T>(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
+        HS_FOR_BITS(C, G_VEL, T)(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
                     [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) v[k] = fma(r.v[k], r.x, v[k]); });   // the chain's dofs, ascending
       }
       for (int k = 0; k < 6; k++) s.cvel[sl][k] = v[k];
@@ -406,7 +406,7 @@ struct Stepper {
     if (sl < NV) {
       const uint32_t dm = HS_LT(C, m).dof_dotmask[sl];
       T v[6] = {0, 0, 0, 0, 0, 0}, cdd[6];
-      for_bits<T>(dm, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
+      HS_FOR_BITS(C, G_VEL, T)(dm, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
                   [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) v[k] = fma(r.v[k], r.x, v[k]); });   // ascending, set bits only
       cross_motion(v, cd, cdd);
       for (int k = 0; k < 6; k++) s.u.r.cdofdot[sl][k] = cdd[k];
@@ -415,7 +415,7 @@ struct Stepper {
     if (sl > 0 && sl < nb) {   // RNE: cacc, cfrc_body
       const uint32_t ch = HS_LT(C, m).body_chainmask[sl];
       T a[6] = {0, 0, 0, -m->gravity[0], -m->gravity[1], -m->gravity[2]};
-      for_bits<T>(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cdofdot[j][k]; return r; },
+      HS_FOR_BITS(C, G_VEL, T)(ch, [&](int j) { ValsX<T, 6> r; r.x = s.qvel[j]; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cdofdot[j][k]; return r; },
                   [&](int, const ValsX<T, 6>& r) { for (int k = 0; k < 6; k++) a[k] = fma(r.v[k], r.x, a[k]); });   // the chain's dofs, ascending
       T f[6], t[6], t2[6];
       mul_inert(s.cinert[sl], a, f);
@@ -427,7 +427,7 @@ struct Stepper {
     if (sl > 0 && sl < nb) {   // subtree sums of cfrc_body
       const uint32_t dm = HS_LT(C, m).body_descmask[sl] & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u);
       T a[6] = {0, 0, 0, 0, 0, 0};
-      for_bits<T>(dm, [&](int c) { Vals<T, 6> r; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cfrc[c][k]; return r; },
+      HS_FOR_BITS(C, G_VEL, T)(dm, [&](int c) { Vals<T, 6> r; for (int k = 0; k < 6; k++) r.v[k] = s.u.r.cfrc[c][k]; return r; },
                   [&](int, const Vals<T, 6>& r) { for (int k = 0; k < 6; k++) a[k] += r.v[k]; });   // the subtree's bodies, ascending
       for (int k = 0; k < 6; k++) s.u.r.csub[sl][k] = a[k];
     }
@@ -1114,11 +1114,17 @@ struct Stepper {
     if (b < nb) {
       const uint32_t dm = b == 0 ? ((1u << nb) - 2u) : HS_LT(C, m).body_descmask[b];
       T a[3] = {0, 0, 0}, ms = 0;
-      for (int c = 1; c < nb; c++)
-        if (bit(dm, c)) {
-          for (int k = 0; k < 3; k++) a[k] += s.u.n.mv[c][k];
-          ms += s.cinert[c][9];
-        }
+      if constexpr (C::GROUPS) {   // the same two sums over the subtree's bodies, ascending, a group per round trip
+        for_bits_g<C, G_POST, T>(dm & ~1u & ((nb < 32 ? (1u << nb) : 0u) - 1u),
+                   [&](int c) { Vals<T, 4> r; for (int k = 0; k < 3; k++) r.v[k] = s.u.n.mv[c][k]; r.v[3] = s.cinert[c][9]; return r; },
+                   [&](int, const Vals<T, 4>& r) { for (int k = 0; k < 3; k++) a[k] += r.v[k]; ms += r.v[3]; });
+      } else {
+        for (int c = 1; c < nb; c++)
+          if (bit(dm, c)) {
+            for (int k = 0; k < 3; k++) a[k] += s.u.n.mv[c][k];
+            ms += s.cinert[c][9];
+          }
+      }
       const T inv = T(1) / (ms > T(1e-15) ? ms : T(1e-15));
       for (int k = 0; k < 3; k++) s.u.n.linv[b][k] = a[k] * inv;
     }
