@@ -214,6 +214,10 @@ hs_batch* hs_batch_create(const hs_model* m, int n_envs, int device, uint64_t se
                           const hs_buffers* external);
 void hs_batch_destroy(hs_batch* b);
 int hs_batch_get_info(const hs_batch* b, hs_batch_info* out);
+/* The schedule the batch, as configured, runs an env step of `nsub` substeps on (n_steps = 1), or a tape launch
+ * of n_steps > 1 such steps: *queue = 1 for the chunk queue, *single = 1 when a wave steps one env, not a pair
+ * (with the queue: its unit).  The launches follow the same plan.  -1 when the batch cannot run that tape launch. */
+int hs_batch_schedule(const hs_batch* b, int nsub, int n_steps, int* queue, int* single);
 int hs_get_buffers(const hs_batch* b, hs_buffers* out);
 int hs_set_config(hs_batch* b, const hs_env_config* cfg);
 /* Base seed of the on-device reset RNG (VecEnv.seed; SB3 seeds workers with seed + rank). */

@@ -136,6 +136,7 @@ def lib():
         "hs_batch_create": (vp, [vp, i, i, u64, i, vp]),
         "hs_batch_destroy": (None, [vp]),
         "hs_batch_get_info": (i, [vp, vp]),
+        "hs_batch_schedule": (i, [vp, i, i, vp, vp]),
         "hs_get_buffers": (i, [vp, vp]),
         "hs_set_config": (i, [vp, vp]),
         "hs_get_config": (i, [vp, vp]),
@@ -242,7 +243,7 @@ def lib():
 
 EXPORTED = ("hs_model_load", "hs_model_free", "hs_model_field", "hs_model_lane_table", "hs_lane_layout",
             "hs_model_lane_source", "hs_batch_create", "hs_batch_destroy",
-            "hs_batch_get_info", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_evaluate", "hs_set_autoreset_noise",
+            "hs_batch_get_info", "hs_batch_schedule", "hs_get_buffers", "hs_set_config", "hs_set_seed", "hs_get_config", "hs_reset", "hs_step", "hs_step_tape", "hs_tape_aborts", "hs_last_tape_ms", "hs_stream_orders", "hs_rollout", "hs_rollout_act", "hs_rollout_max_steps", "hs_evaluate", "hs_set_autoreset_noise",
             "hs_physics_step", "hs_state_io", "hs_kinematics", "hs_set_debug", "hs_debug_lose_handoff", "hs_debug_queue_order", "hs_debug_queue_counters", "hs_get_debug", "hs_synchronize", "hs_batch_counters", "hs_gae",
             "hs_reward_eval", "hs_reward", "hs_pack_outputs",
             "hs_ppo_act", "hs_ppo_post", "hs_gauss_logp", "hs_gauss_logp_grad",

@@ -203,21 +203,21 @@ class HsBatch:
     def queued(self, nsub=None):
         """True when an env step of this batch runs on the chunk-queue schedule (HS_SCHED_AUTO, more
         env pairs than resident waves, >= 2 substeps; include/hsim.h)."""
-        nsub = self.cfg.frame_skip if nsub is None else nsub
-        n = max(hi - lo for _, lo, hi in self._groups)
-        return (self.cfg.schedule in (_lib.HS_SCHED_AUTO, _lib.HS_SCHED_FIXED_ORDER) and nsub >= 2
-                and 0 < self.resident_waves < (n + 1) // 2)
+        return self.schedule(nsub)[0]
 
     def schedule_name(self, nsub=None):
-        """The schedule an env step of this batch runs on (the largest group's; hs_kernels.hip
-        launch_step): "queue" (chunk queue), "single" (one wave per env) or "paired"."""
-        if self.queued(nsub):
-            return "queue"
-        n = max(hi - lo for _, lo, hi in self._groups)
-        s = self.cfg.schedule
-        if s == _lib.HS_SCHED_SINGLE or (s == _lib.HS_SCHED_AUTO and 0 < self.resident_waves and n <= self.resident_waves):
-            return "single"
-        return "paired"
+        """The schedule an env step of this batch runs on (the largest group's; hs_batch_schedule):
+        "queue" (chunk queue), "single" (one wave per env) or "paired"."""
+        queue, single = self.schedule(nsub)
+        return "queue" if queue else "single" if single else "paired"
+
+    def schedule(self, nsub=None, n_steps=1):
+        """(queued, single) of the largest group's launch of n_steps env steps (hs_batch_schedule)."""
+        h = max(self._groups, key=lambda g: g[2] - g[1])[0]
+        queue, single = C.c_int(0), C.c_int(0)
+        check(lib().hs_batch_schedule(h, int(self.cfg.frame_skip if nsub is None else nsub), int(n_steps),
+                                      C.byref(queue), C.byref(single)))
+        return bool(queue.value), bool(single.value)
 
     # -- tensors (device views, valid until the next call) ---------------------------------
     def __getattr__(self, name):

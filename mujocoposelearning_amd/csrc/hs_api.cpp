@@ -135,6 +135,13 @@ int resident_waves_of(const hs_batch* b) {
   return by_precision(b->precision, [&](auto zero) { return hs::resident_waves<decltype(zero)>(pgs); });
 }
 
+// the schedule plan (hs_schedule.h) of an env step of `nsub` substeps, or of a tape launch of n_steps > 1 of them,
+// as launch_step will make it for the batch as configured
+hs::SchedulePlan plan_of(const hs_batch* b, int nsub, int n_steps) {
+  return hs::schedule_plan(b->cfg.schedule, hs::MODE_ENV_STEP, nsub, n_steps, false, b->n, resident_waves_of(b),
+                           b->mid && b->qsync, b->lose_env1);
+}
+
 template <typename T>
 int state_io(hs_batch* b, int dir, double* qpos, double* qvel, double* warm, double* time, double* ctrl) {
   const auto& m = b->model->host;
@@ -279,34 +286,25 @@ int launch(hs_batch* b, int mode, const float* act, const uint8_t* mask, const v
   if (!b) return fail("null batch");
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)stream)) return -1;
-  auto p = params_of(b, mode, nsub);
-  p.nsteps = x.nsteps;
-  int nv = b->model->host.nv;
   // a tape launch of a batch with a fused-capable termination condition: the TERM instances (the entry points
   // have refused every other tape launch of a batch with a condition)
-  TermArgs tm{};
-  const bool term = mode == MODE_ENV_STEP && b->term_prog && b->term_kind != 0 && (x.nsteps > 1 || x.ro);
-  if (term) {
-    if (b->precision != HS_FP64) return fail("a fused launch with a termination condition runs on the fp64 Newton engine");
-    tm.kind = b->term_kind;
-    tm.grace_steps = b->grace_steps;
-    tm.min_height = b->term_min_height;
-    tm.max_roll_pitch = b->term_max_roll_pitch;
-    tm.grace_count = b->grace_count;
-    tm.grace_episode = b->grace_episode;
-    tm.early = b->early;
-    tm.mid_count = b->mid_count;
-  }
-  // (the rollout, evaluation, norm and termination arguments are null on the fp32 engine: their entry points ask
+  const bool term = mode == MODE_ENV_STEP && b->term_prog && b->term_kind != 0 && (x.nsteps > 1 || x.fused.ro.obs);
+  if (term && b->precision != HS_FP64)
+    return fail("a fused launch with a termination condition runs on the fp64 Newton engine");
+  // (the rollout, evaluation, norm and termination parts are absent on the fp32 engine: their entry points ask
   // for fp64)
   const hipError_t e = by_precision(b->precision, [&](auto zero) {
     using T = decltype(zero);
-    const hs_tape_out* t = x.tape;
-    TapeOut<T> to{t ? (T*)t->obs : nullptr, t ? (T*)t->reward : nullptr, t ? t->terminated : nullptr,
-                  t ? t->truncated : nullptr};
-    const InitArgs<T> in{(const T*)b->init_q, (const T*)b->init_v, b->init_n};   // (hs_set_initial_states)
-    return launch_step<T>((const DevModel<T>*)b->dmodel, nv, env_buffers<T>(b), act, mask, (const T*)nq, (const T*)nvz,
-                          p, b->n, (hipStream_t)stream, &to, x.ro, x.ev, x.nm, term ? &tm : nullptr, &in);
+    StepLaunch<T> s{(const DevModel<T>*)b->dmodel, b->model->host.nv, env_buffers<T>(b), act, mask, (const T*)nq,
+                    (const T*)nvz, params_of(b, mode, nsub), b->n};
+    s.p.nsteps = x.nsteps;
+    if (const hs_tape_out* t = x.tape) s.tape = {(T*)t->obs, (T*)t->reward, t->terminated, t->truncated};
+    s.fused = x.fused;
+    if (term)
+      s.tm = {b->term_kind, b->grace_steps, b->term_min_height, b->term_max_roll_pitch, b->grace_count,
+              b->grace_episode, b->early, b->mid_count};
+    s.in = {(const T*)b->init_q, (const T*)b->init_v, b->init_n};   // (hs_set_initial_states)
+    return launch_step<T>(s, (hipStream_t)stream);
   });
   if (e == hipErrorInvalidValue) return fail("no kernel instance for this model's nv (compiled: nv = 27)");
   return hip_rc(e, "step kernel launch");
@@ -491,6 +489,16 @@ int hs_batch_get_info(const hs_batch* b, hs_batch_info* out) {
   return 0;
 }
 
+int hs_batch_schedule(const hs_batch* b, int nsub, int n_steps, int* queue, int* single) {
+  if (!b || !queue || !single) return fail("null argument");
+  DeviceGuard g(b->device);
+  const hs::SchedulePlan plan = plan_of(b, nsub, n_steps);
+  if (!plan.valid) return fail("hs_batch_schedule: the batch cannot run a tape launch of n_steps steps");
+  *queue = plan.queue;
+  *single = plan.single;
+  return 0;
+}
+
 int hs_get_buffers(const hs_batch* b, hs_buffers* out) {
   if (!b || !out) return fail("null argument");
   *out = b->buf;
@@ -549,9 +557,10 @@ int hs_debug_queue_order(hs_batch* b, int* out, int n) {
   if (!b->qsync || b->cfg.schedule != HS_SCHED_AUTO) return 0;
   DeviceGuard g(b->device);
   if (!hip_ok(hipDeviceSynchronize(), "sync")) return -1;
-  // the queue's unit, as launch_step picks it (a small batch only ever queues tape launches, by env)
-  const int resident = resident_waves_of(b);
-  const int nunits = b->n <= resident ? b->n : (b->n + 1) / 2;
+  // the queue's unit: a tape launch's (a small batch only ever queues tape launches, by env)
+  const hs::SchedulePlan plan = plan_of(b, b->cfg.frame_skip, 2);
+  if (!plan.valid) return 0;
+  const int nunits = plan.units;
   std::vector<int> q(hs::qsync_words(b->n));
   if (!hip_ok(hipMemcpy(q.data(), b->qsync, q.size() * sizeof(int), hipMemcpyDeviceToHost), "qsync")) return -1;
   const int par = q[hs::QS_EPOCH] & 1;   // the parity the next launch reads

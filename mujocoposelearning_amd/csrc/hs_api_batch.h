@@ -127,14 +127,12 @@ inline size_t elem_size(const hs_batch* b) { return b->precision == HS_FP64 ? 8 
 // a step with the ctrl copy on rewrites every env's data.ctrl (commit), one with it off leaves it stale
 inline void env_step_committed(hs_batch* b) { b->ctrl_stale = !(b->cfg.outputs & HS_OUT_CTRL); }
 
-// what a launch sets beyond its mode and inputs: a tape launch's step count and per-step outputs, and the
-// fused rollout's, evaluation's and obs normalisation's arguments
+// what a fused launch sets beyond its mode and inputs: the tape's step count and per-step outputs, and the
+// fused policy's parts as StepLaunch takes them (hs_kernels.h)
 struct LaunchExtra {
   int nsteps = 1;
   const hs_tape_out* tape = nullptr;
-  const RolloutArgs* ro = nullptr;
-  const EvalArgs* ev = nullptr;
-  const NormArgs* nm = nullptr;
+  FusedArgs fused{};
 };
 
 // hs_api.cpp

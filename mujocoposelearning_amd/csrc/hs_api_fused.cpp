@@ -194,20 +194,20 @@ int fused_policy_launch(hs_batch* b, const FusedCall& c, const void* bufs, const
   const std::string who_norm = c.norm ? who + "_norm" : who;
   int hidden = 0;
   if (int rc = fused_policy_check(b, c.pol, c.act, c.t_begin, c.n_steps, c.t_total, who_norm, &hidden)) return rc;
-  hs::NormArgs nm{};
+  hs::LaunchExtra x;
+  x.nsteps = c.n_steps;
   if (c.norm)
-    if (int rc = norm_args_check(b, c.on, who_norm, &nm)) return rc;
+    if (int rc = norm_args_check(b, c.on, who_norm, &x.fused.nm)) return rc;
   if (int rc = check()) return rc;
   DeviceGuard g(b->device);
   if (order_streams(b, (hipStream_t)c.stream)) return -1;
   const int resident = hs::resident_waves<double>(false);
   if (resident <= 0 || !b->mid || !b->qsync) return fail(who + ": no resident-wave count / queue buffers");
-  hs::RolloutArgs ro = policy_args(c.pol, hidden, c.act);
+  hs::RolloutArgs& ro = x.fused.ro = policy_args(c.pol, hidden, c.act);
   ro.t_begin = c.t_begin; ro.t_total = c.t_total;
   std::vector<Region> regs = state_regions(b);
   if (int rc = fill(ro, regs)) return rc;
-  hs::LaunchExtra x;
-  x.nsteps = c.n_steps; x.ro = &ro; x.ev = ev; x.nm = c.norm ? &nm : nullptr;
+  if (ev) x.fused.ev = *ev;
   int rc = guarded_tape(b, regs, (hipStream_t)c.stream, [&] {
     return hs::launch(b, hs::MODE_ENV_STEP, ro.act_clip, nullptr, nullptr, nullptr, b->cfg.frame_skip, c.stream, x);
   });

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "hs_model.h"
+#include "hs_schedule.h"
 
 namespace hs {
 
@@ -28,7 +29,7 @@ constexpr int QS_HEAD = 0, QS_EXIT = 1, QS_EPOCH = 2, QS_ABORT = 3, QS_FLAG = 4;
 // flag value of a queued hand-off: the launch tag (epoch + 1, 20 bits) and the hand-off's position
 // in the launch (the env step of a tape launch and its stage), so a consumer waits for exactly its
 // predecessor: stage 0 = first chunk of step t handed over, 1 = step t committed
-constexpr int QTAG_STEPS = 511;   // most env steps per tape launch
+// (QTAG_STEPS, hs_schedule.h: most env steps per tape launch)
 __host__ __device__ constexpr int qtag(uint32_t epoch, int t, int stage) {
   return (int)((((epoch & 0xFFFFFu) + 1u) << 10) | (uint32_t)(2 * t + stage + 1));
 }
@@ -53,7 +54,6 @@ constexpr size_t qs_ord(int npairs, int par) {
 // small-batch tape launches (launch_step)
 constexpr size_t qsync_words(int n_envs) { return qs_ord(n_envs, 2); }
 
-enum StepMode { MODE_ENV_STEP = 0, MODE_RESET = 1, MODE_PHYSICS = 2 };
 enum RewardId { REWARD_NONE = -1, REWARD_STAND = 0, REWARD_KNEELING = 1, REWARD_WALK = 2 };
 // per-env warning counters: MuJoCo's mj_checkPos / mj_checkVel / mj_checkAcc resets, contacts past the
 // wide tier, and a lost chunk-queue hand-off (a scheduling failure, not physics: the env is reset the
@@ -124,16 +124,11 @@ struct TapeOut {
   uint8_t* terminated;
   uint8_t* truncated;
 };
-// hs_env_config.schedule (SCHED_FIXED_ORDER: AUTO with the chunk queue's claims in the fixed
-// permutation instead of cost order -- A/B runs and tests)
-enum Schedule { SCHED_AUTO = 0, SCHED_DIRECT = 1, SCHED_SINGLE = 2, SCHED_FIXED_ORDER = 3 };
 // optional outputs (hs_env_config.outputs): the aux row (qacc, subtree com, ncon, nefc, solver
 // iterations -- data views and stats) and the data.ctrl copy (data views / host rewards)
 enum Outputs { OUT_AUX = 1, OUT_CTRL = 2 };
 enum Solver { SOLVER_NEWTON = 0, SOLVER_PGS = 1 };
 
-// actions: [N][nu] float32 (may be null in MODE_RESET); reset_mask: [N] (null = all);
-// noise_qpos/noise_qvel: [N][nq]/[N][nv] host-supplied reset noise (null = device RNG).
 // Fused PPO rollout (hs_rollout, fp64 engine): a tape launch whose actions come from the policy.
 // After each env step the env's wave runs the SB3 MlpPolicy's pi net (2 hidden layers of H = 64, 128
 // or 256, ReLU or Tanh) on the new obs, draws the action (the Philox stream of ppo_act_kernel) and does the
@@ -198,6 +193,13 @@ struct NormArgs {
   float clip;
 };
 
+// The fused policy's parts of a launch, as the rollout and evaluation entry points fill them (fp64 engine)
+struct FusedArgs {
+  RolloutArgs ro;   // absent: ro.obs null
+  EvalArgs ev;      // absent: ev.episode0 null
+  NormArgs nm;      // absent: nm.mean null
+};
+
 // A built-in termination condition evaluated inside a tape launch (hs_set_termination_builtin, the TERM kernel
 // instances only; hs_term_builtin.h): after every env step the predicate on the post-step qpos, the grace
 // counter, terminated |= early.  The count travels from an env's step to its next beside the hand-off row, in
@@ -224,24 +226,37 @@ struct InitArgs {
   int K;
 };
 
-// p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape` (may be null), env
-// steps of one env pair run back to back on the chunk queue with the state handed over through
-// b.mid; no wide-tier launch follows (an overflow sets qsync[QS_ABORT], the host replays the tape).
+// One step launch.  The optional parts (tape, fused.*, tm, in) are held by value; a value-initialised one is
+// absent: the member the kernels key on is null / 0 (fused.ro.obs, fused.ev.episode0, fused.nm.mean, tm.kind, in.K).
+// p.nsteps > 1: a tape launch -- actions [nsteps][N][nu], outputs per step in `tape`, env steps of one env
+// pair run back to back on the chunk queue with the state handed over through b.mid; no wide-tier launch
+// follows (an overflow sets qsync[QS_ABORT], the host replays the tape).
 template <typename T>
-hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
-                       const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
-                       const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape = nullptr,
-                       const RolloutArgs* ro = nullptr, const EvalArgs* ev = nullptr, const NormArgs* nm = nullptr,
-                       const TermArgs* tm = nullptr, const InitArgs<T>* in = nullptr);
+struct StepLaunch {
+  const DevModel<T>* model;
+  int nv;
+  EnvBuffers<T> b;
+  const float* actions;        // [N][nu] float32 (may be null in MODE_RESET)
+  const uint8_t* reset_mask;   // [N] (null = all)
+  const T *noise_qpos, *noise_qvel;   // [N][nq] / [N][nv] host-supplied reset noise (null = device RNG)
+  StepParams p;
+  int nenv;
+  TapeOut<T> tape;
+  FusedArgs fused;
+  TermArgs tm;
+  InitArgs<T> in;
+};
+template <typename T>
+hipError_t launch_step(const StepLaunch<T>& s, hipStream_t stream);
 
-// The fused rollout / evaluation instance with obs normalisation (KArgs::nm set) on the chunk queue: kargs is
-// launch_step's KArgs<double>, max_grid its grid (the launch takes no more waves than the instance holds)
-hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream);
-// The same for the five instances that evaluate a built-in termination condition (KArgs::tm set; a code
-// object of their own): the tape (neither rollout nor eval), the rollout and the evaluation, the latter two
-// with or without obs normalisation
-hipError_t launch_queue_term(const void* kargs, unsigned max_grid, bool rollout, bool eval, bool norm,
-                             hipStream_t stream);
+// A chunk-queue kernel instance: the solver and the fused features compiled into it
+enum QueueInstance : unsigned { QI_PGS = 1, QI_ROLL = 2, QI_EVAL = 4, QI_NORM = 8, QI_TERM = 16 };
+// The queue instances in code objects of their own: the two with obs normalisation (QI_NORM without QI_TERM)
+// and the five with a built-in termination condition (QI_TERM).  s: launch_step's request with the schedule
+// plan in s.p (KArgs is private to each pass over hs_kernels.hip: every object builds its own); max_grid: the
+// plan's grid; hipErrorInvalidValue: no such instance.
+hipError_t launch_queue_norm(const StepLaunch<double>& s, unsigned instance, unsigned max_grid, hipStream_t stream);
+hipError_t launch_queue_term(const StepLaunch<double>& s, unsigned instance, unsigned max_grid, hipStream_t stream);
 
 // waves of the resident step-kernel instance the current device holds at once (0 if unknown)
 template <typename T>

@@ -32,7 +32,10 @@
 //   hs_reward.h       the reward plug-ins' inputs and formulas, numpy's summation order
 //   hs_policy.h       the fused rollout's / evaluation's policy forward (pi net on a wave's two envs)
 //   hs_env_step.h     reset, obs, commit, step_pair and its phases (load, outcome, hand-off, next action)
-//   this file         the __global__ kernels, the host launchers, the explicit instantiations
+//   this file         the __global__ kernels and, at its end, the explicit instantiations
+//   hs_launch.h       the host launchers (included after the kernels): wave counts, queue-instance dispatch,
+//                     launch_step
+//   hs_schedule.h     the schedule plan launch_step follows (plain C++, no device code; through hs_kernels.h)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -392,198 +395,11 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs<T> a) {
 }
 
 }  // namespace
+}  // namespace hs
 
-template <typename T>
-hipError_t launch_pack(const PackArgs<T>& a, hipStream_t stream) {
-  const size_t total = (size_t)a.n * (a.obs_dim + a.ncols + a.nwarn);
-  if (total == 0) return hipSuccess;
-  const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 2048);
-  hipLaunchKernelGGL((pack_kernel<T>), dim3(blocks), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
+#include "hs_launch.h"
 
-template <typename T>
-hipError_t launch_reward_eval(const RewardEvalArgs<T>& a, hipStream_t stream) {
-  if (a.n <= 0) return hipSuccess;
-  if (a.nv < 6 || a.nv > HL || a.nu < 0 || a.nu > HL || a.nbody < 2 || a.nq < 7) return hipErrorInvalidValue;
-  const long long threads = (long long)a.n * HL;
-  const unsigned blocks = (unsigned)((threads + 255) / 256);
-  hipLaunchKernelGGL((reward_eval_kernel<T>), dim3(blocks), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
-
-// waves of the resident step-kernel instance the current device holds at once (occupancy x CUs),
-// cached per device (a racing first call computes the same value twice: benign)
-template <typename T>
-int resident_waves(bool pgs) {
-  constexpr int MAXDEV = 64;
-  static int cache[2][MAXDEV] = {};   // 0: not yet computed
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-  int* c = dev < MAXDEV ? &cache[pgs ? 1 : 0][dev] : nullptr;
-  if (c && *c != 0) return *c > 0 ? *c : 0;
-  int per_cu = 0, v = -1;
-  hipDeviceProp_t prop;
-  hipError_t e = hipGetDeviceProperties(&prop, dev);
-  if (e == hipSuccess)
-    e = pgs ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel<T, 27, true>, WAVE, 0)
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel<T, 27, false>, WAVE, 0);
-  if (e == hipSuccess && per_cu > 0) v = per_cu * prop.multiProcessorCount;
-  if (c) *c = v;
-  return v > 0 ? v : 0;
-}
-
-// waves of a chunk-queue instance the current device holds at once (0 if unknown), cached per
-// device.  The queue's grid must not exceed it: a wave's first item is item blockIdx.x, taken without
-// a claim (step_kernel_queue), so every wave of the grid has to be running from the start.  It is
-// below resident_waves() where the queue instance's occupancy is below the direct kernel's (the fp32
-// Newton engine: 1 wave per SIMD against 2).
-template <typename T, bool PGS, bool ROLL, bool EVAL = false, bool NORM = false, bool TERM = false>
-int queue_waves() {
-  constexpr int MAXDEV = 64;
-  static int cache[MAXDEV] = {};   // 0: not yet computed
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return 0;
-  if (cache[dev] != 0) return cache[dev] > 0 ? cache[dev] : 0;
-  int per_cu = 0, v = -1;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, step_kernel_queue<T, 27, PGS, ROLL, EVAL, NORM, TERM>, WAVE, 0) == hipSuccess &&
-      per_cu > 0)
-    v = per_cu * prop.multiProcessorCount;
-  cache[dev] = v;
-  return v > 0 ? v : 0;
-}
-
-template <typename T>
-hipError_t launch_step(const DevModel<T>* dmodel, int nv, const EnvBuffers<T>& b, const float* actions,
-                       const uint8_t* reset_mask, const T* noise_qpos, const T* noise_qvel,
-                       const StepParams& p, int nenv, hipStream_t stream, const TapeOut<T>* tape,
-                       const RolloutArgs* ro, const EvalArgs* ev, const NormArgs* nm, const TermArgs* tm,
-                       const InitArgs<T>* in) {
-  if (nenv <= 0) return hipSuccess;
-  if (nv != 27) return hipErrorInvalidValue;
-  KArgs<T> args{(MPtr<T>)dmodel, b, actions, reset_mask, noise_qpos, noise_qvel, p, nenv,
-                tape ? *tape : TapeOut<T>{nullptr, nullptr, nullptr, nullptr}, ro ? *ro : RolloutArgs{},
-                ev ? *ev : EvalArgs{}, nm ? *nm : NormArgs{}, tm ? *tm : TermArgs{},
-                in ? *in : InitArgs<T>{nullptr, nullptr, 0}};
-  if (args.in.K < 0 || (args.in.K > 0 && (!args.in.q || !args.in.v))) return hipErrorInvalidValue;
-  if (nm && (!ro || !nm->mean || !nm->inv_std || !(nm->clip > 0.f))) return hipErrorInvalidValue;
-  // fused rollouts: the fp64 Newton engine
-  if (ro && (sizeof(T) != 8 || !ro->obs || p.solver == SOLVER_PGS)) return hipErrorInvalidValue;
-  // fused evaluation: a rollout launch (the policy, ro.obs = the staging rows) with result slots
-  if (ev && (!ro || !ev->episode0 || ev->max_episodes < 1 || ev->n_trace < 0 || ev->n_trace > nenv))
-    return hipErrorInvalidValue;
-  // a built-in termination condition: tape launches of the fp64 Newton engine with auto-reset (an early end
-  // resets inside the launch)
-  if (tm && (sizeof(T) != 8 || p.solver == SOLVER_PGS || p.mode != MODE_ENV_STEP || !p.autoreset ||
-             (tm->kind != TERM_FALLEN && tm->kind != TERM_LOST_BALANCE) || tm->grace_steps < 1 || !tm->grace_count ||
-             !tm->grace_episode || !tm->early || !tm->mid_count || !(args.p.nsteps > 1 || ro)))
-    return hipErrorInvalidValue;
-  if (args.p.nsteps < 1) args.p.nsteps = 1;
-  // chunk-queue schedule when the env pairs outnumber the waves the GPU holds at once (the fp64
-  // engine: 1 wave per SIMD), for multi-substep calls (HS_SCHED_DIRECT: never)
-  const int npairs = (nenv + 1) / 2;
-  const int resident = resident_waves<T>(p.solver == SOLVER_PGS);
-  const bool may_queue = p.schedule == SCHED_AUTO || p.schedule == SCHED_FIXED_ORDER;
-  args.p.queue = (may_queue && b.mid && b.qsync && p.mode != MODE_RESET && p.nsub >= 2 && resident > 0 &&
-                  npairs > resident) ? 1 : 0;
-  // tape launch (several env steps of an action tape): always the chunk queue, with whole env steps
-  // as items, whatever the batch size -- a pair's next env step starts as soon as its own previous
-  // one is committed, so the steps of different pairs overlap instead of each step ending on its
-  // slowest pair
-  const bool tape_launch = args.p.nsteps > 1 || ro != nullptr;
-  if (tape_launch) {
-    if (p.mode != MODE_ENV_STEP || !b.mid || !b.qsync || resident <= 0 || args.p.nsteps > QTAG_STEPS)
-      return hipErrorInvalidValue;
-    args.p.queue = 1;
-  }
-  // a tape launch of a small batch (every env fits a resident wave of its own) queues single envs,
-  // not pairs: twice the waves, each env's steps back to back (configs[4]'s 1024 envs would otherwise
-  // leave half of the resident wave slots idle)
-  const bool qsingle = tape_launch && may_queue && nenv <= resident;
-  const int nunits = qsingle ? nenv : npairs;
-  args.p.qorder = p.schedule == SCHED_AUTO ? 1 : 0;
-  // fallback claim order (first queued launch, SCHED_FIXED_ORDER): a fixed multiplicative
-  // permutation of the pairs (the same for both chunk kinds, so a pair's last substep is still
-  // claimed npairs items after its first chunk).  Items whose cost is correlated with the env index
-  // -- e.g. env clocks staggered by index, bench.py's window -- are spread over the launch instead
-  // of arriving together at its end.
-  args.p.qmul = 1;
-  if (args.p.queue) {
-    auto gcd = [](uint32_t a, uint32_t b) { while (b) { uint32_t t = a % b; a = b; b = t; } return a; };
-    uint32_t q = (uint32_t)(0.6180339887 * nunits) | 1u;
-    while (gcd(q, (uint32_t)nunits) != 1u) q += 2;
-    args.p.qmul = (int)(q % (uint32_t)nunits == 0 ? 1 : q);
-  }
-  // single-env schedule: one wave per env (the upper half-wave a ghost of the lower) when every
-  // env gets a resident wave of its own -- small batches (configs[4]'s 1024 envs per GPU) would
-  // otherwise leave SIMDs idle with one wave per env pair
-  args.p.single = qsingle || (!args.p.queue && (p.schedule == SCHED_SINGLE ||
-                                                (p.schedule == 0 && resident > 0 && nenv <= resident))) ? 1 : 0;
-  // the lost-hand-off test hook names an env (+ 1); the kernel compares it with its queue unit
-  if (args.p.dbg_lose_pair1 > 0 && !qsingle) args.p.dbg_lose_pair1 = (args.p.dbg_lose_pair1 - 1) / 2 + 1;
-  const dim3 grid(args.p.queue ? (tape_launch ? std::min(resident, nunits) : resident) : (args.p.single ? nenv : npairs)),
-      block(WAVE);
-  // the wide tier's grid: enough waves for a few deferred envs at once, few enough that the
-  // common no-overflow launch (every wave reads the count and exits) costs a few microseconds
-  const dim3 wgrid(std::min((nenv + 1) / 2, 32));
-  // one solver's launches: the resident tier (chunk-queue or direct schedule), then the wide tier's
-  // re-run of the envs it deferred (a generic lambda, not a function template: the kernel instances
-  // then keep their order in the code object)
-  // (the queue's grid: no more waves than its instance holds at once, queue_waves)
-  auto queue_grid = [&](int held) { return dim3(std::min((int)grid.x, held)); };
-  auto launch_tiers = [&](auto pgs) -> hipError_t {
-    constexpr bool PGS = decltype(pgs)::value;
-    if (args.p.queue) {
-      const int held = queue_waves<T, PGS, false>();
-      if (held <= 0) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((step_kernel_queue<T, 27, PGS>), queue_grid(held), block, 0, stream, args);
-    } else {
-      hipLaunchKernelGGL((step_kernel<T, 27, PGS>), grid, block, 0, stream, args);
-    }
-    if (b.redo && !tape_launch) hipLaunchKernelGGL((step_kernel_wide<T, 27, PGS>), wgrid, block, 0, stream, args);
-    return hipSuccess;
-  };
-  hipError_t rc = hipSuccess;
-  if (tm) {
-    // the TERM instances live in an object of their own (launch_queue_term below)
-    if constexpr (sizeof(T) == 8) return launch_queue_term(&args, grid.x, ro != nullptr, ev != nullptr, nm != nullptr, stream);
-  }
-  if (p.solver == SOLVER_PGS) {
-    rc = launch_tiers(std::true_type{});
-  } else if (ro) {
-    if constexpr (sizeof(T) == 8) {
-      // the NORM instances live in an object of their own (launch_queue_norm below)
-      if (nm) return launch_queue_norm(&args, grid.x, ev != nullptr, stream);
-      const int held = ev ? queue_waves<T, false, true, true>() : queue_waves<T, false, true>();
-      if (held <= 0) return hipErrorInvalidValue;
-      if (ev)
-        hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true, true>), queue_grid(held), block, 0, stream, args);
-      else
-        hipLaunchKernelGGL((step_kernel_queue<T, 27, false, true>), queue_grid(held), block, 0, stream, args);
-    }
-  } else {
-    rc = launch_tiers(std::false_type{});
-  }
-  return rc != hipSuccess ? rc : hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_kinematics(const DevModel<T>* dmodel, int nv, const T* qpos, T* out, hipStream_t stream) {
-  if (nv != 27) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((kin_kernel<T, 27>), dim3(1), dim3(WAVE), 0, stream, (MPtr<T>)dmodel, qpos, out);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_kinematics_batch(const DevModel<T>* dmodel, int nv, int n, const T* qpos, const T* state_qpos,
-                                   const int* envs, T* out, hipStream_t stream) {
-  if (nv != 27 || n < 1 || (envs ? !state_qpos : !qpos)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((kin_batch_kernel<T, 27>), dim3((unsigned)n), dim3(WAVE), 0, stream, (MPtr<T>)dmodel, qpos,
-                     state_qpos, envs, out);
-  return hipGetLastError();
-}
+namespace hs {
 // The Makefile compiles this file once per precision (HS_ONLY_F32 / HS_ONLY_F64), so each engine
 // gets its own code-generation flags (the fp64 one without MachineLICM), and once more
 // (HS_ONLY_NORM, the fp64 flags) for the two fused instances whose policy normalises its obs
@@ -592,43 +408,19 @@ hipError_t launch_kinematics_batch(const DevModel<T>* dmodel, int nv, int n, con
 // A fourth pass (HS_ONLY_TERM, the fp64 flags) does the same for the five instances that evaluate a built-in
 // termination condition (hs_set_termination_builtin).
 #if defined(HS_ONLY_NORM)
-hipError_t launch_queue_norm(const void* kargs, unsigned max_grid, bool eval, hipStream_t stream) {
-  const KArgs<double>& args = *static_cast<const KArgs<double>*>(kargs);
-  const int held = eval ? queue_waves<double, false, true, true, true>() : queue_waves<double, false, true, false, true>();
-  if (held <= 0) return hipErrorInvalidValue;
-  const dim3 grid(std::min(max_grid, (unsigned)held)), block(WAVE);
-  if (eval)
-    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, true, true, true>), grid, block, 0, stream, args);
-  else
-    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, true, false, true>), grid, block, 0, stream, args);
-  return hipGetLastError();
+hipError_t launch_queue_norm(const StepLaunch<double>& s, unsigned instance, unsigned max_grid, hipStream_t stream) {
+  return launch_queue(QueueInstances<QI_ROLL | QI_EVAL | QI_NORM, QI_ROLL | QI_NORM>{}, kernel_args(s), instance, max_grid,
+                      stream);
 }
 #elif defined(HS_ONLY_TERM)
-hipError_t launch_queue_term(const void* kargs, unsigned max_grid, bool rollout, bool eval, bool norm,
-                             hipStream_t stream) {
-  const KArgs<double>& args = *static_cast<const KArgs<double>*>(kargs);
-  if (!rollout && (eval || norm)) return hipErrorInvalidValue;
-  // one instance: its wave count, then its launch
-  auto go = [&](auto roll, auto ev, auto nm) -> hipError_t {
-    constexpr bool R = decltype(roll)::value, E = decltype(ev)::value, N = decltype(nm)::value;
-    const int held = queue_waves<double, false, R, E, N, true>();
-    if (held <= 0) return hipErrorInvalidValue;
-    const dim3 grid(std::min(max_grid, (unsigned)held)), block(WAVE);
-    hipLaunchKernelGGL((step_kernel_queue<double, 27, false, R, E, N, true>), grid, block, 0, stream, args);
-    return hipGetLastError();
-  };
-  using Y = std::true_type;
-  using F = std::false_type;
-  if (!rollout) return go(F{}, F{}, F{});
-  if (eval) return norm ? go(Y{}, Y{}, Y{}) : go(Y{}, Y{}, F{});
-  return norm ? go(Y{}, F{}, Y{}) : go(Y{}, F{}, F{});
+hipError_t launch_queue_term(const StepLaunch<double>& s, unsigned instance, unsigned max_grid, hipStream_t stream) {
+  return launch_queue(QueueInstances<QI_TERM, QI_ROLL | QI_EVAL | QI_NORM | QI_TERM, QI_ROLL | QI_EVAL | QI_TERM,
+                                      QI_ROLL | QI_NORM | QI_TERM, QI_ROLL | QI_TERM>{},
+                      kernel_args(s), instance, max_grid, stream);
 }
 #else
 #ifndef HS_ONLY_F64
-template hipError_t launch_step<float>(const DevModel<float>*, int, const EnvBuffers<float>&, const float*,
-                                       const uint8_t*, const float*, const float*, const StepParams&, int,
-                                       hipStream_t, const TapeOut<float>*, const RolloutArgs*, const EvalArgs*,
-                                       const NormArgs*, const TermArgs*, const InitArgs<float>*);
+template hipError_t launch_step<float>(const StepLaunch<float>&, hipStream_t);
 template int resident_waves<float>(bool);
 template hipError_t launch_kinematics<float>(const DevModel<float>*, int, const float*, float*, hipStream_t);
 template hipError_t launch_kinematics_batch<float>(const DevModel<float>*, int, int, const float*, const float*,
@@ -637,10 +429,7 @@ template hipError_t launch_reward_eval<float>(const RewardEvalArgs<float>&, hipS
 template hipError_t launch_pack<float>(const PackArgs<float>&, hipStream_t);
 #endif
 #ifndef HS_ONLY_F32
-template hipError_t launch_step<double>(const DevModel<double>*, int, const EnvBuffers<double>&, const float*,
-                                        const uint8_t*, const double*, const double*, const StepParams&, int,
-                                        hipStream_t, const TapeOut<double>*, const RolloutArgs*, const EvalArgs*,
-                                        const NormArgs*, const TermArgs*, const InitArgs<double>*);
+template hipError_t launch_step<double>(const StepLaunch<double>&, hipStream_t);
 template int resident_waves<double>(bool);
 template hipError_t launch_kinematics<double>(const DevModel<double>*, int, const double*, double*, hipStream_t);
 template hipError_t launch_kinematics_batch<double>(const DevModel<double>*, int, int, const double*, const double*,
