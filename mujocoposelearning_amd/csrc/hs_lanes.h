@@ -359,7 +359,9 @@ __device__ __forceinline__ float rsqrt_t<float>(float x) { return __builtin_amdg
 // fp64: below recip()
 // 1/x: fp32 is v_rcp_f32 under -fno-hip-fp32-correctly-rounded-divide-sqrt; fp64 is v_rcp_f64 +
 // one cubic correction (e + e^2) instead of two Newton steps: 4 dependent operations instead of 5,
-// the same ~1 ulp for normal nonzero x (fp64 0.662 -> 0.656 ms per configs[1] launch)
+// the same ~1 ulp for normal nonzero x (fp64 0.662 -> 0.656 ms per configs[1] launch).
+// Domain of recip(double): normal, nonzero x whose reciprocal is normal too; 0 and denormals give NaN
+// by construction (v_rcp_f64 returns +-inf there and e = 1 - x * inf is NaN), no class check.
 __device__ __forceinline__ float recip(float x) { return 1.0f / x; }
 __device__ __forceinline__ double recip(double x) {
   double y = __builtin_amdgcn_rcp(x);

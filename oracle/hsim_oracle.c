@@ -1176,3 +1176,62 @@ void orc_step_n(const OrcModel* m, OrcData* d, const double* ctrl, int nsub) {
     orc_step(m, d);
   }
 }
+
+/* ------------------------------------------------------------------ unit harness (tests/unit_kernels.py)
+ * The narrow phase of n constructed geom pairs, for the oracle's conventions (contact count, slot order,
+ * the two-contact parallel case, the frame's tangent).  Pair i is geoms 0 and 1 of a two-geom model / data
+ * filled here: g[i] = {pos, z axis} of each geom, sz[i] = {r1, h1, r2, h2} (h = 0 for a sphere; a plane's
+ * axis is its normal), fn[i] = 0 plane-sphere, 1 plane-capsule, 2 sphere-sphere, 3 sphere-capsule,
+ * 4 capsule-capsule.  collision()'s bounding-sphere early out (margin 0), the col_* function and
+ * make_frame, all as above.  cnt[i] = contacts, out[i][k] = {pos, frame[0..5], dist} of contact k. */
+void orc_collide_pairs(int n, const int* fn, const double* g, const double* sz, int* cnt, double* out) {
+  static OrcModel m;
+  static OrcData d;
+  for (int i = 0; i < n; i++) {
+    const int f = fn[i];
+    const int t1 = f < 2 ? 0 : (f < 4 ? 2 : 3), t2 = (f == 0 || f == 2) ? 2 : 3;
+    m.geom_type[0] = t1; m.geom_type[1] = t2;
+    for (int q = 0; q < 2; q++) {
+      const double* gq = g + ((size_t)i * 2 + q) * 6;
+      memcpy(d.geom_xpos[q], gq, 3 * sizeof(double));
+      memset(d.geom_xmat[q], 0, 9 * sizeof(double));
+      d.geom_xmat[q][2] = gq[3]; d.geom_xmat[q][5] = gq[4]; d.geom_xmat[q][8] = gq[5];
+      m.geom_size[q][0] = sz[4 * (size_t)i + 2 * q];
+      m.geom_size[q][1] = sz[4 * (size_t)i + 2 * q + 1];
+      m.geom_rbound[q] = m.geom_size[q][0] + m.geom_size[q][1];
+    }
+    OrcContact tmp[4];
+    memset(tmp, 0, sizeof tmp);
+    int nc = 0, far = 0;
+    if (t1 != 0) {
+      double dif[3] = {d.geom_xpos[0][0] - d.geom_xpos[1][0], d.geom_xpos[0][1] - d.geom_xpos[1][1],
+                       d.geom_xpos[0][2] - d.geom_xpos[1][2]};
+      far = sqrt(dot3(dif, dif)) > m.geom_rbound[0] + m.geom_rbound[1];
+    }
+    if (far) nc = 0;
+    else if (f == 0) nc = col_plane_sphere(&m, &d, tmp, 0, 1, 0.0);
+    else if (f == 1) nc = col_plane_capsule(&m, &d, tmp, 0, 1, 0.0);
+    else if (f == 2) nc = col_sphere_sphere(&m, &d, tmp, 0, 1, 0.0);
+    else if (f == 3) nc = col_sphere_capsule(&m, &d, tmp, 0, 1, 0.0);
+    else if (f == 4) nc = col_capsule_capsule(&m, &d, tmp, 0, 1, 0.0);
+    cnt[i] = nc;
+    for (int k = 0; k < 2; k++) {
+      double* o = out + ((size_t)i * 2 + k) * 10;
+      memset(o, 0, 10 * sizeof(double));
+      if (k >= nc) continue;
+      make_frame(tmp[k].frame);
+      memcpy(o, tmp[k].pos, 3 * sizeof(double));
+      memcpy(o + 3, tmp[k].frame, 6 * sizeof(double));
+      o[9] = tmp[k].dist;
+    }
+  }
+}
+/* make_frame on n frames f[i] = {normal, tangent hint}, in place */
+void orc_make_frames(int n, double* f) {
+  for (int i = 0; i < n; i++) {
+    double fr[9] = {0};
+    memcpy(fr, f + 6 * (size_t)i, 6 * sizeof(double));
+    make_frame(fr);
+    memcpy(f + 6 * (size_t)i, fr, 6 * sizeof(double));
+  }
+}

@@ -99,6 +99,9 @@ extern long orc_stat_ls_evals;     /* inexact line-search cost evaluations so fa
  * the reference never requests them (zeros), so this is hsim's opt-in "full_state" mode. */
 void orc_contact_forces(const OrcModel* m, OrcData* d);
 void orc_step_n_full(const OrcModel* m, OrcData* d, const double* ctrl, int nsub, int full);
+/* unit harness (tests/unit_kernels.py): the narrow phase / make_frame on constructed inputs, hsim_oracle.c */
+void orc_collide_pairs(int n, const int* fn, const double* g, const double* sz, int* cnt, double* out);
+void orc_make_frames(int n, double* f);
 #ifdef __cplusplus
 }
 #endif

@@ -135,9 +135,32 @@ def lib():
         _LIB.orc_step_n_full.restype = None
         _LIB.orc_contact_forces.argtypes = [C.c_void_p, C.c_void_p]
         _LIB.orc_contact_forces.restype = None
+        _LIB.orc_collide_pairs.argtypes = [C.c_int] + [C.c_void_p] * 5
+        _LIB.orc_collide_pairs.restype = None
+        _LIB.orc_make_frames.argtypes = [C.c_int, C.c_void_p]
+        _LIB.orc_make_frames.restype = None
         assert _LIB.orc_sizeof_model() == C.sizeof(OrcModel), "OrcModel layout mismatch"
         assert _LIB.orc_sizeof_data() == C.sizeof(OrcData), "OrcData layout mismatch"
     return _LIB
+
+
+def collide_pairs(fn, g, sz):
+    """The oracle's narrow phase on n constructed geom pairs (orc_collide_pairs): fn [n], g [n][2][6] = (pos, z axis)
+    of each geom, sz [n][4] = (r1, h1, r2, h2) -> contact counts [n], contacts [n][2][10] = (pos, normal, t1, dist)."""
+    fn = np.ascontiguousarray(fn, dtype=np.int32)
+    g = np.ascontiguousarray(g, dtype=np.float64).reshape(len(fn), 2, 6)
+    sz = np.ascontiguousarray(sz, dtype=np.float64).reshape(len(fn), 4)
+    cnt = np.zeros(len(fn), np.int32)
+    out = np.zeros((len(fn), 2, 10))
+    lib().orc_collide_pairs(len(fn), fn.ctypes.data, g.ctypes.data, sz.ctypes.data, cnt.ctypes.data, out.ctypes.data)
+    return cnt, out
+
+
+def make_frames(f):
+    """make_frame of the oracle on n (normal, tangent hint) records [n][6] -> (normal, t1) [n][6]."""
+    f = np.array(f, dtype=np.float64).reshape(-1, 6)
+    lib().orc_make_frames(len(f), f.ctypes.data)
+    return f
 
 
 def _fill(dst, arr):
