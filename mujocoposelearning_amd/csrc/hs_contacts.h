@@ -181,6 +181,31 @@ template <typename C, typename T>
 __device__ __forceinline__ uint32_t chain_mask(MPtr<T> m, int sl, int nb) {
   return (sl > 0 && sl < nb) ? HS_LT(C, m).body_chainmask[sl] : 0u;
 }
+// contact-frame velocities con_v of this lane's contact slots from the body spatial velocities bv
+template <typename T, typename C>
+__device__ __forceinline__ void contact_vel(Scratch<T, C>& s, int sl, const T (*bv)[6]) {
+#pragma unroll
+  for (int cs = 0; cs < C::CON; cs += HL) {   // contact slots of this lane (one per lane in the resident tier)
+    const int c = cs + sl;
+    if (c < s.ncon) {
+      const uint32_t bb = s.con_bb[c];
+      const int b1 = bb & 0xff, b2 = (bb >> 8) & 0xff;
+      T r[3] = {s.con_pos[c][0] - s.com[0], s.con_pos[c][1] - s.com[1], s.con_pos[c][2] - s.com[2]};
+      T w[3], v1[3], v2[3];
+      cross3(bv[b2], r, w);
+      for (int k = 0; k < 3; k++) v2[k] = bv[b2][3 + k] + w[k];
+      cross3(bv[b1], r, w);
+      for (int k = 0; k < 3; k++) v1[k] = bv[b1][3 + k] + w[k];
+      T dv[3] = {v2[0] - v1[0], v2[1] - v1[1], v2[2] - v1[2]};
+      T t2[3];
+      cross3(s.con_n[c], s.con_t1[c], t2);
+      s.con_v[c][0] = dot3(s.con_n[c], dv);
+      s.con_v[c][1] = dot3(s.con_t1[c], dv);
+      s.con_v[c][2] = dot3(t2, dv);
+    }
+  }
+  WSYNC();
+}
 template <int NV, typename T, typename C>
 __device__ __forceinline__ void map_vx(Scratch<T, C>& s, int sl, int nb, uint32_t ch) {
   if (sl < nb) {   // body spatial velocity = sum over the body's dof chain of cdof_j x_j
@@ -195,25 +220,22 @@ __device__ __forceinline__ void map_vx(Scratch<T, C>& s, int sl, int nb, uint32_
     for (int k = 0; k < 6; k++) s.u.n.bvel[sl][k] = v[k];
   }
   WSYNC();
+  contact_vel(s, sl, s.u.n.bvel);
+}
+// map_vx's first stage for two generalized vectors in one walk of the chain (rows() of the C::WALKS instances):
+// s.qvel -> u.n.bvel and s.vx -> u.n.cfrc, each cdof row read once, each sum with map_vx's ascending FMAs.
+// u.n.cfrc has bvel's shape and is dead here: post_constraint writes it after the solve (hs_scratch.h).
+template <int NV, typename T, typename C>
+__device__ __forceinline__ void chain_vel2(Scratch<T, C>& s, int sl, int nb, uint32_t ch) {
+  struct V2 { T x, y; T v[6]; };
+  if (sl < nb) {
+    T v[6] = {0, 0, 0, 0, 0, 0}, u[6] = {0, 0, 0, 0, 0, 0};
+    for_bits_g<C, G_VX, T>(ch, [&](int j) { V2 r; r.x = s.qvel[j]; r.y = s.vx[j]; for (int k = 0; k < 6; k++) r.v[k] = s.cdof[j][k]; return r; },
+                           [&](int, const V2& r) {
 #pragma unroll
-  for (int cs = 0; cs < C::CON; cs += HL) {   // contact slots of this lane (one per lane in the resident tier)
-    const int c = cs + sl;
-    if (c < s.ncon) {
-      const uint32_t bb = s.con_bb[c];
-      const int b1 = bb & 0xff, b2 = (bb >> 8) & 0xff;
-      T r[3] = {s.con_pos[c][0] - s.com[0], s.con_pos[c][1] - s.com[1], s.con_pos[c][2] - s.com[2]};
-      T w[3], v1[3], v2[3];
-      cross3(s.u.n.bvel[b2], r, w);
-      for (int k = 0; k < 3; k++) v2[k] = s.u.n.bvel[b2][3 + k] + w[k];
-      cross3(s.u.n.bvel[b1], r, w);
-      for (int k = 0; k < 3; k++) v1[k] = s.u.n.bvel[b1][3 + k] + w[k];
-      T dv[3] = {v2[0] - v1[0], v2[1] - v1[1], v2[2] - v1[2]};
-      T t2[3];
-      cross3(s.con_n[c], s.con_t1[c], t2);
-      s.con_v[c][0] = dot3(s.con_n[c], dv);
-      s.con_v[c][1] = dot3(s.con_t1[c], dv);
-      s.con_v[c][2] = dot3(t2, dv);
-    }
+                             for (int k = 0; k < 6; k++) { v[k] = fma(r.v[k], r.x, v[k]); u[k] = fma(r.v[k], r.y, u[k]); }
+                           });
+    for (int k = 0; k < 6; k++) { s.u.n.bvel[sl][k] = v[k]; s.u.n.cfrc[sl][k] = u[k]; }
   }
   WSYNC();
 }
@@ -232,6 +254,47 @@ __device__ __forceinline__ T row_Jx(MPtr<T> m, const Scratch<T, C>& s, int desc,
   }
   int comp = kind == RK_CN ? 1 : 1 + ((kind - RK_P0) >> 1);
   return s.con_v[j][0] + coef * s.con_v[j][comp];
+}
+
+// row_Jx for all of a lane's row slots at once (the C::WALKS instances): every slot's two LDS operands are
+// read first -- xv[j] twice for a joint row, con_v[j][0] and con_v[j][comp] for a contact row -- behind one
+// scheduling fence, then each slot's value is formed from them by its kind's expression of row_Jx, so the
+// slots share one LDS round trip where the calls one after the other wait for one each.  Tendon rows keep
+// row_Jx's loop under a wave-uniform test (no lane of humanoid.xml's usual step holds one).  xv: the
+// generalized vector the body velocities behind con_v were summed from (s.vx, or s.qvel in rows()).
+template <typename T, typename C>
+__device__ __forceinline__ void rows_Jx(MPtr<T> m, const Scratch<T, C>& s, const T* xv, const bool (&vr)[C::RPL],
+                                        const int (&rd)[C::RPL], const T (&rc)[C::RPL], T (&out)[C::RPL]) {
+  T a[C::RPL], b[C::RPL];
+  bool ten = false;
+#pragma unroll
+  for (int q = 0; q < C::RPL; q++) {
+    const int kind = rk_kind(rd[q]), j = rk_id(rd[q]);
+    const bool con = kind >= RK_CN;
+    const int comp = kind == RK_CN ? 1 : 1 + ((kind - RK_P0) >> 1);
+    const T* p0 = con ? &s.con_v[j][0] : &xv[j];     // (a tendon or an empty slot reads xv[id]: in bounds, unused)
+    const T* p1 = con ? &s.con_v[j][comp] : p0;
+    a[q] = *p0;
+    b[q] = *p1;
+    ten = ten || (vr[q] && kind >= RK_TLO && kind <= RK_THI);
+  }
+  SCHED_FENCE();
+#pragma unroll
+  for (int q = 0; q < C::RPL; q++) {
+    const T cv = fma(rc[q], b[q], a[q]), jv = rc[q] * a[q];
+    out[q] = vr[q] ? (rk_kind(rd[q]) >= RK_CN ? cv : jv) : T(0);
+  }
+  if (__ballot(ten) != 0) {
+#pragma unroll
+    for (int q = 0; q < C::RPL; q++) {
+      const int kind = rk_kind(rd[q]), j = rk_id(rd[q]);
+      if (vr[q] && kind >= RK_TLO && kind <= RK_THI) {
+        T v = 0;
+        for (int w = 0; w < HS_LT(C, m).ten_nwrap[j]; w++) v += HS_LT(C, m).ten_wrapcoef[j][w] * xv[HS_LT(C, m).ten_wrapdof[j][w]];
+        out[q] = rc[q] * v;
+      }
+    }
+  }
 }
 
 // world-frame force direction u of a contact row
@@ -321,28 +384,10 @@ __device__ __forceinline__ void for_active_contacts_ld(const uint32_t* act, LD&&
         act[w], [&](int j) { return ld(w * HL + j); }, [&](int j, const auto& v) { f(w * HL + j, v); });
 }
 
-// (J' f)_i for dof sub-lane i (contacts via point Jacobians, joint limits via the dof's
-// limit-row slots, tendon limits via rows [njl, nlim))
+// the joint-limit and tendon-limit terms of (J' f)_i, added to the contacts' acc: the dof's limit-row slots
+// and rows [njl, nlim)
 template <typename T, typename C>
-__device__ __forceinline__ T jtf_lane(MPtr<T> m, const Scratch<T, C>& s, int sl, const T* cd) {
-  T acc = 0;
-  struct CV { uint32_t m1, m2; T p[3], f[3]; };
-  for_active_contacts_ld<T, C>(s.con_act, [&](int c) {
-    CV v;
-    v.m1 = s.con_m1[c]; v.m2 = s.con_m2[c];
-    for (int k = 0; k < 3; k++) { v.p[k] = s.con_pos[c][k]; v.f[k] = s.con_F[c][k]; }
-    return v;
-  }, [&](int, const CV& v) {
-    const int in2 = bit(v.m2, sl), in1 = bit(v.m1, sl);
-    if (in1 != in2) {
-      T r[3] = {v.p[0] - s.com[0], v.p[1] - s.com[1], v.p[2] - s.com[2]};
-      T w[3];
-      cross3(cd, r, w);
-      T jp[3] = {cd[3] + w[0], cd[4] + w[1], cd[5] + w[2]};
-      T x = dot3(jp, v.f);
-      acc += in2 ? x : -x;
-    }
-  });
+__device__ __forceinline__ T jtf_tail(MPtr<T> m, const Scratch<T, C>& s, int sl, T acc) {
   if (sl < MAXDOF) {
     int lr = s.lim_row[sl];
     int lo = (lr & 0xff) - 1, hi = (lr >> 8) - 1;
@@ -356,6 +401,59 @@ __device__ __forceinline__ T jtf_lane(MPtr<T> m, const Scratch<T, C>& s, int sl,
       if (HS_LT(C, m).ten_wrapdof[id][w] == sl) acc += f * HS_LT(C, m).ten_wrapcoef[id][w];
   }
   return acc;
+}
+
+// (J' f)_i for dof sub-lane i: contacts via point Jacobians, then jtf_tail.  AUG (the C::WALKS instances' Newton
+// iteration): the same walk over the active contacts also adds the contact terms of the Newton Hessian to aug
+// (Stepper::solve).  Both read con_m1 / con_m2 / con_pos and form the same r = pos - com, w = cd x r and
+// jp = cd[3:] + w, so a contact's operands are read once and its round trip is paid once.  Each accumulator keeps
+// the guard and the operation order it has in a loop of its own: J'f takes every contact with in1 != in2, the
+// Hessian those of them with m1 == 0 (then in1 = 0 and in2 = bit(m2, sl) = 1).
+template <typename T>
+struct ConF { uint32_t m1, m2; T p[3], f[3]; };
+template <typename T>
+struct ConFU { uint32_t m1, m2; T p[3], f[3], U[6]; };
+template <bool AUG, typename T, typename C>
+__device__ __forceinline__ T jtf_walk(MPtr<T> m, const Scratch<T, C>& s, int sl, const T* cd, T* aug) {
+  T acc = 0;
+  using CV = std::conditional_t<AUG, ConFU<T>, ConF<T>>;
+  for_active_contacts_ld<T, C>(s.con_act, [&](int c) {
+    CV v;
+    v.m1 = s.con_m1[c]; v.m2 = s.con_m2[c];
+    for (int k = 0; k < 3; k++) { v.p[k] = s.con_pos[c][k]; v.f[k] = s.con_F[c][k]; }
+    if constexpr (AUG)
+      for (int k = 0; k < 6; k++) v.U[k] = s.con_U[c][k];
+    return v;
+  }, [&](int, const CV& v) {
+    const int in2 = bit(v.m2, sl), in1 = bit(v.m1, sl);
+    if (in1 != in2) {
+      T r[3] = {v.p[0] - s.com[0], v.p[1] - s.com[1], v.p[2] - s.com[2]};
+      T w[3];
+      cross3(cd, r, w);
+      T jp[3] = {cd[3] + w[0], cd[4] + w[1], cd[5] + w[2]};
+      T x = dot3(jp, v.f);
+      acc += in2 ? x : -x;
+      if constexpr (AUG) {
+        if (v.m1 == 0u) {   // plane contacts; body-body ones enter the Hessian as dense rank-1 rows
+          const T* U = v.U;
+          T z[3] = {U[0] * jp[0] + U[3] * jp[1] + U[4] * jp[2], U[3] * jp[0] + U[1] * jp[1] + U[5] * jp[2],
+                    U[4] * jp[0] + U[5] * jp[1] + U[2] * jp[2]};
+          T rz[3];
+          cross3(r, z, rz);
+          for (int k = 0; k < 3; k++) { aug[k] += rz[k]; aug[3 + k] += z[k]; }
+        }
+      }
+    }
+  });
+  return jtf_tail(m, s, sl, acc);
+}
+template <typename T, typename C>
+__device__ __forceinline__ T jtf_lane(MPtr<T> m, const Scratch<T, C>& s, int sl, const T* cd) {
+  return jtf_walk<false>(m, s, sl, cd, (T*)nullptr);
+}
+template <typename T, typename C>
+__device__ __forceinline__ T jtf_aug_lane(MPtr<T> m, const Scratch<T, C>& s, int sl, const T* cd, T (&aug)[6]) {
+  return jtf_walk<true>(m, s, sl, cd, aug);
 }
 
 }  // namespace

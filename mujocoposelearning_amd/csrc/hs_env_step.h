@@ -52,7 +52,7 @@ __device__ __forceinline__ void physics_step(Stepper<T, NV, C>& st, KPtr<T> k, T
   bool bv = sl < m->nv && isbad(s.qvel[sl]);
   if (hballot(bq, up)) { warn[WARN_BADQPOS]++; reset_state(m, s, sl, time, xws); }
   else if (hballot(bv, up)) { warn[WARN_BADQVEL]++; reset_state(m, s, sl, time, xws); }
-  T D[C::RPL], ar[C::RPL], rc[C::RPL];
+  T D[C::RPL], ar[C::RPL], rc[C::RPL], jar0[C::RPL];
   int rd[C::RPL];
   for (int attempt = 0; attempt < 2; attempt++) {
     HS_STAMP(st.clk, 0);
@@ -68,12 +68,12 @@ __device__ __forceinline__ void physics_step(Stepper<T, NV, C>& st, KPtr<T> k, T
     HS_STAMP(st.clk, 2);
     st.velocity_forces();
     HS_STAMP(st.clk, 3);
-    if (st.rows(D, ar, rd, rc)) warn[WARN_OVERFLOW]++;
+    if (st.template rows<!PGS>(D, ar, rd, rc, xws, jar0)) warn[WARN_OVERFLOW]++;
     HS_STAMP(st.clk, 5);
     if constexpr (PGS)
       st.solve_pgs(xws, opaque(k)->p.max_newton, D, ar, rd, rc, *pc);
     else
-      st.solve(xws, opaque(k)->p.max_newton, sizeof(T) == 8 ? T(1e-13) : T(1e-7), D, ar, rd, rc);
+      st.solve(xws, opaque(k)->p.max_newton, sizeof(T) == 8 ? T(1e-13) : T(1e-7), D, ar, rd, rc, jar0);
     bool ba = sl < m->nv && isbad(st.qacc);
     bool redo = hballot(ba, up) != 0 && attempt == 0;
     if (__ballot(redo) == 0) break;          // wave-uniform loop control

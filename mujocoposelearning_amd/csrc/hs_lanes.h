@@ -36,6 +36,10 @@ struct Cap {
   // the chain / subtree sums read their operands a group of bits at a time (for_bits_g below): the same
   // instances again, and a constant of its own for the same reason
   static constexpr bool GROUPS = LT;
+  // the Newton solve walks the active contacts once per iteration for J'f and the Hessian's contact terms
+  // (jtf_aug_lane), and the row slots' J x operands are read in one batch (rows_Jx, hs_contacts.h): the same
+  // instances again (profiles/newton_walks.md)
+  static constexpr bool WALKS = LT;
   static_assert((NCON % HL == 0 || HL % NCON == 0) && NEFC % HL == 0, "capacity in whole half-waves");
 };
 // resident tier per precision (hs_model.h).  The fp64 instances keep the lane table in LDS: at one wave

@@ -80,6 +80,14 @@ struct Scratch {
                              sizeof(KinTail<T>) <= sizeof(T) * C::CON * 9),
                 "the near-pair list fits con_F, past the KinTail over con_v / con_U");
   __device__ __forceinline__ uint32_t* near_list() { return reinterpret_cast<uint32_t*>(&con_F[0][0]); }
+  // The second body-velocity set of the C::WALKS instances' rows() (chain_vel2, hs_contacts.h: J qacc_warmstart
+  // beside J qvel in u.n.bvel) lies in u.n.cfrc, which has bvel's shape.  u.n.cfrc is dead for the whole of
+  // rows(): its only writer is post_constraint, after the solve, and its readers (obs / reward / commit with
+  // full_state) run after the last substep's post_constraint and before the next kinematics, which overwrites
+  // the union anyway (u.k).  The RNE member u.r lies over the same bytes and is last read at the end of
+  // velocity_forces (csub -> qfrc_smooth), before rows(); u.n.cb (the Cholesky column pairs, between bvel and
+  // cfrc) is first written in the solve.  rows() reads the set back (contact_vel) before it returns, so nothing
+  // of it is live when the solve starts.  No LDS is added.
   union {   // phase-local arrays (aliased)
     Kin k;                                                        // kinematics + collision
     struct { T crb[MAXBODY][10]; T buf[MAXDOF][6]; } c;          // composite rigid body

@@ -450,8 +450,15 @@ struct Stepper {
     WSYNC();
   }
 
-  // mj_makeConstraint + mj_makeImpedance + reference (aref); row q of this lane: r = sl + 32 q
-  __device__ __forceinline__ int rows(T (&D)[C::RPL], T (&ar)[C::RPL], int (&rd)[C::RPL], T (&rc)[C::RPL]) {
+  // mj_makeConstraint + mj_makeImpedance + reference (aref); row q of this lane: r = sl + 32 q.
+  // NEWTON (the Newton instances with C::WALKS): the rows' J x operands are read in one batch (rows_Jx), and the
+  // chain walk behind J qvel also sums J xws (xws = qacc_warmstart, both known here), so that the initial
+  // jar = J xws - aref of solve() comes out of this phase (jar0) and solve() walks no chain at its entry.
+  // The PGS instances (NEWTON = false) keep the one-vector text.
+  template <bool NEWTON>
+  __device__ __forceinline__ int rows(T (&D)[C::RPL], T (&ar)[C::RPL], int (&rd)[C::RPL], T (&rc)[C::RPL], T xws,
+                                      T (&jar0)[C::RPL]) {
+    constexpr bool WK = C::WALKS && NEWTON;
     phase_begin();
     damp = sl < NV ? HS_LT(C, m).dof_damping[sl] : T(0);
     int overflow = 0;
@@ -525,13 +532,23 @@ struct Stepper {
       }
     }
     if (sl == 0) { s.ncon = ncon; s.nefc = nrow; s.nlim = nlim; s.njl = njl; }
-    if (sl < NV) s.vx[sl] = s.qvel[sl];
-    WSYNC();
-    map_vx<NV>(s, sl, nb, chain_mask<C>(m, sl, nb));     // row velocities J qvel for aref
+    if constexpr (WK) {
+      if (sl < NV) s.vx[sl] = xws;      // s.vx = qacc_warmstart (solve() starts from it); J qvel reads s.qvel
+      WSYNC();
+      chain_vel2<NV>(s, sl, nb, chain_mask<C>(m, sl, nb));
+      contact_vel(s, sl, s.u.n.bvel);                      // con_v of J qvel
+    } else {
+      if (sl < NV) s.vx[sl] = s.qvel[sl];
+      WSYNC();
+      map_vx<NV>(s, sl, nb, chain_mask<C>(m, sl, nb));     // row velocities J qvel for aref
+    }
+    // (WK) aref's operands, until the batch of J qvel is read
+    [[maybe_unused]] T rB[WK ? C::RPL : 1], rKi[WK ? C::RPL : 1], rpm[WK ? C::RPL : 1];
 #pragma unroll
     for (int q = 0; q < C::RPL; q++) {
       int r = sl + HL * q;
       D[q] = 0;
+      if constexpr (WK) { rB[q] = 0; rKi[q] = 0; rpm[q] = 0; }
       ar[q] = 0;
       rd[q] = 0;
       rc[q] = 0;
@@ -593,18 +610,36 @@ struct Stepper {
         T R = rscale * fmax(T(1e-15), (1 - imp) * dA * recip(imp));
         D[q] = recip(R);
         s.row_D[r] = D[q];
-        ar[q] = -B * row_Jx(m, s, rd[q], rc[q]) - K * imp * (pos - margin);
+        if constexpr (WK) { rB[q] = B; rKi[q] = K * imp; rpm[q] = pos - margin; }
+        else ar[q] = -B * row_Jx(m, s, rd[q], rc[q]) - K * imp * (pos - margin);
       }
       uint32_t dm = hballot(dense, up);
       if (sl == 0) s.dense_mask[q] = dm;
+    }
+    if constexpr (WK) {
+      bool vr[C::RPL];
+      T jx[C::RPL];
+#pragma unroll
+      for (int q = 0; q < C::RPL; q++) vr[q] = sl + HL * q < nrow;
+      rows_Jx(m, s, s.qvel, vr, rd, rc, jx);
+#pragma unroll
+      for (int q = 0; q < C::RPL; q++)
+        if (vr[q]) ar[q] = -rB[q] * jx[q] - rKi[q] * rpm[q];
+      WSYNC();
+      contact_vel(s, sl, s.u.n.cfrc);                      // con_v of J qacc_warmstart
+      rows_Jx(m, s, s.vx, vr, rd, rc, jx);
+#pragma unroll
+      for (int q = 0; q < C::RPL; q++) jar0[q] = vr[q] ? jx[q] - ar[q] : T(0);
     }
     WSYNC();
     return overflow;
   }
 
   // primal Newton (mj_solNewton semantics), warm-started; x = qacc
+  // jar0: the initial jar = J xws - aref from rows<true>() where it sums two vectors per chain walk
   __device__ __forceinline__ void solve(T xws, int maxit, T tol, const T (&D)[C::RPL], const T (&ar)[C::RPL],
-                                        const int (&rd)[C::RPL], const T (&rc)[C::RPL]) {
+                                        const int (&rd)[C::RPL], const T (&rc)[C::RPL], const T (&jar0)[C::RPL]) {
+    constexpr bool WK = C::WALKS;
     phase_begin();
     const int nefc = s.nefc;
     T x = sl < NV ? xws : T(0);
@@ -617,10 +652,15 @@ struct Stepper {
     if (sl < NV) s.vx[sl] = x;
     WSYNC();
     T Mx = matvec_lds(Mr, s.vx);     // kept current below (Mx += alpha M s)
-    map_vx<NV>(s, sl, nb, bch);
     T jar[C::RPL], Js[C::RPL];
+    if constexpr (WK) {
 #pragma unroll
-    for (int q = 0; q < C::RPL; q++) jar[q] = vr[q] ? row_Jx(m, s, rd[q], rc[q]) - ar[q] : T(0);
+      for (int q = 0; q < C::RPL; q++) jar[q] = jar0[q];
+    } else {
+      map_vx<NV>(s, sl, nb, bch);
+#pragma unroll
+      for (int q = 0; q < C::RPL; q++) jar[q] = vr[q] ? row_Jx(m, s, rd[q], rc[q]) - ar[q] : T(0);
+    }
     HS_STAMP(clk, 6);
     bool done = false;      // this half-wave's solver has converged
     int it = 0;
@@ -637,7 +677,12 @@ struct Stepper {
       WSYNC();
       contact_aggregates(m, s, sl);
       HS_STAMP(clk, 7);
-      T jtf = jtf_lane(m, s, sl, cd);
+      // the contact terms of the Hessian come out of J'f's walk over the active contacts (WK), ahead of the
+      // convergence test: on the converging iteration they are dropped (the walk costs, not the FMAs)
+      T aug[6] = {0, 0, 0, 0, 0, 0};
+      T jtf;
+      if constexpr (WK) jtf = jtf_aug_lane(m, s, sl, cd, aug);
+      else jtf = jtf_lane(m, s, sl, cd);
       T g = sl < NV ? Mx - fsmooth - jtf : T(0);
       const T gn2 = hsum(g * g);                 // |g| scale < tol, squared (no sqrt on the chain)
       const bool conv = scale * scale * gn2 < tol * tol;
@@ -649,10 +694,9 @@ struct Stepper {
       T hdinv = 0, hdiag = 0;
       // Hessian lower rows: M + contact (tree form) + joint limits (diag) + dense rank-1 rows
       {
-        T aug[6] = {0, 0, 0, 0, 0, 0};
         T dadd = 0;
         struct CU { uint32_t m1, m2; T p[3], U[6]; };
-        for_active_contacts_ld<T, C>(s.con_act, [&](int c) {
+        if constexpr (!WK) for_active_contacts_ld<T, C>(s.con_act, [&](int c) {
           CU v;
           v.m1 = s.con_m1[c]; v.m2 = s.con_m2[c];
           for (int k = 0; k < 3; k++) v.p[k] = s.con_pos[c][k];
@@ -775,8 +819,12 @@ struct Stepper {
       HS_STAMP(clk, 18);
       map_vx<NV>(s, sl, nb, bch);
       HS_STAMP(clk, 19);
+      if constexpr (WK) {
+        rows_Jx(m, s, s.vx, vr, rd, rc, Js);
+      } else {
 #pragma unroll
-      for (int q = 0; q < C::RPL; q++) Js[q] = vr[q] ? row_Jx(m, s, rd[q], rc[q]) : T(0);
+        for (int q = 0; q < C::RPL; q++) Js[q] = vr[q] ? row_Jx(m, s, rd[q], rc[q]) : T(0);
+      }
       HS_STAMP(clk, 16);
       // alpha = 1 is exact when no row changes state on [0, 1] (jar is linear in alpha)
       bool same1 = true;
@@ -836,7 +884,8 @@ struct Stepper {
     }
     WSYNC();
     niter = s.niter;
-    // final forces -> qfrc_constraint
+    // final forces -> qfrc_constraint (recomputed after an exit at the loop's top too, where they are in LDS
+    // already: skipping it there measured slower, profiles/newton_walks.md)
 #pragma unroll
     for (int q = 0; q < C::RPL; q++)
       if (vr[q]) s.row_f[sl + HL * q] = jar[q] < 0 ? -D[q] * jar[q] : T(0);
